@@ -19,18 +19,24 @@ train_real (the reference's real-view training step, morpheus.py:1147-1236: 2048
 ragged samples, albedo_normal, shipped regularisers, point loss, pose optimisation, occupancy refresh every 16 steps;
 --glue reference keeps the reference's own caller-side loss code), train_virtual (its virtual-view step, :1393-1408: a whole
 72^2 .. 180^2 novel view, random shading, SDS replaced by an injected pred_rgb gradient), density128 (forward-only
-model.density on a 128^3 grid: export_mesh / update_occ_grid's query, morpheus.py:367-408).  The default run
-(`python bench.py`) carries train_real (eager, HIP-graph replay, reference glue) and train_virtual (72^2, 180^2) beside the
-cfg3 headline under the keys `train_real` / `train_virtual`, per-kernel timers off.
+model.density on a 128^3 grid: export_mesh / update_occ_grid's query, morpheus.py:367-408).
+
+A plain run (`python bench.py --steps K --warmup W`) sets up ONE workload in this process, warms it up, times K steps with the
+per-kernel timers on and prints the line: nothing else.  `--full` adds everything else the benchmark measures: on a headline
+workload at N=1 with --mode auto, the two arithmetic modes each in its own process (the top-level numbers are then the faster
+one's), the same step replayed from a HIP graph, train_real (eager, HIP-graph replay, reference glue), train_virtual (72^2,
+180^2) and train_loop beside the cfg3 headline under those keys, per-kernel timers off; and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs below); the inputs are
+synthetic and seeded, so two builds run with the same arguments can be compared file by file.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- the step's LARGEST time item (the weight-gradient group included), SURVEY 8(d): top-level frac = algorithmic
                   FLOPs / HIP-event time / (dense peak of the matrix pipe the kernels issue on / slice products per fp32 MAC);
                   beside it the HBM view (parked bytes, algorithmic bytes, PMC traffic) and `per_kernel` with the same numbers
                   for every MLP entry of the step
-  cpu_baseline -- the CPU oracle ("port") timed on a bounded sample of the same workload
-  modes        -- N=1: the two arithmetic modes (b3 / f32, both fp32-faithful), each timed in its own process; the top-level
-                  numbers are the faster one's
+  cpu_baseline -- --full: the CPU oracle ("port") timed on a bounded sample of the same workload (null otherwise)
+  modes        -- --full, N=1: the two arithmetic modes (b3 / f32, both fp32-faithful), each timed in its own process; the
+                  top-level numbers are the faster one's
 plus roofline_hashgrid (HBM-bound hash-grid stage, as north_star asks) and a per-kernel time table.
 """
 from __future__ import annotations
@@ -81,8 +87,15 @@ def parse_args(argv=None):
                     help="train_real: caller-side loss code.  fused = this build's rewrite (one launch per loss group, one operand "
                          "scope per step); reference = the reference's own operator chains and a loss.item() per step around the "
                          "swapped-in render_rays -- what INTEGRATION.md's three edits alone give")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: on a headline workload at N=1 with --mode auto, every arithmetic mode "
+                         "in its own process, the HIP-graph replay and the training-step extras; the CPU baseline.  Without it "
+                         "the run times the one workload in this process (--mode auto: MORPHEUS_MLP or the library default, b3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, render outputs, every "
+                         "parameter and gradient) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default run only: skip the extra workloads (train_real eager / replayed / reference glue, train_virtual) "
+                    help="--full only: skip the extra workloads (train_real eager / replayed / reference glue, train_virtual) "
                          "that ride beside the cfg3 headline")
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -205,7 +218,8 @@ def build_stub(args, rank, world):
         return loss
 
     return dict(step=step, rays_per_step=args.rays, bucket=bucket, desc="stub (CPU toy step, plumbing test only)",
-                samples=lambda: args.rays * args.samples)
+                samples=lambda: args.rays * args.samples,
+                named_params=lambda: [("table", table)] + [("net." + n, p) for n, p in net.named_parameters()])
 
 
 def build_render_workload(args, rank, world, dev):
@@ -238,6 +252,7 @@ def build_render_workload(args, rank, world, dev):
     if world > 1 and not args.no_overlap:
         bucket.overlap_early([model.encoder.embeddings, model.encoder_c.embeddings])
     shading = "albedo_normal" if args.workload == "cfg3b" else "albedo"
+    last = {}
 
     def step():
         bucket.zero()
@@ -246,12 +261,15 @@ def build_render_workload(args, rank, world, dev):
         loss.backward()
         bucket.allreduce_mean()
         opt.step()
+        if args.dump_outputs:
+            last["res"] = res
         return loss
 
     desc = ("snoopy.yaml full deform field" + (" + FD normals (albedo_normal)" if args.workload == "cfg3b" else "")
             if not cano else "snoopy.yaml canonical field only") + \
         f", {N} rays x {S} samples per GPU, fwd+bwd+Adam ({args.workload}" + (", one frame per rank = cfg5" if world > 1 else "") + ")"
-    return dict(step=step, rays_per_step=N, bucket=bucket, desc=desc, samples=lambda: N * S, frame=frame)
+    return dict(step=step, rays_per_step=N, bucket=bucket, desc=desc, samples=lambda: N * S, frame=frame, last=last,
+                named_params=model.named_parameters)
 
 
 def build_train_real(args, rank, world, dev):
@@ -323,7 +341,7 @@ def build_train_real(args, rank, world, dev):
                                  "`with model.operand_scope():` around the step"}[args.glue]
     return dict(step=step, rays_per_step=args.rays, bucket=bucket, desc=desc + (", captured in a HIP graph" if graphed else ""),
                 samples=lambda: (sum(sample_log[-args.steps:]) / max(len(sample_log[-args.steps:]), 1)), occupied=occ,
-                graphed=graphed, glue=args.glue)
+                graphed=graphed, glue=args.glue, named_params=model.named_parameters)
 
 
 def pretouch_vram(dev, fraction: float = 0.85):
@@ -408,7 +426,7 @@ def build_train_virtual(args, rank, world, dev):
     return dict(step=step, rays_per_step=res * res, bucket=bucket, desc=desc,
                 samples=lambda: (sum(sample_log[-args.steps:]) / max(len(sample_log[-args.steps:]), 1)), occupied=occ,
                 shadings=lambda: {k: shade_log[-args.steps:].count(k) for k in sorted(set(shade_log[-args.steps:]))},
-                pretouch=touched)
+                pretouch=touched, named_params=model.named_parameters)
 
 
 def build_train_loop(args, rank, world, dev):
@@ -485,7 +503,7 @@ def build_train_loop(args, rank, world, dev):
     return dict(step=step, rays_per_step=rays_per_iter, bucket=bucket,
                 desc=desc + ("; real-view steps 2..%d of an iteration replayed from HIP graphs" % n_real if graphed else ""),
                 samples=lambda: (sum(sample_log[-args.steps:]) / max(len(sample_log[-args.steps:]), 1)), occupied=occ, glue=args.glue,
-                iters=True, graphed=graphed)
+                iters=True, graphed=graphed, named_params=model.named_parameters)
 
 
 def build_density128(args, rank, world, dev):
@@ -508,7 +526,8 @@ def build_density128(args, rank, world, dev):
         return tot
 
     return dict(step=step, rays_per_step=pts.shape[0], bucket=None, samples=lambda: pts.shape[0],
-                desc=f"forward-only model.density (warp + both hash grids + sdf/colour nets) on {R}^3 grid points, no_grad")
+                desc=f"forward-only model.density (warp + both hash grids + sdf/colour nets) on {R}^3 grid points, no_grad",
+                named_params=model.named_parameters)
 
 
 # ------------------------------------------------------------------------------------------------ roofline
@@ -709,6 +728,7 @@ def run_one(args):
     rank, local, world = mdist.init_from_env()
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    torch.manual_seed(rank)          # the training steps' random batches: the same arguments give the same inputs
     if stub:
         dev = torch.device("cpu")
         wl = build_stub(args, rank, world)
@@ -905,7 +925,39 @@ def run_one(args):
     out["cpu_baseline"] = None
     if world > 1:
         dist.destroy_process_group()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl, loss)
     return out
+
+
+def dump_outputs(out_dir, wl, loss, budget_bytes=64_000_000):
+    """--dump-outputs: what the LAST timed step handed its caller -- the loss, the render outputs (render workloads), every
+    parameter after the optimiser step and its gradient -- as <out_dir>/<name>.npy in float32 (float64 stays float64).  An array
+    above the per-array cap that keeps the total under 64 MB is replaced by a fixed sample of its flattened elements (seed 0,
+    sorted indices), so two builds run with the same arguments write files of the same shapes to compare."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss}
+    for k, v in (wl.get("last") or {}).get("res", {}).items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays["out." + k] = v
+    for name, p in wl["named_params"]():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    cap = max(a.size for a in host.values())
+    while sum(min(a.size, cap) * a.itemsize for a in host.values()) > budget_bytes:
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ both arithmetic modes
@@ -931,24 +983,33 @@ def _run_child(flags, mode, timeout, env=None):
         except OSError:
             pass
 
+
+def _drop_flags(argv, names):
+    """argv without the given value-taking flags (`--flag value` and `--flag=value`)."""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a in names:
+            skip = True
+        elif not a.startswith(tuple(n + "=" for n in names)):
+            out.append(a)
+    return out
+
+
 FAITHFUL = ("b3", "f32")      # modes whose operands keep all 24 significand bits of the reference's fp32 (models/decoders.py:59-64)
 
 
 def run_modes(args, argv):
-    """N = 1, headline workloads, --mode auto: time every arithmetic mode in its OWN process (fresh allocator, timers and
+    """--full, N = 1, headline workloads, --mode auto: time every arithmetic mode in its OWN process (fresh allocator, timers and
     operand caches; the same isolation the CPU baseline gets) and report them side by side.  The top-level line is the
     faster of the two (both keep all 24 operand bits; `modes_ms_per_step` carries both)."""
-    base, skip = [], False
-    for a in argv:                   # every child gets its own --detail-out
-        if skip:
-            skip = False
-        elif a == "--detail-out":
-            skip = True
-        elif not a.startswith("--detail-out="):
-            base.append(a)
+    base = _drop_flags(argv, ("--detail-out", "--dump-outputs"))      # every child gets its own
+    dump = args.dump_outputs
     results, errors = {}, {}
     for m in args.modes.split(","):
-        r, err = _run_child(base + ["--mode", m, "--no-cpu-baseline"], m, 900)
+        r, err = _run_child(base + ["--mode", m, "--no-cpu-baseline"] +
+                            (["--dump-outputs", os.path.join(dump, f".mode_{m}")] if dump else []), m, 900)
         if r is None:
             errors[m] = err
         else:
@@ -957,6 +1018,13 @@ def run_modes(args, argv):
     if not faithful:
         raise SystemExit("bench.py: no fp32-faithful mode produced a result: " + json.dumps(errors))
     best = min(faithful, key=lambda m: results[m]["ms_per_step"])
+    if dump:                         # the headline's outputs are the faster mode's
+        import shutil
+        src = os.path.join(dump, f".mode_{best}")
+        for name in os.listdir(src):
+            os.replace(os.path.join(src, name), os.path.join(dump, name))
+        for m in args.modes.split(","):
+            shutil.rmtree(os.path.join(dump, f".mode_{m}"), ignore_errors=True)
     out = dict(results[best])
     out["headline_mode"] = best
     out["headline_rule"] = ("value / ms_per_step / dtype / roofline / kernels are those of the faster fp32-faithful mode (b3: exact "
@@ -1122,15 +1190,18 @@ def compact_line(out, detail_path=None):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.dump_outputs:            # the ranks and the per-mode children run in ROOT: hand them an absolute path
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = _drop_flags(argv, ("--dump-outputs",)) + ["--dump-outputs", args.dump_outputs]
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args, argv))
     stub = bool(os.environ.get("MORPHEUS_BENCH_STUB"))
     headline = args.workload in ("cfg3", "cfg2", "cfg3b")
-    if args.gpus == 1 and args.mode == "auto" and headline and not stub and not args.graph:
+    if args.full and args.gpus == 1 and args.mode == "auto" and headline and not stub and not args.graph:
         out = run_modes(args, argv)
     else:
         out = run_one(args)
-        if out is not None and args.gpus == 1 and headline and not args.no_cpu_baseline and not stub:
+        if out is not None and args.full and args.gpus == 1 and headline and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_rays, args.samples)
             if out["cpu_baseline"]["value"]:
                 out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)

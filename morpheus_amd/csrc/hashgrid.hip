@@ -16,7 +16,9 @@
 //   * both tables (3.2 MB each) are L2-resident per XCD; gathers are 8-byte float2 loads.
 #include "common.h"
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 
 // explicit fmaf where the reference kernel (nvcc -fmad=true) fuses, nothing else contracted:
 // the CPU oracle does the same, so features agree to the last bit of the interpolation.
@@ -647,7 +649,7 @@ __global__ __launch_bounds__(BRK_THREADS, 8) void grid_fwd_brick_kernel(const fl
 template <int NEED_DX, bool STAGED>
 __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_kernel(
     const float2 *__restrict__ grad, const float *__restrict__ x, const float2 *__restrict__ emb, GridMeta meta, BrickMeta bm,
-    const int32_t *__restrict__ perm, const int32_t *__restrict__ brick_start, float *__restrict__ grad_emb,
+    const int32_t *__restrict__ perm, const int32_t *__restrict__ brick_start, long long *__restrict__ emb_acc, int acc_shift,
     float *__restrict__ grad_x, int L, int n_levels, float bound, float two_bound, const uint32_t *__restrict__ gmax_bits) {
     // per vertex: fixed-point sum of the x channel, of the y channel, and (d/dx forms) the vertex's table row -- 8-byte words.
     // (Interleaved or channel-major made no difference in a round-5 A/B.  The bank-conflict replays the counters show are NOT
@@ -665,6 +667,10 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     for (int i = threadIdx.x; i < BRK_NODES_MAX; i += BRK_THREADS) acc[W * i] = 0, acc[W * i + 1] = 0;
     float to_fx, from_fx;
     fx_scales(*gmax_bits, to_fx, from_fx);
+    // the call's headroom (acc_shift) goes into the scale every term is quantized with: each term is rounded once, on the same grid
+    // whichever work item of a split brick sums it, and every sum after that is exact
+    to_fx = ldexpf(to_fx, -acc_shift);
+    const float fx_lim = ldexpf(FX_LIMIT, -acc_shift);      // the clamp below saturates inside the same headroom
     const int l = threadIdx.x & 15, sub = threadIdx.x >> 4;
     // this lane's level
     const bool lev_on = l < n_levels;
@@ -749,8 +755,8 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
             // (the magic add is exact only below 2^51: a NaN / Inf gradient or a stale maximum word must saturate to ONE bounded
             //  contribution, not write arbitrary bit patterns into the brick's accumulators -- one v_med3_f32 per value, outside the
             //  corner loop; v_med3 returns the smallest operand when one is a NaN)
-            const double gxd = (double)__builtin_amdgcn_fmed3f(gr.x * to_fx, -FX_LIMIT, FX_LIMIT),
-                         gyd = (double)__builtin_amdgcn_fmed3f(gr.y * to_fx, -FX_LIMIT, FX_LIMIT);
+            const double gxd = (double)__builtin_amdgcn_fmed3f(gr.x * to_fx, -fx_lim, fx_lim),
+                         gyd = (double)__builtin_amdgcn_fmed3f(gr.y * to_fx, -fx_lim, fx_lim);
             // (Same-vertex collisions of the four points a wave carries are NOT what the atomics cost: with row k of the wave
             //  walking the corners in the order c ^ k -- four different vertices per instruction -- the kernel ran the same
             //  1.16 ms; without the atomics 0.77 ms.  It is the 64-bit atomic rate itself.)
@@ -799,7 +805,10 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
         }
     }
     __syncthreads();
-    // flush touched vertices: one global atomic per (vertex, channel) instead of one per (point, corner, channel).
+    // flush touched vertices: one global atomic per (vertex, channel) instead of one per (point, corner, channel).  The flush stays in
+    // fixed point: integer adds into the table-sized emb_acc commute, so the table gradient does not depend on the order in which the
+    // work items sharing a row finish (float atomics here made two runs of one step differ); grid_acc_finalize_kernel converts once.
+    // (the scale leaves acc_shift bits of headroom, so that a whole call's sum of a row stays inside the int64 range)
     // One flat loop over the brick's vertex slots (five rounds of the 1024 lanes) instead of one loop per level: eleven of the sixteen
     // levels have fewer than 256 slots, their rounds ran with three quarters of the lanes idle -- and the flush is instruction time, not
     // atomic throughput (round 6, same box, cfg3's two launches: shipped 1.08 ms, the same loop without its atomics 1.06, no flush 0.92;
@@ -824,10 +833,22 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
             const uint32_t sel = (uint32_t)fp[10];
             uint32_t row = ((cx + ym + zm) & sel) | ((cx ^ ym ^ zm) & (uint32_t)fp[9] & ~sel);
             if (__builtin_expect(fp[12] != 0, 0)) row %= (uint32_t)fp[11];
-            float *ge = grad_emb + ((size_t)fp[13] + row) * 2;
-            atomicAdd(ge + 0, (float)qx * from_fx);
-            atomicAdd(ge + 1, (float)qy * from_fx);
+            unsigned long long *ga = reinterpret_cast<unsigned long long *>(emb_acc + ((size_t)fp[13] + row) * 2);
+            atomicAdd(ga + 0, (unsigned long long)qx);
+            atomicAdd(ga + 1, (unsigned long long)qy);
         }
+    }
+}
+
+// grad_emb[i] += emb_acc[i] in the float scale of the call (from_fx of its max |grad|, times 2^acc_shift): one rounding per entry.
+__global__ void grid_acc_finalize_kernel(const long long *__restrict__ emb_acc, float *__restrict__ grad_emb, int64_t n, int acc_shift,
+                                         const uint32_t *__restrict__ gmax_bits) {
+    float to_fx, from_fx;
+    fx_scales(*gmax_bits, to_fx, from_fx);
+    const double scale = (double)from_fx * (double)(1LL << acc_shift);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const long long a = emb_acc[i];
+        if (a != 0) grad_emb[i] += (float)((double)a * scale);
     }
 }
 
@@ -967,10 +988,10 @@ extern "C" int mh_grid_encode_fwd_binned(const float *x, const float *emb, const
 
 extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, const float *emb, const int32_t *offsets_host,
                                          const int32_t *res_host, const int32_t *perm, const int32_t *brick_start,
-                                         float *grad_emb, float *grad_x, int32_t accumulate_dx, int64_t M, int32_t L,
-                                         int32_t n_levels, float bound, const uint32_t *gmax_bits, void *stream) {
+                                         float *grad_emb, int64_t *emb_acc, float *grad_x, int32_t accumulate_dx, int64_t M,
+                                         int32_t L, int32_t n_levels, float bound, const uint32_t *gmax_bits, void *stream) {
     if (M == 0) return MH_OK;
-    if (!grad || !x || !emb || !grad_emb || !perm || !brick_start || M < 0 || n_levels < 0 || n_levels > L || L != 16 ||
+    if (!grad || !x || !emb || !grad_emb || !emb_acc || !perm || !brick_start || M < 0 || n_levels < 0 || n_levels > L || L != 16 ||
         !(bound > 0.f))
         return MH_ERR_ARG;
     GridMeta meta;
@@ -982,6 +1003,12 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
     const unsigned work_items = (unsigned)(NBRK + M / BRK_CHUNK_SMALL + 1);
     // max|grad| (float bits): supplied by the producer of `grad` (mh_field_bwd_data computes it on the fly), else
     // reduced here into the scratch word behind the work-item table
+    // a table row receives at most 8 terms per point (hash collisions included), each at most 2^(FX_BITS - acc_shift) in fixed
+    // point (the scale and the NaN / Inf clamp of grid_bwd_brick_kernel): keep 8 M such terms inside +-2^62
+    int acc_shift = 0;
+    while (acc_shift < 40 && (double)M * 8.0 > std::ldexp(1.0, 62 - FX_BITS + acc_shift)) acc_shift++;
+    const int64_t n_acc = (int64_t)offsets_host[L] * 2;
+    if (!mh_zero_async(emb_acc, sizeof(int64_t) * (size_t)n_acc, mh_stream(stream))) return MH_ERR_LAUNCH;
     const uint32_t *gmax = gmax_bits;
     if (!gmax) {
         uint32_t *own = reinterpret_cast<uint32_t *>(const_cast<int32_t *>(brick_start)) + (2 * NBRK + 4);
@@ -992,7 +1019,8 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
 #define BRK_LAUNCH(DXMODE, STG)                                                                                                \
     hipLaunchKernelGGL((grid_bwd_brick_kernel<DXMODE, STG>), dim3(work_items), dim3(BRK_THREADS), 0, mh_stream(stream),       \
                        reinterpret_cast<const float2 *>(grad), x, reinterpret_cast<const float2 *>(emb), meta, bm, perm,     \
-                       brick_start, grad_emb, grad_x, (int)L, (int)n_levels, bound, 2.0f * bound, gmax)
+                       brick_start, reinterpret_cast<long long *>(emb_acc), acc_shift, grad_x, (int)L, (int)n_levels, bound,          \
+                       2.0f * bound, gmax)
     const bool staged = BRK_STAGE && M >= g_stage_min_points.load(std::memory_order_relaxed);
     if (grad_x && accumulate_dx) {
         // grad_x already holds a gradient of the same points (the field nets' d/dx): each visited point adds to its own row
@@ -1005,6 +1033,9 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
         BRK_LAUNCH(0, false);
     }
 #undef BRK_LAUNCH
+    MH_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grid_acc_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0,
+                       mh_stream(stream), reinterpret_cast<const long long *>(emb_acc), grad_emb, n_acc, acc_shift, gmax);
     MH_CHECK_LAUNCH();
     return MH_OK;
 }

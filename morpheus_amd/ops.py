@@ -232,8 +232,8 @@ def _grid_bwd(lib, x, embs, grads, o_p, r_p, L, n_levels, bound, need_dx, gmax_p
     """Embedding (and position) gradients of several tables evaluated at the same points: ONE brick binning shared by all
     tables.  gmax_ptrs[k]: device address of max|grads[k]| as float bits when its producer reduced it on the fly
     (mh_field_bwd_data), else None -> the kernel reduces it itself.
-    sums[k]: device ADDRESS of a running table-gradient sum this call adds into (the brick kernel's flush is an atomic add
-    anyway), or None -> a fresh zero-filled table.  g_x_into: a [M,3] gradient of the same points that the tables' d/dx is added
+    sums[k]: device ADDRESS of a running table-gradient sum this call adds into (the brick kernel's last pass adds to the
+    table), or None -> a fresh zero-filled table.  g_x_into: a [M,3] gradient of the same points that the tables' d/dx is added
     to in the kernel (brick path only), or None.
     -> (g_x or None, [g_emb; None where the gradient went into sums[k]])."""
     M = x.shape[0]
@@ -252,9 +252,10 @@ def _grid_bwd(lib, x, embs, grads, o_p, r_p, L, n_levels, bound, need_dx, gmax_p
                 binned = _bin_points(lib, x, bound)
             acc_dx = need_dx and g_x_total is not None
             g_x = g_x_total if acc_dx else (torch.empty_like(x) if need_dx else None)
+            emb_acc = torch.empty(emb.numel(), dtype=torch.int64, device=emb.device)     # the kernel's fixed-point table sum
             _e = TIMER.start()
             check(lib.mh_grid_encode_bwd_binned(ptr(grad), ptr(x), ptr(emb), o_p, r_p, ptr(binned[0]), ptr(binned[1]),
-                                                g_emb_p, ptr(g_x), int(acc_dx), M, L, n_levels, bound,
+                                                g_emb_p, ptr(emb_acc), ptr(g_x), int(acc_dx), M, L, n_levels, bound,
                                                 None if gmax_ptrs is None else gmax_ptrs[k], stream()),
                   "mh_grid_encode_bwd_binned")
             TIMER.stop("mh_grid_encode_bwd_binned", _e)
@@ -764,7 +765,7 @@ class _QueryAccumulator:
     Each query's backward produces (a) the raw weight / bias / beta gradient [24 929], (b) a full table gradient [419 640, 2] per
     hash table.  Handed to autograd one tensor per query, that is a zero fill per table and an add per tensor per extra query
     (about 30 launches of 0.1 - 3.4 MB per step).  Instead the queries ADD INTO ONE TENSOR EACH inside their own kernels
-    (mh_field_bwd_fused's reduction launch with accumulate = 1; the brick kernel's flush is an atomic add anyway) and return None
+    (mh_field_bwd_fused's reduction launch with accumulate = 1; the brick kernel's last pass adds into the table) and return None
     for token, beta and tables; `_PackOperands.backward` -- the node behind the token every query takes, which autograd runs only
     after ALL of them have run, None gradients included -- hands the finished sums to beta and the tables (its extra inputs) and
     maps the raw sum to the parameters.  Gradients that reach beta or a table along other paths are added by autograd as usual:

@@ -10,11 +10,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(args, extra_env=None):
+def _run(args, extra_env=None, cwd=ROOT):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MORPHEUS_BENCH_STUB"] = "1"
     env.update(extra_env or {})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, cwd=ROOT, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, cwd=cwd, capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -46,6 +46,26 @@ def test_world_size_mismatch_is_an_error():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE" in (out.stderr + out.stdout)
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, parameters and gradients as float .npy files, at most 64 MB; the inputs are
+    seeded, so the same arguments write the same arrays (the stub step is deterministic on the CPU).  A relative DIR is the caller's,
+    also through the rank launcher (whose ranks run in the repository root)."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(["--steps", "3", "--warmup", "1", "--rays", "32", "--dump-outputs", str(d), "--detail-out", str(tmp_path / "d.json")])
+        assert r["steps"] == 3 and r["cpu_baseline"] is None
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and {"loss.npy", "param.table.npy", "grad.table.npy"} <= set(names)
+    for n in names:
+        x, y = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64_000_000
+    assert float(np.load(dirs[1] / "loss.npy")) == np.float32(json.load(open(tmp_path / "d.json"))["config"]["loss"])
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", "32", "--dump-outputs", "rel"], cwd=tmp_path)
+    assert r["n_gpus"] == 2 and sorted(os.listdir(tmp_path / "rel")) == names
 
 
 def test_driver_line_is_compact_and_complete(tmp_path):

@@ -62,3 +62,26 @@ def test_optimisation_loop_with_replayed_real_view_steps():
         if hg["captures_inside_the_timed_region"] == 0 and abs(lg - le) <= 0.3 * abs(le):
             return
     assert False, tried
+
+
+def test_plain_headline_run_dumps_its_last_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` on the headline workload (cfg3): one process, K timed steps, no CPU baseline and no
+    other arithmetic mode; DIR holds the last timed step's render outputs, loss, parameters after Adam and their gradients, as finite
+    float .npy files whose loss is the line's."""
+    import numpy as np
+    d, detail = tmp_path / "out", tmp_path / "detail.json"
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d),
+                          "--detail-out", str(detail)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    lines = run.stdout.rstrip().splitlines()
+    assert run.returncode == 0 and lines and lines[-1].startswith("{"), (run.stderr or run.stdout)[-1500:]
+    line, full = json.loads(lines[-1]), json.load(open(detail))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "rays/s"
+    assert line["cpu_baseline"] is None and "modes" not in full and full["config"]["mlp_mode"] == "b3"
+    names = set(os.listdir(d))
+    assert {"loss.npy", "out.image.npy", "out.depth.npy", "param.encoder.embeddings.npy", "grad.encoder.embeddings.npy"} <= names
+    for n in names:
+        a = np.load(d / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    assert np.load(d / "out.image.npy").shape == (1, 16384, 3)
+    assert float(np.load(d / "loss.npy")) == np.float32(full["config"]["loss"])
+    assert sum(os.path.getsize(d / n) for n in names) <= 64_000_000

@@ -936,6 +936,30 @@ def test_field_large_batch_gradients(with_color):
         assert float((ga - gb).abs().max()) / scale <= 2e-5, (tuple(gb.shape), float((ga - gb).abs().max()) / scale)
 
 
+def test_grid_table_gradient_is_order_free():
+    """The brick-binned backward's table gradient does not depend on the order in which its workgroups finish or the points arrive:
+    a repeated call and the same points in shuffled order give the same bits.  Half the 2 M points sit in a small ball, so hot
+    bricks split into many chunks that share rows, as do the coarse levels' bricks; their fixed-point sums are flushed with
+    integer atomics and converted once (float atomics there made two runs of one training step differ)."""
+    from morpheus_amd import ops
+    emb, offs, res = _grid_setup()
+    g = torch.Generator().manual_seed(22)
+    M = 1 << 21
+    x = torch.cat([0.05 * torch.randn(M // 2, 3, generator=g), torch.rand(M // 2, 3, generator=g) * 2 - 1]).clamp(-1.0, 1.0)
+    gw = torch.randn(M, 32, generator=g)
+    perm = torch.randperm(M, generator=g)
+
+    def run(xx, ww):
+        e = emb.to(DEV).clone().requires_grad_(True)
+        (ops.grid_encode(xx.to(DEV), e, offs, res, 1.01) * ww.to(DEV)).sum().backward()
+        return e.grad
+
+    a, b, c = run(x, gw), run(x, gw), run(x[perm], gw[perm])
+    assert float(a.abs().max()) > 0
+    assert torch.equal(a, b), "repeated call: table gradient differs"
+    assert torch.equal(a, c), "shuffled points: table gradient differs"
+
+
 def test_grid_large_batch_gradients():
     """The brick-binned hash-grid backward at a batch where hot bricks split into many chunks and every workgroup loops
     (1.5 M points: two thirds along rays through the box -- dense near the near plane -- one third uniform): one call against
@@ -973,7 +997,7 @@ def test_grid_large_batch_gradients():
     finally:
         lib.mh_grid_stage_min_points(before)
     assert torch.equal(gx1, gx3)
-    # (the on-chip fixed-point sums are order-free; the flush of hot bricks' chunks adds floats to one row in arrival order)
+    # (the fixed-point sums, on chip and in the flush, are order-free: test_grid_table_gradient_is_order_free)
     assert float((ge1 - ge3).abs().max()) / float(ge3.abs().max()) <= 1e-6
     scale = float(ge2.abs().max())
     assert float((ge1 - ge2).abs().max()) / scale <= 1e-5, float((ge1 - ge2).abs().max()) / scale

@@ -27,7 +27,7 @@ def timeit(fn, n=5):
 def run(x, tag):
     M = x.shape[0]
     grad = torch.randn(M, 32, device=dev)
-    g_emb = torch.zeros_like(emb); g_x = torch.empty(M, 3, device=dev)
+    g_emb = torch.zeros_like(emb); g_x = torch.empty(M, 3, device=dev); emb_acc = torch.empty(emb.numel(), dtype=torch.int64, device=dev)
     ws = torch.empty(lib.mh_grid_bin_workspace_ints(), dtype=torch.int32, device=dev)
     perm = torch.empty(M, dtype=torch.int32, device=dev); bs = torch.empty(lib.mh_grid_bin_index_ints(), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream().cuda_stream
@@ -38,7 +38,7 @@ def run(x, tag):
     for nl in (16,):
         for dx, staged in ((False, False), (True, False), (True, True)):
             lib.mh_grid_stage_min_points(0 if staged else 1 << 40)        # d/dx forms: a brick's rows staged in LDS / gathered
-            t = timeit(lambda: lib.mh_grid_encode_bwd_binned(grad.data_ptr(), x.data_ptr(), emb.data_ptr(), P(o_p), P(r_p), perm.data_ptr(), bs.data_ptr(), g_emb.data_ptr(), g_x.data_ptr() if dx else None, 0, M, 16, nl, 1.01, None, st))
+            t = timeit(lambda: lib.mh_grid_encode_bwd_binned(grad.data_ptr(), x.data_ptr(), emb.data_ptr(), P(o_p), P(r_p), perm.data_ptr(), bs.data_ptr(), g_emb.data_ptr(), emb_acc.data_ptr(), g_x.data_ptr() if dx else None, 0, M, 16, nl, 1.01, None, st))
             print(f"   binned n_levels={nl:2d} dx={int(dx)}{' rows staged in LDS' if staged else (' rows gathered' if dx else '')}: {t:.3f} ms")
     lib.mh_grid_stage_min_points(knob)
     t = timeit(lambda: lib.mh_grid_encode_bwd(grad.data_ptr(), x.data_ptr(), emb.data_ptr(), P(o_p), P(r_p), g_emb.data_ptr(), None, M, 16, 16, 1.01, st), 2)
