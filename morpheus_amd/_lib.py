@@ -98,6 +98,9 @@ _SIGS = {
     "mh_render_loss_bwd": (ctypes.c_int, [_P] * 7 + [_I64, _F, _F, _F, _P, _P, _P, _P, _P]),
     "mh_graph_count_memset_nodes": (ctypes.c_int, [_P, _P, _P, _P]),
     "mh_graph_replace_memset_nodes": (ctypes.c_int, [_P, _P]),
+    "mh_mc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "mh_mc_count": (ctypes.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P]),
+    "mh_mc_emit": (ctypes.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -2508,6 +2508,7 @@ extern "C" const char *mh_status_string(int status) {
         case MH_OK: return "ok";
         case MH_ERR_ARG: return "invalid argument (null pointer, bad size or unsupported configuration)";
         case MH_ERR_LAUNCH: return "kernel launch failed (hipGetLastError)";
+        case MH_ERR_OVERFLOW: return "result count overflow (2^31 or more vertices or triangles)";
         default: return "unknown status";
     }
 }

@@ -1,0 +1,118 @@
+"""Mesh export on the device: export_mesh (morpheus.py:367-408) without the host round trip.
+
+The reference queries the SDF on a resolution^3 grid in S^3 sub-grids, copies every sub-grid to the host, runs
+mcubes.marching_cubes there, queries the colours at the vertices and writes the file with trimesh.  Here the volume stays on
+the device, marching cubes runs on the HIP kernels of csrc/mesh.hip (mh_mc_count + mh_mc_emit; conventions in
+include/morpheus_hip.h) and write_ply writes the binary PLY that Open3D reads (render_all_meshes, morpheus.py:431).
+"""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+
+
+def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
+    """volume: contiguous fp32 CUDA tensor [nx,ny,nz] -> (vertices float32 [V,3] in index space, triangles int64 [T,3]),
+    as mcubes.marching_cubes returns them (up to vertex order and winding).  One host synchronisation (to size the outputs)."""
+    require_gpu(volume)
+    if volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous():
+        raise MorpheusHipError(f"marching_cubes takes a contiguous float32 [nx,ny,nz] volume, got {volume.dtype} "
+                               f"{tuple(volume.shape)}")
+    lib = _lib.load()
+    nx, ny, nz = volume.shape
+    wbytes = lib.mh_mc_workspace_bytes(nx, ny, nz)
+    if wbytes < 0:
+        raise MorpheusHipError(f"marching_cubes: shape {tuple(volume.shape)} unsupported (each side >= 2, < 2^31 points)")
+    dev = volume.device
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    iso = float(isovalue)
+    s = stream()
+    check(lib.mh_mc_count(ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(counts), s), "mh_mc_count")
+    V, T = counts.tolist()
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
+    if V or T:
+        check(lib.mh_mc_emit(ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles), s), "mh_mc_emit")
+    return vertices, triangles.long()
+
+
+@torch.no_grad()
+def sdf_volume(model, resolution: int = 128, S: int = 128, t=None, cano: bool = False) -> torch.Tensor:
+    """The query of morpheus.py:381-395: model.density on torch.linspace(-1, 1, resolution)^3 in S^3 sub-grids, each
+    sub-grid's SDF written into a [res,res,res] device volume (no host copy)."""
+    dev = next(model.parameters()).device
+    X = Y = Z = torch.linspace(-1, 1, resolution).split(S)
+    sdf = torch.empty(resolution, resolution, resolution, dtype=torch.float32, device=dev)
+    for xi, xs in enumerate(X):
+        for yi, ys in enumerate(Y):
+            for zi, zs in enumerate(Z):
+                xx, yy, zz = torch.meshgrid(xs, ys, zs, indexing="ij")
+                pts = torch.cat([xx.reshape(-1, 1), yy.reshape(-1, 1), zz.reshape(-1, 1)], dim=-1)
+                val = model.density(pts.to(dev), t=t, cano=cano)
+                sdf[xi * S: xi * S + len(xs), yi * S: yi * S + len(ys), zi * S: zi * S + len(zs)] = \
+                    val["sdf"].reshape(len(xs), len(ys), len(zs))
+    return sdf
+
+
+@torch.no_grad()
+def extract_mesh(model, resolution: int = 128, S: int = 128, t=None, cano: bool = False, color_mesh: bool = True):
+    """export_mesh (morpheus.py:367-408) minus the file, on the device: sdf_volume, marching cubes at 0, vertices mapped to
+    [-1, 1], albedo at the vertices.
+    -> dict(vertices [V,3] fp32, triangles [T,3] int64, colors [V,3] fp32 or None, sdf [res,res,res] fp32)"""
+    sdf = sdf_volume(model, resolution, S, t, cano)
+    vertices, triangles = marching_cubes(sdf, 0.0)
+    vertices = vertices / (resolution - 1.0) * 2 - 1
+    colors = None
+    if color_mesh:
+        colors = model.density(vertices, t=t, cano=cano)["albedo"] if vertices.shape[0] else vertices.new_zeros(0, 3)
+    return {"vertices": vertices, "triangles": triangles, "colors": colors, "sdf": sdf}
+
+
+def write_ply(path: str, vertices, triangles, colors=None) -> None:
+    """Binary little-endian PLY: float x y z [uchar red green blue alpha], faces as `list uchar int vertex_indices`.
+    Colours in [0, 1] are stored as round(clip(c, 0, 1) * 255) with alpha 255."""
+    v = np.ascontiguousarray(_host(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(_host(triangles), dtype="<i4").reshape(-1, 3)
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
+            "property float x", "property float y", "property float z"]
+    if colors is not None:
+        c = np.rint(np.clip(_host(colors).astype(np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+        head += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
+        vrec = np.empty(v.shape[0], dtype=[("xyz", "<f4", 3), ("rgba", "u1", 4)])
+        vrec["xyz"] = v
+        vrec["rgba"][:, :3] = c
+        vrec["rgba"][:, 3] = 255
+    else:
+        vrec = v
+    head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", 3)])
+    frec["n"] = 3
+    frec["idx"] = f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def export_mesh(model, mesh_savepath: str, resolution: int = 128, S: int = 128, t=None, cano: bool = False,
+                color_mesh: bool = True) -> dict:
+    """export_mesh (morpheus.py:367-408): extract_mesh, then write_ply to mesh_savepath (its directory is created)."""
+    d = os.path.dirname(mesh_savepath)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    mesh = extract_mesh(model, resolution=resolution, S=S, t=t, cano=cano, color_mesh=color_mesh)
+    write_ply(mesh_savepath, mesh["vertices"], mesh["triangles"], mesh["colors"])
+    return mesh
+
+
+def _host(a) -> Optional[np.ndarray]:
+    if isinstance(a, torch.Tensor):
+        return a.detach().cpu().numpy()
+    return np.asarray(a)
