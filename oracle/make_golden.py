@@ -137,15 +137,15 @@ def probe_points(n, stream=300, scale=1.15):
     return synth.hash_tensor((n, 3), stream, scale)
 
 
-def grad_digest(named_grads):
-    """Compact gradient record: per-tensor L2 norm, sum, and 64 strided samples."""
+def grad_digest(named_grads, sample_dtype=np.float32):
+    """Compact gradient record: per-tensor L2 norm, sum, and 64 strided samples (stored as sample_dtype)."""
     out = {}
     for k, g in named_grads.items():
         g = g.detach().reshape(-1).double()
         idx = torch.linspace(0, g.numel() - 1, min(64, g.numel())).long()
         out[k + "|norm"] = np.float64(g.norm().item())
         out[k + "|sum"] = np.float64(g.sum().item())
-        out[k + "|samples"] = g[idx].float().numpy()
+        out[k + "|samples"] = g[idx].float().numpy() if sample_dtype == np.float32 else g[idx].numpy().astype(sample_dtype)
     return out
 
 
@@ -357,15 +357,18 @@ class DrawInjector:
     """Closed-form stand-ins for torch.rand / rand_like / randn_like while a reference (or HIP) function runs: the k-th
     draw of shape `shape` is synth.hash_tensor(shape, 8000 + k) (uniform: +0.5; normal: x 3.4 ~ unit variance), so the
     reference here and the HIP path on the GPU box see IDENTICAL random perturbations as long as they draw in the same
-    order with the same shapes (tests/util.py carries the same class)."""
+    order with the same shapes (tests/util.py carries the same class).  cast: applied to every draw (the float64 runs take the
+    fp32 draw VALUES in double)."""
 
-    def __init__(self, base=8000):
-        self.k, self.base = 0, base
+    def __init__(self, base=8000, cast=None):
+        self.k, self.base, self.cast = 0, base, cast
 
     def _next(self, shape, normal, device=None, dtype=None):
         self.k += 1
         v = synth.hash_tensor(tuple(shape), self.base + self.k, 0.5)          # [-0.5, 0.5)
         v = v * 3.4 if normal else v + 0.5
+        if self.cast is not None:
+            v = self.cast(v)
         return v.to(device) if device is not None else v
 
     def __enter__(self):
@@ -688,6 +691,71 @@ def _virtual_step_in_double(g, hw, S, tag):
         print("virtual step in double:", tag, prec, "loss", float(total), "draws", n_draws)
 
 
+def _fake_host(m, cfg, samples):
+    """The `self` of the unbound MorpheuS methods: model, preset sampler, config."""
+    import morpheus as ref_morpheus
+    sampler = _PresetSampler()
+    sampler.samples = samples
+    fake = types.SimpleNamespace(model=m, occupancy_grid=sampler, config=cfg, dataset=types.SimpleNamespace(num_frames=200),
+                                 global_step=1000, device="cpu")
+    fake.get_ortho_normal_dir = types.MethodType(ref_morpheus.MorpheuS.get_ortho_normal_dir, fake)
+    fake.get_normal_smoothness_loss = types.MethodType(ref_morpheus.MorpheuS.get_normal_smoothness_loss, fake)
+    return fake
+
+
+def real_view_loss(m, cfg, rays, smp, data, prec="f32"):
+    """The reference's real-view training call (morpheus.py:1147-1236 with real_view=True, optimize_pose=True): the background drawn
+    first (get_bg_color, :893-894), render_rays with the depth / mask supervision, then get_real_view_render_loss,
+    get_real_view_point_loss and get_regularization_loss, draws injected.  prec "f64": rays, samples, data and draws in double
+    (the draw VALUES are the fp32 ones); the model must be a double one (build_ref_model_f64).
+    -> (loss, n_draws, rec, res, terms): rec["keep"] / rec["angle_draw"] when normal_smoothness draws its angles on the points kept
+    inside the 1.1 sphere; terms = (render, point, regularisation) losses."""
+    import morpheus as ref_morpheus
+    cast = (lambda v: v.double() if torch.is_tensor(v) and v.is_floating_point() else v) if prec == "f64" else (lambda v: v)
+    o, d, t, rid = [cast(v) for v in rays]
+    N = o.shape[1]
+    data = {k: cast(v) for k, v in data.items()}
+    fake = _fake_host(m, cfg, tuple(cast(v) for v in smp))
+    rec = {}
+    with DrawInjector(cast=cast if prec == "f64" else None) as inj:
+        inner = fake.get_normal_smoothness_loss
+
+        def recording(rays_o, rays_d, rays_t, depth):
+            # which of the npts x N surface-band points the reference keeps (inside the 1.1 sphere, morpheus.py:543-549): it
+            # draws the perturbation angles on the KEPT points only; the HIP-side test hands them to the same points
+            off_draw = synth.hash_tensor((int(cfg["train"]["trunc"] * 100 + 1),), inj.base + inj.k + 1, 0.5) + 0.5
+            rec["keep"] = keep_mask_of_smoothness_points(depth.detach(), rays_o.detach(), rays_d.detach(), cfg["train"]["trunc"], off_draw)
+            rec["angle_draw"] = inj.k + 2
+            return inner(rays_o, rays_d, rays_t, depth)
+
+        fake.get_normal_smoothness_loss = recording
+        bg = torch.rand((N, 3))                                       # get_bg_color, real view (morpheus.py:893-894): draw 1
+        res = ref_morpheus.MorpheuS.render_rays(fake, o, d, t, rid, N, 1, bg_color=bg, ambient_ratio=1.0,
+                                                shading="albedo_normal", real_view=True, cano=False,
+                                                rays_depth=data["depth"].view(1, -1, 1), rays_mask=data["mask"].view(1, -1, 1),
+                                                optimize_pose=True)
+        n_draws = inj.k
+    B, H, W = 1, N, 1
+    pred_rgb, pred_depth, pred_mask, pred_normal, _ = ref_morpheus.MorpheuS.get_pred_from_outputs(fake, res, B, H, W)
+    gt_rgb, gt_depth, gt_mask = ref_morpheus.MorpheuS.get_gt_from_data(
+        fake, {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}, bg, B, H, W)
+    bce = torch.nn.functional.binary_cross_entropy
+    if prec == "f64":    # the mask loss's target is `gt_mask.float()` (morpheus.py:959): a 0 / 1 mask, the same values in double
+        torch.nn.functional.binary_cross_entropy = lambda x, y, *a, **k: bce(x, y.to(x.dtype), *a, **k)
+    try:
+        l_render = ref_morpheus.MorpheuS.get_real_view_render_loss(fake, pred_rgb, pred_depth, pred_mask, gt_rgb, gt_depth, gt_mask,
+                                                                   data["rays_o"], data["rays_d"])
+    finally:
+        torch.nn.functional.binary_cross_entropy = bce
+    l_point = ref_morpheus.MorpheuS.get_real_view_point_loss(fake, gt_rgb, gt_depth, gt_mask, data["rays_o"], data["rays_d"],
+                                                             data["rays_t"], res)
+    l_reg = ref_morpheus.MorpheuS.get_regularization_loss(fake, res, pred_normal, cano=False)
+    loss = l_render
+    loss = loss + l_point
+    loss = loss + l_reg
+    return loss, n_draws, rec, res, (l_render, l_point, l_reg)
+
+
 def gen_round5():
     """cfg4's STEP COMPOSITION (morpheus.py:1390-1424): one virtual-view backward and one real-view backward feeding torch.optim.Adam
     over model.get_params_all(lr) (:154-155), learning rates set by the reference's own update_learning_rate (:472-503) and, in the
@@ -720,13 +788,7 @@ def gen_round5():
     data_r = trainstep.sample_real_view_rays(frame, N_r, sel)
 
     def fake_of(m, cfg, samples):
-        sampler = _PresetSampler()
-        sampler.samples = samples
-        fake = types.SimpleNamespace(model=m, occupancy_grid=sampler, config=cfg, dataset=types.SimpleNamespace(num_frames=200),
-                                     global_step=1000, device="cpu")
-        fake.get_ortho_normal_dir = types.MethodType(ref_morpheus.MorpheuS.get_ortho_normal_dir, fake)
-        fake.get_normal_smoothness_loss = types.MethodType(ref_morpheus.MorpheuS.get_normal_smoothness_loss, fake)
-        return fake
+        return _fake_host(m, cfg, samples)
 
     def virtual_loss(m, cfg):
         fake = fake_of(m, cfg, smp_v)
@@ -738,35 +800,7 @@ def gen_round5():
                 ref_morpheus.MorpheuS.get_regularization_loss(fake, res, pred_normal, cano=False)), res
 
     def real_loss(m, cfg):
-        fake = fake_of(m, cfg, smp_r)
-        rec = {}
-        with DrawInjector() as inj:
-            inner = fake.get_normal_smoothness_loss
-
-            def recording(rays_o, rays_d, rays_t, depth):
-                # which of the npts x N surface-band points the reference keeps (inside the 1.1 sphere, morpheus.py:543-549): it
-                # draws the perturbation angles on the KEPT points only; the HIP-side test hands them to the same points
-                off_draw = synth.hash_tensor((int(cfg["train"]["trunc"] * 100 + 1),), inj.base + inj.k + 1, 0.5) + 0.5
-                rec["keep"] = keep_mask_of_smoothness_points(depth.detach(), rays_o.detach(), rays_d.detach(), cfg["train"]["trunc"], off_draw)
-                rec["angle_draw"] = inj.k + 2
-                return inner(rays_o, rays_d, rays_t, depth)
-
-            fake.get_normal_smoothness_loss = recording
-            bg = torch.rand((N_r, 3))                                     # get_bg_color, real view (morpheus.py:893-894): draw 1
-            res = ref_morpheus.MorpheuS.render_rays(fake, o_r, d_r, t_r, rid_r, N_r, 1, bg_color=bg, ambient_ratio=1.0,
-                                                    shading="albedo_normal", real_view=True, cano=False,
-                                                    rays_depth=data_r["depth"].view(1, -1, 1), rays_mask=data_r["mask"].view(1, -1, 1),
-                                                    optimize_pose=True)
-            n_draws = inj.k
-        B, H, W = 1, N_r, 1
-        pred_rgb, pred_depth, pred_mask, pred_normal, _ = ref_morpheus.MorpheuS.get_pred_from_outputs(fake, res, B, H, W)
-        gt_rgb, gt_depth, gt_mask = ref_morpheus.MorpheuS.get_gt_from_data(
-            fake, {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_r.items()}, bg, B, H, W)
-        loss = ref_morpheus.MorpheuS.get_real_view_render_loss(fake, pred_rgb, pred_depth, pred_mask, gt_rgb, gt_depth, gt_mask,
-                                                               data_r["rays_o"], data_r["rays_d"])
-        loss = loss + ref_morpheus.MorpheuS.get_real_view_point_loss(fake, gt_rgb, gt_depth, gt_mask, data_r["rays_o"], data_r["rays_d"],
-                                                                     data_r["rays_t"], res)
-        loss = loss + ref_morpheus.MorpheuS.get_regularization_loss(fake, res, pred_normal, cano=False)
+        loss, n_draws, rec, _, _ = real_view_loss(m, cfg, (o_r, d_r, t_r, rid_r), smp_r, data_r)
         return loss, n_draws, rec
 
     g["real|sel"] = sel.numpy().astype(np.int32)
@@ -839,6 +873,87 @@ def gen_round6():
     print("round6.npz", len(g), "arrays")
 
 
+# ----------------------------------------------------------------------------- round-7 fixture (round7.npz)
+# the real-view terms whose gradient passes through the finite-difference normals (the `plain` case turns them off)
+FD_NORMAL_TERMS = ("eik_weight", "ori_weight", "normal_smooth_2d", "normal_smooth_3d", "normal_smooth_3d_t", "normal_smoothness")
+ROUND7_FS_WEIGHT = 10.0      # `plain` turns the free-space term on (the shipped config has fs_weight 0) at the weight of sdf_loss
+
+
+def round7_config(cfg, case):
+    """The training config of a round-7 case: `full` is the reference's loop as shipped; `plain` has every term through the FD normals
+    off and the free-space loss on.  (shading stays albedo_normal: at ambient_ratio 1.0 the normals enter the colour with weight 0.)"""
+    if case == "plain":
+        for k in FD_NORMAL_TERMS:
+            cfg["train"][k] = 0.0
+        cfg["train"]["fs_weight"] = ROUND7_FS_WEIGHT
+    return cfg
+
+
+def gen_round7():
+    """The real-view training step (morpheus.py:946-1029, 1147-1236: real_view=True, optimize_pose=True, depth / mask supervision;
+    render, point and regularisation losses; backward) of the imported reference in fp32 AND in float64 on the same inputs, draws
+    injected (the f64 run takes the fp32 draw values in double), 1 024 rays of frame 25 x 64 samples, two cases (round7_config):
+        plain  every term through the FD normals off, fs_loss on: everything else of the step (RGB / mask / depth, sdf_loss, fs_loss,
+               the surface point loss, code_reg, pose) -- the HIP path is held to the reference's own fp32 round-off;
+        full   the step as the reference's loop runs it (normal_smooth_3d, normal_smoothness, ori_weight ...); the normal_smoothness
+               keep mask recorded (and equal in both precisions).
+    Stored per case and precision: the loss and its three groups, the in-render terms, image / depth / opacity, and grad_digest of
+    every parameter gradient (f64 samples in double)."""
+    from bench_support import trainstep
+    g = {}
+    hw, S, n_rays = 64, 64, 1024
+    sel = real_view_case("b", hw, S, n_rays)
+    rays = [v[:, sel] for v in synth.frame_rays(25, hw, hw)]
+    smp = ofield.uniform_samples(rays[0][0], rays[1][0], synth.ray_jitter(hw * hw)[sel], S, 1.01)
+    frame = trainstep.make_frames([25], hw, hw, "cpu")[0]
+    data = trainstep.sample_real_view_rays(frame, n_rays, sel)
+    g["sel"] = sel.numpy().astype(np.int32)
+    g["hw"], g["S"] = np.int32(hw), np.int32(S)
+    for case in ("plain", "full"):
+        keeps = {}
+        cfg = round7_config(ref_config(), case)
+        for k in FD_NORMAL_TERMS + ("fs_weight",):      # the HIP-side test applies these to its model's config
+            g[case + "|train|" + k] = np.float64(cfg["train"][k])
+        for prec in ("f32", "f64"):
+            if prec == "f32":
+                m, cfg = build_ref_model(synth.make_state("b"), 0.75)
+            else:
+                m, cfg = build_ref_model_f64(synth.make_state("b"), 0.75)
+                m.encoder.differentiable = m.encoder_c.differentiable = True
+            m.train()
+            cfg = round7_config(cfg, case)
+            m.zero_grad()
+            loss, n_draws, rec, res, terms = real_view_loss(m, cfg, rays, smp, data, prec)
+            loss.backward()
+            key = case + "|" + prec
+            g[key + "|n_draws"] = np.int32(n_draws)
+            g[key + "|loss"] = np.float64(float(loss))
+            for name, v in zip(("loss_render", "loss_point", "loss_reg"), terms):
+                g[key + "|" + name] = np.float64(float(v))
+            for lk in ("sdf_loss", "fs_loss", "loss_code", "loss_normal_perturb", "normal_reg"):
+                if lk in res and torch.is_tensor(res[lk]):
+                    g[key + "|" + lk] = np.float64(float(res[lk]))
+            dt = np.float64 if prec == "f64" else np.float32
+            for name in ("image", "depth", "weights_sum"):
+                g[key + "|" + name] = res[name].detach().numpy().astype(dt)
+            for kk, v in grad_digest({k: p.grad for k, p in m.named_parameters() if p.grad is not None}, dt).items():
+                g[key + "|grad|" + kk] = v
+            # the whole pose-gradient row of the frame (the 64 strided samples of the [200, 6] tensor hold one of its entries)
+            g[key + "|pose_grad_row"] = m.pose_array.data.grad[25].detach().numpy().astype(dt)
+            if "keep" in rec:
+                keeps[prec] = rec["keep"]
+                g[key + "|keep_bits"] = np.packbits(rec["keep"].numpy())
+                g[key + "|n_keep"] = np.int32(int(rec["keep"].sum()))
+                g[key + "|angle_draw"] = np.int32(rec["angle_draw"])
+            print("round7:", key, "loss", float(loss), "draws", n_draws, "kept", int(rec["keep"].sum()) if "keep" in rec else "-")
+        assert g[case + "|f32|n_draws"] == g[case + "|f64|n_draws"], case
+        assert (case == "full") == bool(keeps), case
+        if keeps:
+            assert torch.equal(keeps["f32"], keeps["f64"]), "fp32 and float64 keep different normal-smoothness points"
+    np.savez_compressed(os.path.join(OUT, "round7.npz"), **g)
+    print("round7.npz", len(g), "arrays", os.path.getsize(os.path.join(OUT, "round7.npz")), "bytes")
+
+
 def main():
     assert os.path.isdir(REF), "make_golden.py needs /root/reference (build container only)"
     os.makedirs(OUT, exist_ok=True)
@@ -856,6 +971,9 @@ def main():
     if "--round6-only" in sys.argv:        # round 6: the 72 x 72 virtual-view step in double (the others are unchanged)
         gen_round6()
         return
+    if "--round7-only" in sys.argv:        # round 7: the real-view step in fp32 and in double (the others are unchanged)
+        gen_round7()
+        return
     if "--extras-only" not in sys.argv:
         gen_operators()
         gen_model()
@@ -865,6 +983,7 @@ def main():
     gen_round4()
     gen_round5()
     gen_round6()
+    gen_round7()
 
 
 if __name__ == "__main__":

@@ -172,3 +172,106 @@ def test_float64_encoder_agrees_with_the_c_restatement():
             assert yb.dtype == torch.float64
             assert float((ya.double() - yb).abs().max()) < 5e-6 and float(yb.abs().max()) > 0.05
             assert torch.equal(ya == 0, yb == 0) or float(((ya == 0) != (yb == 0)).float().mean()) < 1e-4   # OOB points and skipped levels
+
+
+def _dydx_points():
+    """u in [0,1]^3 (plus a few just outside) where the clamp and the cells matter: the half-texel band at each of the six faces of
+    every level (u < 0.5 / res or u > 1 - 0.5 / res), the faces themselves (u = 0, u = 1), cell faces of the finest level (res 128)
+    and of level 5 (res 32), random interior points, and points just outside.  Every coordinate is a multiple of 2^-16 or one of
+    the exact values above, so that u * res - 0.5 is exact in fp32 as well as in double: the three implementations then place every
+    point in the same cell and differ by the round-off of the weights and differences only (a point within an fp32 ulp of a cell face
+    would otherwise switch cells between them, a discrete event that is not what this compares)."""
+    q = 2.0 ** -16
+    rnd = ((synth.hash_tensor((3000, 3), 9200, 0.5) + 0.5).double() / q).round() * q
+    band = rnd[:1200].clone()
+    for k in range(1200):                                             # 200 points per face: one axis in the band of level 0
+        ax, hi = (k // 200) % 3, (k // 600) == 1
+        v = float((synth.hash_tensor((1,), 9300 + k, 0.5) + 0.5).item()) * (0.5 / 16)
+        v = round(v / q) * q
+        band[k, ax] = 1.0 - v if hi else v
+    faces = rnd[1200:1500].clone()
+    for k in range(300):
+        faces[k, k % 3] = 0.0 if (k // 3) % 2 == 0 else 1.0
+    cells = rnd[1500:2100].clone()
+    cells[:300, 0] = (torch.floor(cells[:300, 0] * 128) + 0.5) / 128        # pos = u * 128 - 0.5 an integer: a cell face of level 15
+    cells[300:, 1] = (torch.floor(cells[300:, 1] * 32) + 0.5) / 32          # ... of level 5 (dense)
+    out = rnd[2100:2200].clone()
+    out[:50, 0] = 1.0 + q
+    out[50:, 2] = -q
+    u = torch.cat([band, faces, cells, out, rnd[2200:]])
+    assert torch.equal(u.float().double(), u)
+    return u
+
+
+def test_float64_encoder_input_gradient_follows_the_kernel_rule():
+    """The float64 yardstick's d/dx (oracle/hashgrid_f64.py) is the kernel's rule (gridencoder.cu:206-246: per axis, the sum over
+    the 4 corner pairs of w * (right - left) * res, the border clamp ignored; zero outside the box) -- the rule of oracle/hashgrid.c
+    and oracle/hashgrid_np.py -- not autograd's slope through the clamp, which is zero in the half-texel band at every face of the
+    box: compared to both fp32 restatements, per point, on the band at all six faces, the faces themselves, cell faces of a dense
+    and of a hashed level and points just outside, all 16 levels and the first 8 (max_level None / 0.5)."""
+    from oracle import hashgrid_np as hnp
+    from oracle.hashgrid import _OracleGridEncode
+    from oracle import hashgrid_f64
+    from oracle.hashgrid_f64 import grid_encode_f64
+    emb, offs, res, _ = make()
+    u = _dydx_points()
+    M = u.shape[0]
+    go = synth.hash_tensor((M, 32), 9201, 1.0)
+    offs_np, res_np, emb_np = offs.numpy(), res.numpy(), emb.numpy()
+    for ml, n_levels in ((None, 16), (0.5, 8)):
+        # the f64 grid through autograd, in world units with bound 0.5 (x = u - 0.5 exactly, dx/du = 1)
+        x = (u - 0.5).requires_grad_(True)
+        y = grid_encode_f64(x, emb.double(), offs.tolist(), res_np, 0.5, ml)
+        (y * go.double()).sum().backward()
+        g64 = x.grad.numpy()
+        # the numpy restatement, per level / axis / channel, contracted with the same output gradient
+        d_np = hnp.dy_du(u.float().numpy(), emb_np, offs_np, res_np, n_levels).astype(np.float64)
+        g_np = np.einsum("mldc,mlc->md", d_np, go.numpy().reshape(M, 16, 2).astype(np.float64))
+        # the C restatement's backward (its dydx buffer)
+        ut = u.float().requires_grad_(True)
+        (_OracleGridEncode.apply(ut, emb, offs, res, n_levels, True) * go).sum().backward()
+        g_c = ut.grad.numpy().astype(np.float64)
+        scale = np.abs(g_np).max()
+        assert scale > 1.0
+        # per point: the fp32 restatements carry ~1e-7 relative round-off of each of the 16 levels' slope (up to res 128 x 0.2)
+        tol = 2e-6 * scale
+        for name, other in (("hashgrid_np.dy_du", g_np), ("hashgrid.c dydx", g_c)):
+            bad = np.abs(g64 - other).max(-1) > tol
+            assert not bad.any(), (name, ml, int(bad.sum()), np.nonzero(bad)[0][:10], float(np.abs(g64 - other).max()))
+        # the per-level Jacobian too (not only its contraction), where the band lies: the first 1 500 points
+        d64 = hashgrid_f64.grid_dy_du_f64(u[:1500], emb.double(), offs.tolist(), res_np, n_levels).numpy()
+        assert np.abs(d64 - d_np[:1500]).max() <= 2e-6 * np.abs(d_np).max()
+        # the band is not vacuous: at the three lower faces the kernel keeps the slope of the border cell along the band's axis
+        # (autograd through the clamp: zero); at the upper faces the clamped right corner is the left one, zero in both; points
+        # outside get none
+        lower = g64[np.arange(600), np.arange(600) // 200]
+        assert (np.abs(lower) > 1e-3 * scale).mean() > 0.95
+        assert (g64[2100:2200] == 0).all() and (g_np[2100:2200] == 0).all()
+        assert (d_np[:, n_levels:] == 0).all()
+
+
+def test_float64_encoder_values_and_table_gradient():
+    """Values of the float64 grid unchanged by its backward (the same function with and without a graph), and its table gradient
+    (autograd's scatter) equal to hashgrid_np.backward_embeddings on the same points, dense and hashed levels, max_level None / 0.5."""
+    from oracle import hashgrid_np as hnp
+    from oracle.hashgrid_f64 import grid_encode_f64
+    emb, offs, res, _ = make()
+    u = _dydx_points()
+    M = u.shape[0]
+    go = synth.hash_tensor((M, 32), 9202, 1.0)
+    offs_np, res_np = offs.numpy(), res.numpy()
+    for ml, n_levels in ((None, 16), (0.5, 8)):
+        with torch.no_grad():
+            y0 = grid_encode_f64(u - 0.5, emb.double(), offs.tolist(), res_np, 0.5, ml)
+        e = emb.double().requires_grad_(True)
+        x = (u - 0.5).requires_grad_(True)
+        y = grid_encode_f64(x, e, offs.tolist(), res_np, 0.5, ml)
+        assert torch.equal(y.detach(), y0)
+        ref = hnp.forward(u.float().numpy(), emb.numpy(), offs_np, res_np, n_levels).astype(np.float64)
+        assert np.abs(y0.numpy() - ref).max() <= 1e-6 * np.abs(ref).max()
+        (y * go.double()).sum().backward()
+        g_np = hnp.backward_embeddings(u.float().numpy(), go.numpy(), offs_np, res_np, n_levels, emb.shape[0], 2)
+        ge = e.grad.numpy()
+        assert np.abs(ge - g_np).max() <= 1e-6 * np.abs(g_np).max()
+        rows_touched = np.abs(g_np).sum(-1) > 0
+        assert rows_touched[:int(offs[6])].any() and rows_touched[int(offs[6]):].any() == (n_levels > 6)
