@@ -815,8 +815,11 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     // profiles/r06_ab_grid_flush.txt).  A slot's level: the number of level starts at or below it (scalar compares); the level's
     // geometry: two 16-byte LDS reads of flush_par; j / n by multiply and shift (brk_div); the branch-free row index of grid_rows8.
     {
-        const int n_last = bm.n[n_levels - 1];
-        const int total = n_levels > 0 ? bm.lds_off[n_levels - 1] + n_last * n_last * n_last : 0;
+        int total = 0;                 // (no level switched on: nothing was accumulated, and there is no last level to index)
+        if (n_levels > 0) {
+            const int n_last = bm.n[n_levels - 1];
+            total = bm.lds_off[n_levels - 1] + n_last * n_last * n_last;
+        }
         for (int j = threadIdx.x; j < total; j += BRK_THREADS) {
             const long long qx = acc[W * j], qy = acc[W * j + 1];
             if (qx == 0 && qy == 0) continue;

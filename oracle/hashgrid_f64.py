@@ -106,6 +106,59 @@ def grid_dy_du_f64(u, emb, offsets, res_tab, n_levels):
     return out
 
 
+def _corner_terms(x, offsets, res_tab, bound, n_levels):
+    """Yields (level, rows [m] int64 numpy, w [m] float64 numpy, keep [m] int64 numpy: index of the point) for the 8 corners of every
+    level < n_levels, corner 7 first, over the points inside the box only -- the terms of the scatter grad_emb[row] += w * grad."""
+    u = (x.detach().double() + bound) / (2 * bound)
+    keep = torch.nonzero(((u >= 0) & (u <= 1)).all(-1))[:, 0]
+    u = u[keep]
+    keep = keep.numpy()
+    for l in range(n_levels):
+        res = int(res_tab[l])
+        T = int(offsets[l + 1]) - int(offsets[l])
+        hashed = res ** 3 > T
+        g, f = _level_geometry(u, res)
+        for corner in range(7, -1, -1):
+            w = torch.ones(u.shape[0], dtype=torch.float64)
+            c = []
+            for d in range(3):
+                if (corner >> d) & 1:
+                    w = w * f[:, d]
+                    c.append(torch.clamp(g[:, d] + 1, max=res - 1))
+                else:
+                    w = w * (1 - f[:, d])
+                    c.append(g[:, d])
+            yield l, (int(offsets[l]) + _rows(c, res, T, hashed)).numpy(), w.numpy(), keep
+
+
+def grid_table_grad_f64(x, grad, offsets, res_tab, bound, n_levels):
+    """x [M,3] (world units, any float type), grad [M, L*C] -> float64 [rows, C]: the table gradient of grid_encode_f64 without its
+    value graph, one pass of the scatter grad_emb[row] += w * grad.  The same bits as the autograd route (_GridEncodeF64): a
+    corner's terms are summed in point order from zero, as index_put_(accumulate) does, and the eight corner sums of a level are
+    added in the order autograd's engine runs their nodes (last built first); points outside the box add nothing there either."""
+    L = len(offsets) - 1
+    C = grad.shape[1] // L
+    gd = grad.detach().double().numpy().reshape(grad.shape[0], L, C)
+    out = np.zeros((int(offsets[-1]), C), dtype=np.float64)
+    first = [True] * L
+    for l, rows, w, keep in _corner_terms(x, offsets, res_tab, bound, n_levels):
+        lo, hi = int(offsets[l]), int(offsets[l + 1])
+        for ch in range(C):
+            s = np.bincount(rows - lo, weights=w * gd[keep, l, ch], minlength=hi - lo)
+            out[lo:hi, ch] = s if first[l] else out[lo:hi, ch] + s
+        first[l] = False
+    return torch.from_numpy(out)
+
+
+def grid_term_counts(x, offsets, res_tab, bound, n_levels):
+    """int64 [rows]: how many (point, corner) terms of the scatter land on each table row -- hash collisions and corners merged by
+    the border clamp counted once each, zero-weight corners included; points outside the box and levels >= n_levels count nothing."""
+    out = np.zeros(int(offsets[-1]), dtype=np.int64)
+    for l, rows, _, _ in _corner_terms(x, offsets, res_tab, bound, n_levels):
+        out += np.bincount(rows, minlength=out.shape[0])
+    return torch.from_numpy(out)
+
+
 class _GridEncodeF64(torch.autograd.Function):
     """Values of _encode; table gradient = autograd's scatter through _encode; input gradient = the kernel's rule."""
 
