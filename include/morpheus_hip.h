@@ -443,6 +443,68 @@ int mh_mc_count(const float *vol, int32_t nx, int32_t ny, int32_t nz, float iso,
 int mh_mc_emit(const float *vol, int32_t nx, int32_t ny, int32_t nz, float iso, void *workspace, float *vertices,
                int32_t *triangles, void *stream);
 
+/* ---- mesh rendering (render_all_meshes, morpheus.py:418-470: an Open3D window per frame there; csrc/raster.hip) -----------
+ * A triangle rasteriser over the arrays mh_mc_emit writes: vertices [V,3] fp32 world space, triangles [T,3] int32, optional
+ * colors [V,3] and normals [V,3] fp32.  Every fp32 expression below is evaluated operator by operator, round to nearest, no
+ * FMA, in the written order (tests/raster_oracle.py is written from this text).  A triangle with an index outside [0, V) is
+ * skipped everywhere.
+ *   camera: OpenCV camera space (x right, y down, z forward).  w2c_host: 12 HOST floats, row-major [3][4] = (R | t), the
+ *     inverse of the camera-to-world pose, formed by the caller in float64.  fx, fy, cx, cy as in mh_generate_rays: the
+ *     centre of pixel (i, j) = (column, row) is at screen coordinate (i + 0.5, j + 0.5).  (An OpenGL c2w becomes an OpenCV
+ *     one by negating its columns 1 and 2.)  H, W in [1, 16384].
+ *   vertex stage: Pc_r = ((w[r][0]*x + w[r][1]*y) + w[r][2]*z) + w[r][3];  sx = (fx*xc)/zc + cx, sy = (fy*yc)/zc + cy;
+ *     X = (int32) rintf(sx*256), Y likewise (8 sub-pixel bits, ties to even).  A triangle with a vertex that has
+ *     !(zc >= near) is dropped whole and counted in *clipped; so is one with a vertex whose rintf(sx*256) or rintf(sy*256)
+ *     is not below 2^23 in magnitude (NaN included).  On-screen coordinates are below 2^22, differences below 2^25, edge
+ *     products below 2^50: exact in int64.
+ *   coverage: A2 = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0) in int64; A2 == 0: dropped; A2 < 0: vertices 1 and 2 trade places
+ *     (both orientations are drawn).  For each edge e -> e+1 with (dx, dy) = (X[e+1]-X[e], Y[e+1]-Y[e]) and the centre
+ *     (px, py) = (256 i + 128, 256 j + 128):  E = dx*(py - Y[e]) - dy*(px - X[e]).  The centre is covered when, on all three
+ *     edges, E > 0, or E == 0 and (dy > 0 or (dy == 0 and dx > 0)).  The tie rule depends on the edge alone and holds for
+ *     exactly one of an edge's two directions, so two triangles on opposite sides of a shared edge never both cover and
+ *     never both miss a centre on it.  Candidates: i in [max((Xmin+127)>>8, 0), min((Xmax-128)>>8, W-1)], j likewise.
+ *   depth: camera-space z of the ray through the pixel centre and the triangle's plane, from the UNSNAPPED camera-space
+ *     vertices a, b, c in the caller's order: e1 = b-a, e2 = c-a, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y -
+ *     e1y*e2x), na = (nx*ax + ny*ay) + nz*az, dir = ((((float)i + 0.5f) - cx)/fx, (((float)j + 0.5f) - cy)/fy, 1),
+ *     z = na / ((nx*dirx + ny*diry) + nz).  A fragment with !(near <= z < inf) is dropped.  This is the camera-space z that
+ *     Open3D's capture_depth_float_buffer is understood to return (0 = background); NOT verified, Open3D was not available.
+ *   depth test: one uint64 per pixel, key = (bits(z) << 32) | t, global atomic minimum; z > 0 makes the bits monotone, equal
+ *     depths go to the lower triangle index.  depth, tri_id and clipped are therefore the same bytes run to run and for
+ *     any order of the launches' work.  They are pinned bit for bit by the numpy restatement.
+ *   resolve, one pixel: z, t from the key; P = (z*dirx, z*diry, z); r_k = vertex_k - P (k = a, b, c);
+ *     w_a = n . (r_b x r_c), w_b = n . (r_c x r_a), w_c = n . (r_a x r_b) (cross and dot in the forms above), s = (w_a + w_b)
+ *     + w_c, l_k = w_k / s (perspective correct: areas in 3-D; when an l_k is not finite -- a sliver whose sub-areas underflow
+ *     or cancel -- all three are 1/3);  attribute = (l_a*A_a + l_b*A_b) + l_c*A_c.
+ *     mode 0 "color": the interpolated colour, 0.7 grey without colors.  mode 1 "normal": the interpolated vertex normal,
+ *     rotated by R, normalised (|v| = sqrtf((x*x + y*y) + z*z), (0,0,1) when that is not in (0, inf)), then (n + 1)/2.
+ *     mode 2 "shaded": colour * (ambient + (1 - ambient) * |n^ . v^|), v^ = normalised -P: a head-light, back faces lit like
+ *     front faces.  Agreement with Open3D's lighting is not a goal.  Empty pixels: depth 0, tri_id -1, image = background.
+ *     The image and the normalised vertex normals are NOT pinned bit for bit: they are held to the error rule of DESIGN 4
+ *     (error against float64 <= 3 x the numpy-fp32 restatement's own, floor 2^-22).
+ *   vertex normals (Open3D compute_vertex_normals): c_t = (b-a) x (c-a) in world space (form above; a triangle with a
+ *     component that is not finite is skipped).  m = max |component| over the mesh, E its biased fp32 exponent field,
+ *     G = 2^(E-126) (a power of two strictly above m), q = G * 2^-40.  Each component is rounded once, k = llrint((double)c /
+ *     q), and added to its three vertices with 64-bit integer atomics: acc [3V + 1] DEVICE int64 holds the sums [V][3] and,
+ *     in its last word, the bits of m.  normal = normalise((float)k_x, (float)k_y, (float)k_z) as above.  The sums are
+ *     order-free: bit-identical run to run and under any permutation of the triangles.
+ * mh_raster_workspace_bytes: host only; -1 for H or W outside [1, 16384] or T outside [0, 2^31).
+ * mh_raster_depth: vertex stage, coverage and depth test into `workspace`; clipped: DEVICE int64, overwritten.  small_area:
+ *   a triangle whose clamped box holds more pixel centres than this is walked by whole wavefronts (queued on the device)
+ *   instead of one lane; <= 0 takes the default; results do not depend on it.  No host synchronisation.
+ * mh_raster_resolve: depth [H,W] fp32, tri_id [H,W] int32, image [H,W,3] fp32 from the workspace mh_raster_depth filled with
+ *   the same mesh and camera.  mode 1 and 2 need normals.  T == 0 or V == 0 is valid and gives the background.
+ * Bad arguments return MH_ERR_ARG before any launch. */
+int mh_mesh_vertex_normals(const float *vertices, int64_t V, const int32_t *triangles, int64_t T, int64_t *acc, float *normals,
+                           void *stream);
+int64_t mh_raster_workspace_bytes(int32_t H, int32_t W, int64_t T);
+int mh_raster_depth(const float *vertices, int64_t V, const int32_t *triangles, int64_t T, const float *w2c_host, float fx,
+                    float fy, float cx, float cy, int32_t H, int32_t W, float near, int32_t small_area, void *workspace,
+                    int64_t *clipped, void *stream);
+int mh_raster_resolve(const float *vertices, int64_t V, const int32_t *triangles, int64_t T, const float *colors,
+                      const float *normals, const float *w2c_host, float fx, float fy, float cx, float cy, int32_t H, int32_t W,
+                      int32_t mode, float ambient, float bg_r, float bg_g, float bg_b, const void *workspace, float *depth,
+                      int32_t *tri_id, float *image, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

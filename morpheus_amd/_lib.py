@@ -101,6 +101,11 @@ _SIGS = {
     "mh_mc_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "mh_mc_count": (ctypes.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P]),
     "mh_mc_emit": (ctypes.c_int, [_P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "mh_mesh_vertex_normals": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "mh_raster_workspace_bytes": (_I64, [_I32, _I32, _I64]),
+    "mh_raster_depth": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _F, _F, _F, _F, _I32, _I32, _F, _I32, _P, _P, _P]),
+    "mh_raster_resolve": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _F, _F, _F, _F,
+                                         _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

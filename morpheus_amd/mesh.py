@@ -3,7 +3,8 @@
 The reference queries the SDF on a resolution^3 grid in S^3 sub-grids, copies every sub-grid to the host, runs
 mcubes.marching_cubes there, queries the colours at the vertices and writes the file with trimesh.  Here the volume stays on
 the device, marching cubes runs on the HIP kernels of csrc/mesh.hip (mh_mc_count + mh_mc_emit; conventions in
-include/morpheus_hip.h) and write_ply writes the binary PLY that Open3D reads (render_all_meshes, morpheus.py:431).
+include/morpheus_hip.h) and write_ply writes the binary PLY that Open3D reads (render_all_meshes,
+morpheus.py:431); morpheus_amd.meshrender renders it here and read_ply reads it back.
 """
 from __future__ import annotations
 
@@ -99,6 +100,54 @@ def write_ply(path: str, vertices, triangles, colors=None) -> None:
         fh.write(("\n".join(head) + "\n").encode("ascii"))
         fh.write(vrec.tobytes())
         fh.write(frec.tobytes())
+
+
+_PLY_TYPES = {"float": "<f4", "uchar": "u1", "int": "<i4"}
+
+
+def read_ply(path: str):
+    """The inverse of write_ply -> (vertices float32 [V,3], triangles int64 [T,3], colors float32 [V,3] = byte / 255, or None)
+    as numpy arrays.  Reads the layout write_ply writes (binary little-endian, float / uchar vertex properties, triangle
+    faces as `list uchar int`); anything else raises MorpheusHipError."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    mark = data.find(b"end_header\n")
+    if mark < 0:
+        raise MorpheusHipError(f"{path}: no PLY header")
+    end = mark + len(b"end_header\n")
+    header = data[:end].decode("ascii", "replace").splitlines()
+    if header[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise MorpheusHipError(f"{path}: not a binary little-endian PLY")
+    elems = []
+    for line in header[2:-1]:
+        w = line.split()
+        if not w or w[0] == "comment":
+            continue
+        if w[0] == "element" and len(w) == 3:
+            elems.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elems and len(w) == 5 and w[1:4] == ["list", "uchar", "int"]:
+            elems[-1][2].append(("list", w[4]))
+        elif w[0] == "property" and elems and len(w) == 3 and w[1] in _PLY_TYPES:
+            elems[-1][2].append((_PLY_TYPES[w[1]], w[2]))
+        else:
+            raise MorpheusHipError(f"{path}: unsupported header line {line!r}")
+    if [e[0] for e in elems] != ["vertex", "face"] or elems[1][2] != [("list", "vertex_indices")] \
+            or any(t == "list" for t, _ in elems[0][2]):
+        raise MorpheusHipError(f"{path}: expected a vertex element and a face element of vertex_indices lists")
+    (_, nv, vprops), (_, nf, _) = elems
+    vdt = np.dtype([(name, t) for t, name in vprops])
+    fdt = np.dtype([("n", "u1"), ("idx", "<i4", 3)])
+    if not {"x", "y", "z"} <= set(vdt.names) or end + nv * vdt.itemsize + nf * fdt.itemsize != len(data):
+        raise MorpheusHipError(f"{path}: vertex properties or file size do not match the header")
+    verts = np.frombuffer(data, vdt, nv, end)
+    faces = np.frombuffer(data, fdt, nf, end + nv * vdt.itemsize)
+    if not (faces["n"] == 3).all():
+        raise MorpheusHipError(f"{path}: only triangle faces are supported")
+    vertices = np.stack([verts["x"], verts["y"], verts["z"]], 1).astype(np.float32)
+    colors = None
+    if {"red", "green", "blue"} <= set(vdt.names):
+        colors = (np.stack([verts["red"], verts["green"], verts["blue"]], 1).astype(np.float32) / np.float32(255.0))
+    return vertices, faces["idx"].astype(np.int64), colors
 
 
 def export_mesh(model, mesh_savepath: str, resolution: int = 128, S: int = 128, t=None, cano: bool = False,

@@ -1,0 +1,202 @@
+"""Mesh rendering on the device: render_all_meshes (morpheus.py:418-470) without an OpenGL window.
+
+The reference opens an Open3D Visualizer per frame, sets the frame's camera (or a 360-degree orbit), and captures the screen
+and the float depth buffer; depths.npz feeds the depth-L1 evaluation (tools/culling.py:eval_depthL1) and the PNGs the
+video_real / video_360 videos.  Here the mesh stays where extract_mesh left it and the HIP rasteriser of csrc/raster.hip
+(mh_raster_depth + mh_raster_resolve, vertex normals by mh_mesh_vertex_normals; conventions in include/morpheus_hip.h)
+renders it.  A render call does not wait for the device: every output's size follows from H and W.
+"""
+from __future__ import annotations
+
+import ctypes
+import glob
+import os
+import re
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+
+MODES = {"color": 0, "normal": 1, "shaded": 2}
+MAX_SIDE = 16384
+
+
+def _mesh_arrays(vertices, triangles, colors=None, normals=None):
+    require_gpu(vertices, triangles, colors, normals)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or not vertices.is_contiguous():
+        raise MorpheusHipError(f"vertices: contiguous float32 [V,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype not in (torch.int32, torch.int64) \
+            or not triangles.is_contiguous():
+        raise MorpheusHipError(f"triangles: contiguous int32 / int64 [T,3], got {triangles.dtype} {tuple(triangles.shape)}")
+    for name, a in (("colors", colors), ("normals", normals)):
+        if a is not None and (a.shape != vertices.shape or a.dtype != torch.float32 or not a.is_contiguous()):
+            raise MorpheusHipError(f"{name}: contiguous float32 [V,3] like vertices, got {a.dtype} {tuple(a.shape)}")
+    # the C ABI takes the int32 indices mh_mc_emit writes; extract_mesh hands out int64 (a device-side cast, no wait)
+    return triangles if triangles.dtype == torch.int32 else triangles.to(torch.int32)
+
+
+def vertex_normal_sums(vertices: torch.Tensor, triangles: torch.Tensor):
+    """-> (normals float32 [V,3], acc int64 [3V + 1]): the area-weighted vertex normals and the fixed-point sums they come
+    from (acc[:3V] = sums [V][3] on the grid q, acc[3V] = the bits of the mesh's largest |cross component|)."""
+    tri = _mesh_arrays(vertices, triangles)
+    V, T = vertices.shape[0], tri.shape[0]
+    acc = torch.empty(3 * V + 1, dtype=torch.int64, device=vertices.device)
+    normals = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
+    check(_lib.load().mh_mesh_vertex_normals(ptr(vertices), V, ptr(tri), T, ptr(acc), ptr(normals), stream()),
+          "mh_mesh_vertex_normals")
+    return normals, acc
+
+
+def vertex_normals(vertices: torch.Tensor, triangles: torch.Tensor) -> torch.Tensor:
+    """Open3D's compute_vertex_normals (morpheus.py:432): the un-normalised cross products of a vertex's triangles summed
+    (order-free, in fixed point), then normalised; (0, 0, 1) for a zero sum."""
+    return vertex_normal_sums(vertices, triangles)[0]
+
+
+def cv2gl(c2w) -> np.ndarray:
+    """OpenGL <-> OpenCV camera-to-world (tools/vis.py:cv2gl): columns 1 and 2 negated.  Its own inverse."""
+    c2w = np.array(c2w, dtype=np.float64)
+    c2w[:3, 1:3] *= -1
+    return c2w
+
+
+def world_to_camera(c2w, convention: str = "opengl") -> np.ndarray:
+    """c2w [4,4] or [3,4] host pose -> row-major float32 [3,4] world -> OpenCV camera, inverted in float64."""
+    if convention not in ("opengl", "opencv"):
+        raise MorpheusHipError(f"convention must be 'opengl' or 'opencv', got {convention!r}")
+    if isinstance(c2w, torch.Tensor):
+        c2w = c2w.detach().cpu().numpy()
+    m = np.eye(4, dtype=np.float64)
+    c = np.asarray(c2w, dtype=np.float64)
+    if c.shape not in ((4, 4), (3, 4)):
+        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
+    m[:3] = c[:3]
+    if convention == "opengl":
+        m = cv2gl(m)
+    return np.ascontiguousarray(np.linalg.inv(m)[:3].astype(np.float32))
+
+
+def _intrinsics(K, fx, fy, cx, cy):
+    if K is not None:
+        K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    if None in (fx, fy, cx, cy):
+        raise MorpheusHipError("render_mesh needs K or fx, fy, cx, cy")
+    return float(fx), float(fy), float(cx), float(cy)
+
+
+def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[torch.Tensor] = None,
+                normals: Optional[torch.Tensor] = None, *, c2w, H: int, W: int, K=None, fx=None, fy=None, cx=None, cy=None,
+                convention: str = "opengl", mode: str = "shaded", near: float = 0.01,
+                background: Sequence[float] = (1.0, 1.0, 1.0), ambient: float = 0.3, small_area: int = 0) -> dict:
+    """Render a triangle mesh from a pinhole camera.
+    -> dict(depth float32 [H,W] camera-space z, 0 where empty; tri_id int32 [H,W], -1 where empty; image float32 [H,W,3];
+            clipped int64 [] triangles dropped because a vertex lies behind `near` or projects beyond the snapping range).
+    c2w is a host pose ('opengl': the dataset's; 'opencv').  mode: 'color' | 'normal' | 'shaded'.  Vertex normals are
+    computed when a mode needs them and none are given.  depth and tri_id do not depend on mode, run or triangle order."""
+    if mode not in MODES:
+        raise MorpheusHipError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    tri = _mesh_arrays(vertices, triangles, colors, normals)
+    H, W = int(H), int(W)
+    V, T = vertices.shape[0], tri.shape[0]
+    lib = _lib.load()
+    wbytes = lib.mh_raster_workspace_bytes(H, W, T)
+    if wbytes < 0:
+        raise MorpheusHipError(f"render_mesh: H, W must be in [1, {MAX_SIDE}] and T below 2^31, got {H} x {W}, T = {T}")
+    fx, fy, cx, cy = _intrinsics(K, fx, fy, cx, cy)
+    w2c = world_to_camera(c2w, convention)
+    w2c_p = w2c.ctypes.data_as(ctypes.c_void_p)
+    if normals is None and MODES[mode] != 0:
+        normals = vertex_normals(vertices, tri)
+    dev = vertices.device
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    clipped = torch.empty((), dtype=torch.int64, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    tri_id = torch.empty(H, W, dtype=torch.int32, device=dev)
+    image = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    s = stream()
+    check(lib.mh_raster_depth(ptr(vertices), V, ptr(tri), T, w2c_p, fx, fy, cx, cy, H, W, float(near), int(small_area),
+                              ptr(ws), ptr(clipped), s), "mh_raster_depth")
+    bg = [float(b) for b in background]
+    check(lib.mh_raster_resolve(ptr(vertices), V, ptr(tri), T, ptr(colors), ptr(normals), w2c_p, fx, fy, cx, cy, H, W,
+                                MODES[mode], float(ambient), bg[0], bg[1], bg[2], ptr(ws), ptr(depth), ptr(tri_id),
+                                ptr(image), s), "mh_raster_resolve")
+    return {"depth": depth, "tri_id": tri_id, "image": image, "clipped": clipped}
+
+
+_PLY_NAME = re.compile(r"mesh_(\d+)_(\d+)\.ply$")
+
+
+def _mesh_sequence(meshes_or_dir, device, epoch=None):
+    """-> iterator of (frame id, mesh dict on the device).  A directory holds mesh_{epoch:04d}_{frame:04d}.ply, every epoch's
+    files side by side (morpheus.py:1489): `epoch` selects one; without it the directory must hold a single epoch."""
+    if isinstance(meshes_or_dir, (str, os.PathLike)):
+        from .mesh import read_ply
+        named = []
+        for path in glob.glob(os.path.join(os.fspath(meshes_or_dir), "*.ply")):
+            m = _PLY_NAME.match(os.path.basename(path))
+            if m:
+                named.append((int(m.group(1)), int(m.group(2)), path))
+        epochs = sorted({e for e, _, _ in named})
+        if epoch is None:
+            if len(epochs) > 1:
+                raise MorpheusHipError(f"{meshes_or_dir} holds the meshes of epochs {epochs}: say which with epoch=")
+        else:
+            named = [n for n in named if n[0] == int(epoch)]
+        if not named:
+            raise MorpheusHipError(f"no mesh_EPOCH_FRAME.ply under {meshes_or_dir}" +
+                                   ("" if epoch is None else f" for epoch {int(epoch)} (found epochs {epochs})"))
+        for _, frame, path in sorted(named):
+            v, t, c = read_ply(path)
+            yield frame, {"vertices": torch.from_numpy(v).to(device), "triangles": torch.from_numpy(t).to(device),
+                          "colors": None if c is None else torch.from_numpy(c).to(device)}
+    else:
+        if epoch is not None:
+            raise MorpheusHipError("epoch selects files of a mesh directory; it has no meaning for an iterable of meshes")
+        for i, mesh in enumerate(meshes_or_dir):
+            yield i, mesh
+
+
+def render_all_meshes(meshes_or_dir, poses, K, H: int, W: int, save_images_dir: Optional[str] = None,
+                      save_depths_dir: Optional[str] = None, scale: int = 4, epoch: Optional[int] = None,
+                      convention: str = "opengl", mode: str = "shaded", near: float = 0.01,
+                      background: Sequence[float] = (1.0, 1.0, 1.0), ambient: float = 0.3, device="cuda",
+                      keep_results: bool = False):
+    """The loop of render_all_meshes (morpheus.py:418-470): mesh i is rendered from poses[i] at (scale*H) x (scale*W) with
+    K[:2] * scale and the principal point at the image centre -- (scale*W/2, scale*H/2) here, where a pixel centre sits at
+    (i + 0.5, j + 0.5); Open3D's set_K writes w/2 - 0.5 for the same point in its integer-centre convention.
+    meshes_or_dir: a directory of mesh_{epoch:04d}_{frame:04d}.ply (frame = index into poses; `epoch` selects the files, and
+    is required when the directory holds several epochs) or an iterable of extract_mesh dicts, so model -> mesh -> depth need
+    not touch the disk.  Writes {i:04d}.png under save_images_dir (needs PIL) and depths.npz with keys depth_{i} under
+    save_depths_dir.  -> {"depth_{i}": host float32 [scale*H, scale*W]}, what depths.npz holds (the reference keeps no more
+    than that across frames); with keep_results the list of render_mesh results instead, device tensors of 20 bytes per
+    pixel and frame.  The per-frame depth PNGs of capture_depth_image (morpheus.py:461) are not written; video encoding
+    stays with the caller."""
+    Image = None
+    if save_images_dir is not None:
+        try:
+            from PIL import Image
+        except ImportError as e:                                   # images were asked for and cannot be written
+            raise MorpheusHipError("render_all_meshes: save_images_dir needs PIL to write PNGs") from e
+        os.makedirs(save_images_dir, exist_ok=True)
+    K = np.array(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
+    fx, fy = K[0, 0] * scale, K[1, 1] * scale
+    h, w = int(H * scale), int(W * scale)
+    results, depths = [], {}
+    for i, mesh in _mesh_sequence(meshes_or_dir, device, epoch):
+        out = render_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), mesh.get("normals"), c2w=poses[i], H=h, W=w,
+                          fx=fx, fy=fy, cx=w / 2.0, cy=h / 2.0, convention=convention, mode=mode, near=near,
+                          background=background, ambient=ambient)
+        if keep_results:
+            results.append(out)
+        depths[f"depth_{i}"] = out["depth"].cpu().numpy()
+        if Image is not None:
+            rgb = (out["image"].nan_to_num(0.0).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
+            Image.fromarray(rgb).save(os.path.join(save_images_dir, f"{i:04d}.png"))
+    if save_depths_dir is not None:
+        os.makedirs(save_depths_dir, exist_ok=True)
+        np.savez(os.path.join(save_depths_dir, "depths.npz"), **depths)
+    return results if keep_results else depths
