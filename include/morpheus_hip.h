@@ -505,6 +505,71 @@ int mh_raster_resolve(const float *vertices, int64_t V, const int32_t *triangles
                       int32_t mode, float ambient, float bg_r, float bg_g, float bg_b, const void *workspace, float *depth,
                       int32_t *tri_id, float *image, void *stream);
 
+/* ---- mesh evaluation (tools/culling.py of the reference: cull_from_one_pose, trimesh.sample.sample_surface, the KD-tree
+ * queries of accuracy / completion / completion_ratio, Open3D's point-to-point ICP; csrc/mesheval.hip) --------------------
+ * Every fp32 expression below is evaluated operator by operator, round to nearest, no FMA, in the written order; so is every
+ * float64 one (tests/mesheval_oracle.py is written from this text).  All counts are in [0, 2^31).
+ *   nearest neighbour (mh_nn_search): query [Nq,3], ref [Nr,3] fp32.  For query q and reference point r:
+ *     dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z, d2 = (dx*dx + dy*dy) + dz*dz in fp32.  A candidate is admissible when
+ *     d2 < +inf (a NaN or an overflowed d2 never wins) and d2 <= max_d2; max_d2 = +inf switches the second test off (the
+ *     caller squares its distance bound once in fp32).  The winner is the admissible candidate of least d2, the lowest index
+ *     among equals: idx [Nq] int32, d2 [Nq] fp32; idx = -1, d2 = +inf without one (Nr == 0 included).  Exact brute force
+ *     over all Nq * Nr pairs.  The reference set is cut into `segments` runs (<= 0: a default from the sizes; at most 4096)
+ *     whose results meet in a 64-bit atomic minimum on (bits(d2) << 32) | index -- d2 >= +0, so the key orders like (d2,
+ *     index): idx and d2 are the same bytes run to run and for every value of `segments`.  workspace: mh_nn_workspace_bytes
+ *     (Nq) = 8 Nq DEVICE bytes (host only; -1 for a bad Nq).  mh_nn_tile_points: reference points per LDS tile (host only;
+ *     for tests that place sizes on the kernel's internal boundaries; 256 queries per workgroup, 64 per wavefront).
+ *   culling (mh_cull_vertices, mh_cull_triangles): w2c_host = 12 HOST doubles, row-major [3][4] = (R | t), world -> OpenCV
+ *     camera, the inverse of the pose formed by the caller in float64; K_host = 9 HOST doubles, row-major 3 x 3.  Per vertex
+ *     (x, y, z) = (double) of its fp32 coordinates, all in float64:
+ *       cam_r = ((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r];  uvz_r = (K[r][0]*cam_0 + K[r][1]*cam_1) + K[r][2]*cam_2;
+ *       pz = uvz_2 + 1e-8;  px = uvz_0 / pz;  py = uvz_1 / pz;
+ *       frustum  = 0 <= px and px <= W-1 and 0 <= py and py <= H-1 and pz > 0   (false whenever a NaN takes part);
+ *       u = (int)px, v = (int)py (truncation), read only when frustum holds;
+ *       observed = frustum and pz < (double)(rendered_depth[v][u] + eps)   -- the sum is an fp32 addition of two fp32 values;
+ *       invalid  = frustum and depth_gt[v][u] <= 0   (false everywhere when depth_gt is NULL).
+ *     rendered_depth, depth_gt: fp32 [H][W], H, W in [1, 16384].  The three masks are uint8 [V] of 0 / 1.
+ *     mh_cull_triangles: keep[t] = 1 when any of the triangle's vertices is observed and not all three are invalid; 0 for a
+ *     triangle with an index outside [0, V).
+ *   area weights (mh_mesh_area_weights): per triangle (a, b, c), with the cross product of the rasteriser's depth stage in
+ *     world space (e1 = b-a, e2 = c-a, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x)):
+ *     area = sqrtf((nx*nx + ny*ny) + nz*nz) * 0.5f; 0 when that is not finite or an index is outside [0, V).  areas [T] fp32.
+ *     m = the largest area, E its biased fp32 exponent field, G = 2^(E-126) (a power of two strictly above m), q = G * 2^-40;
+ *     qarea[t] = llrint((double)area / q) (the division is exact: a multiplication by 2^(166-E)); qarea [T + 1] DEVICE int64,
+ *     its last word the bits of m.  The caller's inclusive prefix sum over qarea[:T] is integer and exact in any order.
+ *   sampling (mh_sample_surface): cum [T] = that inclusive prefix sum, total = cum[T-1] > 0; uniforms [count,3] fp32 in
+ *     [0, 1).  target = (int64)((double)u0 * (double)total) (0 for u0 < 0 or NaN, total-1 for u0 >= 1, and never above
+ *     total-1); face = the first f with cum[f] > target (binary search: lo = 0, hi = T-1; while lo < hi: mid = (lo+hi)>>1;
+ *     cum[mid] > target ? hi = mid : lo = mid+1), so a face of quantised area 0 is never chosen.  r1 = u1, r2 = u2; if
+ *     r1 + r2 > 1 (fp32): r1 = 1 - r1, r2 = 1 - r2; point_a = (v0_a + r1*(v1_a - v0_a)) + r2*(v2_a - v0_a) in fp32.  points
+ *     [count,3] fp32 (NaN for a face with an index outside [0, V)), face [count] int32.
+ *   rigid alignment (mh_icp_transform, mh_icp_sums): T_host = 12 HOST doubles, row-major [3][4].  out_r = (float)(((T[r][0]*x
+ *     + T[r][1]*y) + T[r][2]*z) + T[r][3]) in float64 from the fp32 source point, rounded once.  mh_icp_sums: over the points
+ *     i with 0 <= idx[i] < Nt, with p = p[i], q = target[idx[i]] (fp32 values taken to float64): sums [17] DEVICE doubles =
+ *     {n, sum d2[i], sum p (3), sum q (3), sum p_a*q_b (9, at 8 + 3a + b)}.  Float64 sums in a fixed order (a lane's points in
+ *     index order, the lanes of a wavefront in an xor butterfly, the wavefronts and then the workgroups' partials in index
+ *     order): the same bytes run to run; against another summation order they differ by float64 round-off only.  workspace:
+ *     mh_icp_workspace_bytes() DEVICE bytes (host only).
+ * Bad arguments return MH_ERR_ARG before any launch; an empty input (Nq, V, T, count or N of 0) returns MH_OK without a launch
+ * and writes nothing. */
+int64_t mh_nn_workspace_bytes(int64_t Nq);
+int32_t mh_nn_tile_points(void);
+int mh_nn_search(const float *query, int64_t Nq, const float *ref, int64_t Nr, float max_d2, int32_t segments, void *workspace,
+                 int32_t *idx, float *d2, void *stream);
+int mh_cull_vertices(const float *vertices, int64_t V, const double *w2c_host, const double *K_host, int32_t H, int32_t W,
+                     const float *rendered_depth, const float *depth_gt, float eps, uint8_t *frustum, uint8_t *observed,
+                     uint8_t *invalid, void *stream);
+int mh_cull_triangles(const int32_t *triangles, int64_t T, int64_t V, const uint8_t *observed, const uint8_t *invalid,
+                      uint8_t *keep, void *stream);
+int mh_mesh_area_weights(const float *vertices, int64_t V, const int32_t *triangles, int64_t T, float *areas, int64_t *qarea,
+                         void *stream);
+int mh_sample_surface(const float *vertices, int64_t V, const int32_t *triangles, int64_t T, const int64_t *cum,
+                      const float *uniforms, int64_t count, float *points, int32_t *face, void *stream);
+int64_t mh_icp_workspace_bytes(void);
+int mh_icp_transform(const float *src, int64_t N, const double *T_host, float *out, void *stream);
+int mh_icp_sums(const float *p, int64_t N, const float *target, int64_t Nt, const int32_t *idx, const float *d2,
+                void *workspace, double *sums, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

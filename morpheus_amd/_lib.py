@@ -106,6 +106,16 @@ _SIGS = {
     "mh_raster_depth": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _F, _F, _F, _F, _I32, _I32, _F, _I32, _P, _P, _P]),
     "mh_raster_resolve": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _F, _F, _F, _F, _I32, _I32, _I32, _F, _F, _F, _F,
                                          _P, _P, _P, _P, _P]),
+    "mh_nn_workspace_bytes": (_I64, [_I64]),
+    "mh_nn_tile_points": (_I32, []),
+    "mh_nn_search": (ctypes.c_int, [_P, _I64, _P, _I64, _F, _I32, _P, _P, _P, _P]),
+    "mh_cull_vertices": (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I32, _P, _P, _F, _P, _P, _P, _P]),
+    "mh_cull_triangles": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P, _P]),
+    "mh_mesh_area_weights": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "mh_sample_surface": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P]),
+    "mh_icp_workspace_bytes": (_I64, []),
+    "mh_icp_transform": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
+    "mh_icp_sums": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 SO = os.path.join(OUT_DIR, "libmorpheus_hip.so")
 SOURCES = ["hashgrid.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_b3.hip", "optim.hip", "wnorm.hip", "normal.hip", "graph.hip", "losses.hip",
-           "mesh.hip", "raster.hip"]
+           "mesh.hip", "raster.hip", "mesheval.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "morpheus_hip.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar fp32 adds / muls of the epilogues into v_pk_* instructions, which
 # cost more than two plain ones beside MFMAs (MI355X_MICROARCH.md); measured on one box, whole library, cfg3: 15.61 -> 15.38
@@ -33,7 +33,9 @@ if any("BRK_EXP" in f for f in FLAGS):
 # zero past the counted parity gate (tests/test_gpu_losses.py compares with the operator chain bit for bit)
 # mesh.hip: the vertex position (p + (iso - f0) / (f1 - f0)) is pinned bit for bit by tests/mc_oracle.py, the same reason
 # raster.hip: projected positions, depth and coverage are pinned bit for bit by tests/raster_oracle.py, the same reason
-FILE_FLAGS = {"losses.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"], "raster.hip": ["-ffp-contract=off"]}
+# mesheval.hip: squared distances, sampled points and cull masks are pinned bit for bit by tests/mesheval_oracle.py, the same reason
+FILE_FLAGS = {"losses.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"], "raster.hip": ["-ffp-contract=off"],
+              "mesheval.hip": ["-ffp-contract=off"]}
 
 
 def _newer(deps, target) -> bool:

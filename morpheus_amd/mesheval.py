@@ -1,0 +1,341 @@
+"""Mesh evaluation on the device: tools/culling.py of the reference (eval_mesh -> cull_meshes -> eval_mesh_3d -> metric_3d.txt,
+and eval_depthL1 on depths.npz) without pyrender, trimesh, open3d or cv2.
+
+The reference culls each exported mesh against its frame's camera (a pyrender depth map of both windings), samples 50 000
+points on the culled mesh and on the ground-truth mesh with trimesh, aligns the two with Open3D's point-to-point ICP, and
+scores accuracy / completion with a CPU KD-tree.  Here the depth map is morpheus_amd.meshrender's, and the HIP kernels of
+csrc/mesheval.hip do the rest: mh_nn_search is the exact brute-force nearest-neighbour search every score and every ICP
+iteration rests on; mh_cull_*, mh_mesh_area_weights / mh_sample_surface and mh_icp_* are the small kernels around it
+(conventions in include/morpheus_hip.h, restated in numpy by tests/mesheval_oracle.py).
+
+Known differences from the reference's scores: no trimesh subdivide_to_size before culling; the ICP parameters and
+stopping rule follow Open3D's documented defaults and were never compared with Open3D; sample_surface is seeded, where the
+reference draws from numpy's global generator.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+from .meshrender import _mesh_arrays, _mesh_sequence, cv2gl, render_mesh
+
+
+def _points(name, a):
+    require_gpu(a)
+    if a.dim() != 2 or a.shape[1] != 3 or a.dtype != torch.float32 or not a.is_contiguous():
+        raise MorpheusHipError(f"{name}: contiguous float32 [N,3], got {a.dtype} {tuple(a.shape)}")
+    return a
+
+
+def _doubles(a: np.ndarray):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+# ---- nearest neighbour ---------------------------------------------------------------------------------------------------
+
+def nearest(query: torch.Tensor, ref: torch.Tensor, max_dist: Optional[float] = None, segments: int = 0):
+    """-> (idx int32 [Nq], d2 float32 [Nq]): for each query the reference point of least d2 = (dx*dx + dy*dy) + dz*dz (rounded
+    fp32 operators), the lowest index among equals; candidates with a NaN or infinite d2, or with d2 > float32(max_dist)^2,
+    are ignored; idx = -1 and d2 = +inf where none is left.  Exact brute force.  `segments` (how many runs the reference set
+    is cut into; 0: chosen from the sizes) never changes the result.  No host synchronisation."""
+    _points("query", query)
+    _points("ref", ref)
+    if segments > 4096:
+        raise MorpheusHipError(f"nearest: at most 4096 segments, got {segments}")
+    max_d2 = math.inf
+    if max_dist is not None:
+        m = np.float32(max_dist)
+        if not m >= 0:
+            raise MorpheusHipError(f"nearest: max_dist must be >= 0, got {max_dist}")
+        with np.errstate(over="ignore"):
+            max_d2 = float(m * m)
+    Nq, Nr = query.shape[0], ref.shape[0]
+    dev = query.device
+    idx = torch.empty(Nq, dtype=torch.int32, device=dev)
+    d2 = torch.empty(Nq, dtype=torch.float32, device=dev)
+    ws = torch.empty(Nq, dtype=torch.int64, device=dev)
+    check(_lib.load().mh_nn_search(ptr(query), Nq, ptr(ref), Nr, max_d2, int(segments), ptr(ws), ptr(idx), ptr(d2), stream()),
+          "mh_nn_search")
+    return idx, d2
+
+
+# ---- culling -------------------------------------------------------------------------------------------------------------
+
+def world_to_camera_f64(c2w) -> np.ndarray:
+    """OpenGL camera-to-world [4,4] or [3,4] host pose -> float64 [3,4] world -> OpenCV camera (columns 1 and 2 negated, then
+    numpy.linalg.inv, as cull_from_one_pose does)."""
+    if isinstance(c2w, torch.Tensor):
+        c2w = c2w.detach().cpu().numpy()
+    c = np.asarray(c2w, dtype=np.float64)
+    if c.shape not in ((4, 4), (3, 4)):
+        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
+    m = np.eye(4, dtype=np.float64)
+    m[:3] = c[:3]
+    return np.ascontiguousarray(np.linalg.inv(cv2gl(m))[:3])
+
+
+def _depth_map(name, d, H, W, device):
+    if d is None:
+        return None
+    if not isinstance(d, torch.Tensor):
+        d = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float32)).to(device)
+    require_gpu(d)
+    if tuple(d.shape) != (H, W) or d.dtype != torch.float32 or not d.is_contiguous():
+        raise MorpheusHipError(f"{name}: contiguous float32 [{H},{W}], got {d.dtype} {tuple(d.shape)}")
+    return d
+
+
+def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[torch.Tensor] = None, *, c2w, K, H: int,
+              W: int, depth_gt=None, eps: float = 0.005, remove_missing_depth: bool = True, rendered_depth=None,
+              return_masks: bool = False) -> dict:
+    """cull_one_mesh / cull_from_one_pose (tools/culling.py:17-49, 86-131): keep the triangles that the camera of pose c2w
+    (OpenGL, as the dataset stores it) observes -- a vertex in the frustum and no further than eps behind the rendered depth
+    -- unless all three vertices fall on pixels without ground-truth depth.
+    -> dict(vertices [V',3], triangles int64 [T',3] re-indexed, colors [V',3] or None), order preserved, unreferenced
+    vertices removed; with return_masks also frustum / observed / invalid (bool [V]) and keep (bool [T]).
+    rendered_depth defaults to render_mesh's double-sided depth map from the same camera (near = 0.01 as the reference's
+    pyrender camera; its zfar = 10 is not restated: the scene box is [-1, 1]^3).  depth_gt: [H,W] float32, needed when
+    remove_missing_depth.  The reference subdivides the mesh to 0.01 edges first; this works on the triangles it is given.
+    One host synchronisation (to size the outputs)."""
+    tri = _mesh_arrays(vertices, triangles, colors)
+    H, W = int(H), int(W)
+    dev = vertices.device
+    Kh = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+    if Kh.shape != (3, 3):
+        raise MorpheusHipError(f"K must be [3,3], got {Kh.shape}")
+    if remove_missing_depth and depth_gt is None:
+        raise MorpheusHipError("cull_mesh: remove_missing_depth needs depth_gt")
+    if rendered_depth is None:
+        rendered_depth = render_mesh(vertices, tri, c2w=c2w, K=Kh, H=H, W=W, convention="opengl", mode="color",
+                                     near=0.01)["depth"]
+    rendered_depth = _depth_map("rendered_depth", rendered_depth, H, W, dev)
+    depth_gt = _depth_map("depth_gt", depth_gt, H, W, dev) if remove_missing_depth else None
+    w2c, w2c_p = _doubles(world_to_camera_f64(c2w))
+    Kd, K_p = _doubles(Kh)
+    V, T = vertices.shape[0], tri.shape[0]
+    frustum, observed, invalid = (torch.zeros(V, dtype=torch.uint8, device=dev) for _ in range(3))
+    keep = torch.zeros(T, dtype=torch.uint8, device=dev)
+    lib, s = _lib.load(), stream()
+    check(lib.mh_cull_vertices(ptr(vertices), V, w2c_p, K_p, H, W, ptr(rendered_depth), ptr(depth_gt), float(eps),
+                               ptr(frustum), ptr(observed), ptr(invalid), s), "mh_cull_vertices")
+    check(lib.mh_cull_triangles(ptr(tri), T, V, ptr(observed), ptr(invalid), ptr(keep), s), "mh_cull_triangles")
+    keep = keep.bool()
+    kept = tri[keep].long()                                        # the host waits here
+    used = torch.zeros(V, dtype=torch.bool, device=dev)
+    used[kept.reshape(-1)] = True
+    remap = torch.cumsum(used, 0) - 1
+    out = {"vertices": vertices[used].contiguous(), "triangles": remap[kept].contiguous(),
+           "colors": None if colors is None else colors[used].contiguous()}
+    if return_masks:
+        out.update(frustum=frustum.bool(), observed=observed.bool(), invalid=invalid.bool(), keep=keep)
+    return out
+
+
+# ---- surface sampling ----------------------------------------------------------------------------------------------------
+
+def area_weights(vertices: torch.Tensor, triangles: torch.Tensor):
+    """-> (areas float32 [T], cum int64 [T]): the triangles' areas and the inclusive prefix sum of their fixed-point values
+    (grid q = G * 2^-40, G the power of two strictly above the largest area): integer, so exact in any order."""
+    tri = _mesh_arrays(vertices, triangles)
+    V, T = vertices.shape[0], tri.shape[0]
+    areas = torch.empty(T, dtype=torch.float32, device=vertices.device)
+    qarea = torch.empty(T + 1, dtype=torch.int64, device=vertices.device)
+    check(_lib.load().mh_mesh_area_weights(ptr(vertices), V, ptr(tri), T, ptr(areas), ptr(qarea), stream()),
+          "mh_mesh_area_weights")
+    return areas, torch.cumsum(qarea[:T], 0)
+
+
+def sample_surface(vertices: torch.Tensor, triangles: torch.Tensor, count: int, *, seed: int = 0,
+                   uniforms: Optional[torch.Tensor] = None):
+    """trimesh.sample.sample_surface, reproducible: faces chosen by area, points uniform inside them.
+    -> (points float32 [count,3], face int32 [count]).  uniforms [count,3] float32 in [0, 1) (column 0 picks the face, 1 and 2
+    the barycentrics) default to a torch.Generator seeded with `seed` on the device.  One host synchronisation (an empty mesh
+    or one of zero total area raises)."""
+    tri = _mesh_arrays(vertices, triangles)
+    count = int(count)
+    dev = vertices.device
+    V, T = vertices.shape[0], tri.shape[0]
+    if T == 0 or V == 0:
+        raise MorpheusHipError("sample_surface: the mesh is empty")
+    if uniforms is None:
+        g = torch.Generator(device=dev)
+        g.manual_seed(int(seed))
+        uniforms = torch.rand(count, 3, generator=g, dtype=torch.float32, device=dev)
+    _points("uniforms", uniforms)
+    if uniforms.shape[0] != count:
+        raise MorpheusHipError(f"uniforms: [{count},3], got {tuple(uniforms.shape)}")
+    _, cum = area_weights(vertices, tri)
+    if int(cum[-1].item()) <= 0:
+        raise MorpheusHipError("sample_surface: the mesh has zero total area")
+    points = torch.empty(count, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(count, dtype=torch.int32, device=dev)
+    check(_lib.load().mh_sample_surface(ptr(vertices), V, ptr(tri), T, ptr(cum), ptr(uniforms), count, ptr(points), ptr(face),
+                                        stream()), "mh_sample_surface")
+    return points, face
+
+
+# ---- rigid alignment -----------------------------------------------------------------------------------------------------
+
+def transform_points(points: torch.Tensor, T) -> torch.Tensor:
+    """T [4,4] or [3,4] host float64 applied to fp32 points: computed in float64, rounded once."""
+    _points("points", points)
+    Th, T_p = _doubles(np.asarray(T, dtype=np.float64)[:3])
+    out = torch.empty_like(points)
+    check(_lib.load().mh_icp_transform(ptr(points), points.shape[0], T_p, ptr(out), stream()), "mh_icp_transform")
+    return out
+
+
+def icp_sums(moved: torch.Tensor, target: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor) -> torch.Tensor:
+    """-> float64 [17] on the device: n, sum d2, sum p, sum q, sum p q^T over the correspondences with idx >= 0, in a fixed
+    order (the same bytes run to run)."""
+    _points("moved", moved)
+    _points("target", target)
+    require_gpu(idx, d2)
+    N = moved.shape[0]
+    if idx.shape != (N,) or idx.dtype != torch.int32 or d2.shape != (N,) or d2.dtype != torch.float32:
+        raise MorpheusHipError("icp_sums: idx int32 [N] and d2 float32 [N] as nearest returns them")
+    lib = _lib.load()
+    sums = torch.zeros(17, dtype=torch.float64, device=moved.device)
+    ws = torch.empty(lib.mh_icp_workspace_bytes(), dtype=torch.uint8, device=moved.device)
+    check(lib.mh_icp_sums(ptr(moved), N, ptr(target), target.shape[0], ptr(idx), ptr(d2), ptr(ws), ptr(sums), stream()),
+          "mh_icp_sums")
+    return sums
+
+
+def kabsch_update(sums: np.ndarray) -> np.ndarray:
+    """The rigid motion [4,4] (no scale) that best maps the p onto the q in the least-squares sense, from the 17 sums."""
+    n = sums[0]
+    mp, mq = sums[2:5] / n, sums[5:8] / n
+    Hm = sums[8:17].reshape(3, 3) - n * np.outer(mp, mq)
+    U, _, Vt = np.linalg.svd(Hm)
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T)) or 1.0])
+    R = Vt.T @ D @ U.T
+    out = np.eye(4)
+    out[:3, :3] = R
+    out[:3, 3] = mq - R @ mp
+    return out
+
+
+def icp_align(source: torch.Tensor, target: torch.Tensor, threshold: float = 0.1, max_iteration: int = 30,
+              relative_fitness: float = 1e-6, relative_rmse: float = 1e-6) -> dict:
+    """get_align_transformation (tools/culling.py:148-166): point-to-point ICP from the identity.
+    -> dict(transformation float64 [4,4] numpy, fitness, inlier_rmse, iterations).  The parameters and the stopping rule
+    (both |delta fitness| and |delta rmse| below their thresholds, or max_iteration) are what Open3D's registration_icp is
+    understood to use; agreement with Open3D is unverified.  One host synchronisation per iteration."""
+    _points("source", source)
+    _points("target", target)
+    Ns = source.shape[0]
+    T = np.eye(4)
+
+    def evaluate():
+        moved = transform_points(source, T)
+        idx, d2 = nearest(moved, target, max_dist=threshold)
+        s = icp_sums(moved, target, idx, d2).cpu().numpy()         # the host waits here
+        n = s[0]
+        return s, (n / Ns if Ns else 0.0), (math.sqrt(s[1] / n) if n > 0 else 0.0)
+
+    if Ns == 0 or target.shape[0] == 0:
+        return {"transformation": T, "fitness": 0.0, "inlier_rmse": 0.0, "iterations": 0}
+    s, fitness, rmse = evaluate()
+    if s[0] == 0:
+        return {"transformation": np.eye(4), "fitness": 0.0, "inlier_rmse": 0.0, "iterations": 0}
+    it = 0
+    while it < max_iteration:
+        T = kabsch_update(s) @ T
+        it += 1
+        s_new, f_new, r_new = evaluate()
+        done = abs(f_new - fitness) < relative_fitness and abs(r_new - rmse) < relative_rmse
+        s, fitness, rmse = s_new, f_new, r_new
+        if done or s[0] == 0:
+            break
+    return {"transformation": T, "fitness": float(fitness), "inlier_rmse": float(rmse), "iterations": it}
+
+
+# ---- the scores ----------------------------------------------------------------------------------------------------------
+
+def _load_mesh(m, device):
+    if isinstance(m, (str, os.PathLike)):
+        from .mesh import read_ply
+        v, t, c = read_ply(os.fspath(m))
+        return {"vertices": torch.from_numpy(v).to(device), "triangles": torch.from_numpy(t).to(device),
+                "colors": None if c is None else torch.from_numpy(c).to(device)}
+    return m
+
+
+def mesh_metrics(rec, gt, align: bool = True, num_points: int = 50000, seed: int = 0, dist_th: float = 0.05,
+                 device="cuda", uniforms_rec=None, uniforms_gt=None) -> dict:
+    """calc_3d_metric (tools/culling.py:189-221) -> {'acc': mean distance rec -> gt in cm, 'comp': mean distance gt -> rec in
+    cm, 'comp ratio': % of gt points closer than dist_th to rec}.  rec / gt: mesh dicts (vertices, triangles) on the device or
+    paths of PLYs in read_ply's layout; a gt with triangles None is a point cloud and is used as it is.  align: icp_align
+    between the two vertex sets first, applied to rec.  Both surfaces are sampled with num_points points (seeds `seed` and
+    `seed + 1`, or the injected uniforms).  Distances are sqrt(d2) in float64, the means in float64."""
+    rec, gt = _load_mesh(rec, device), _load_mesh(gt, device)
+    rv = rec["vertices"]
+    if align:
+        rv = transform_points(rv, icp_align(rv, gt["vertices"])["transformation"])
+    def count(u):                                                  # injected uniforms bring their own count
+        return num_points if u is None else u.shape[0]
+
+    rec_pts = sample_surface(rv, rec["triangles"], count(uniforms_rec), seed=seed, uniforms=uniforms_rec)[0]
+    if gt.get("triangles") is None:
+        gt_pts = _points("gt vertices", gt["vertices"])
+    else:
+        gt_pts = sample_surface(gt["vertices"], gt["triangles"], count(uniforms_gt), seed=seed + 1, uniforms=uniforms_gt)[0]
+    d_acc = nearest(rec_pts, gt_pts)[1].double().sqrt()
+    d_comp = nearest(gt_pts, rec_pts)[1].double().sqrt()
+    return {"acc": float(d_acc.mean()) * 100, "comp": float(d_comp.mean()) * 100,
+            "comp ratio": float((d_comp < dist_th).double().mean()) * 100}
+
+
+def eval_mesh(meshes_or_dir, gt_meshes, poses, K, H: int, W: int, depths_gt, save_file: Optional[str] = None, epoch: int = 0,
+              mesh_epoch: Optional[int] = None, align: bool = True, num_points: int = 50000, seed: int = 0, eps: float = 0.005,
+              remove_missing_depth: bool = True, device="cuda") -> dict:
+    """The loop of eval_mesh + eval_mesh_3d (tools/culling.py:223-235, 262-275): mesh i is culled from poses[i] against
+    depths_gt[i] and scored against gt_meshes[i]; nothing is written in between.  meshes_or_dir as in render_all_meshes
+    (`mesh_epoch` selects a directory's files); gt_meshes: mesh dicts or PLY paths by frame.  Appends the reference's line
+    "Ep_{epoch}:\\t Acc:{}\\t Comp:{}" to save_file.  -> {"acc": [...], "comp": [...], "comp ratio": [...], "frames": [...]}."""
+    out = {"acc": [], "comp": [], "comp ratio": [], "frames": []}
+    for i, mesh in _mesh_sequence(meshes_or_dir, device, mesh_epoch):
+        culled = cull_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), c2w=poses[i], K=K, H=H, W=W,
+                           depth_gt=depths_gt[i], eps=eps, remove_missing_depth=remove_missing_depth)
+        m = mesh_metrics(culled, gt_meshes[i], align=align, num_points=num_points, seed=seed, device=device)
+        for k in ("acc", "comp", "comp ratio"):
+            out[k].append(m[k])
+        out["frames"].append(i)
+    if save_file is not None:
+        with open(save_file, "a") as fh:
+            print("Ep_{}:\t Acc:{}\t Comp:{}".format(epoch, np.array(out["acc"]).mean(), np.array(out["comp"]).mean()), file=fh)
+    return out
+
+
+def eval_depth_l1(depths, depths_gt, masks, save_dir: Optional[str] = None) -> np.ndarray:
+    """eval_depthL1 (tools/culling.py:237-260): per frame the mean of |gt - pred| over the pixels with gt > 0, mask > 0 and an
+    error in (0, 1]; 0 for a frame without such a pixel (the reference takes the mean of nothing there: nan).  depths: what render_all_meshes returns ({"depth_{i}": [H,W]}) or the path of a depths.npz; depths_gt
+    [F,H,W]; masks [F,H,W] or [F,H,W,C] (channel 0).  Writes depthL1_scores.txt and depthL1_score_mean.txt (%.5f) under
+    save_dir; the reference's colour-mapped error images need cv2 and are not written.  Host arithmetic, as there."""
+    if isinstance(depths, (str, os.PathLike)):
+        depths = np.load(os.fspath(depths))
+    errors = []
+    for i in range(len(depths_gt)):
+        pred = np.asarray(depths[f"depth_{i}"])
+        gt = depths_gt[i].cpu().numpy() if isinstance(depths_gt[i], torch.Tensor) else np.asarray(depths_gt[i])
+        mask = masks[i].cpu().numpy() if isinstance(masks[i], torch.Tensor) else np.asarray(masks[i])
+        if mask.ndim == 3:
+            mask = mask[..., 0]
+        err = np.abs(gt - pred)
+        counted = (gt > 0) & (mask > 0) & (err > 0) & (err <= 1.0)
+        errors.append(err[counted].mean() if counted.any() else 0.0)
+    errors = np.array(errors)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        np.savetxt(os.path.join(save_dir, "depthL1_scores.txt"), errors, fmt="%.5f")
+        np.savetxt(os.path.join(save_dir, "depthL1_score_mean.txt"), np.array([errors.mean()]), fmt="%.5f")
+    return errors
