@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+from ._lib import MorpheusHipError, launch, ptr, require_gpu
 
 
 def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
@@ -34,13 +34,12 @@ def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
     ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     iso = float(isovalue)
-    s = stream()
-    check(lib.mh_mc_count(ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(counts), s), "mh_mc_count")
+    launch("mh_mc_count", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(counts))
     V, T = counts.tolist()
     vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
     triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
     if V or T:
-        check(lib.mh_mc_emit(ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles), s), "mh_mc_emit")
+        launch("mh_mc_emit", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles))
     return vertices, triangles.long()
 
 

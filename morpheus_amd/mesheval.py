@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+from ._lib import MorpheusHipError, launch, ptr, require_gpu
 from .meshrender import _mesh_arrays, _mesh_sequence, cv2gl, render_mesh
 
 
@@ -62,8 +62,7 @@ def nearest(query: torch.Tensor, ref: torch.Tensor, max_dist: Optional[float] = 
     idx = torch.empty(Nq, dtype=torch.int32, device=dev)
     d2 = torch.empty(Nq, dtype=torch.float32, device=dev)
     ws = torch.empty(Nq, dtype=torch.int64, device=dev)
-    check(_lib.load().mh_nn_search(ptr(query), Nq, ptr(ref), Nr, max_d2, int(segments), ptr(ws), ptr(idx), ptr(d2), stream()),
-          "mh_nn_search")
+    launch("mh_nn_search", ptr(query), Nq, ptr(ref), Nr, max_d2, int(segments), ptr(ws), ptr(idx), ptr(d2))
     return idx, d2
 
 
@@ -123,10 +122,9 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
     V, T = vertices.shape[0], tri.shape[0]
     frustum, observed, invalid = (torch.zeros(V, dtype=torch.uint8, device=dev) for _ in range(3))
     keep = torch.zeros(T, dtype=torch.uint8, device=dev)
-    lib, s = _lib.load(), stream()
-    check(lib.mh_cull_vertices(ptr(vertices), V, w2c_p, K_p, H, W, ptr(rendered_depth), ptr(depth_gt), float(eps),
-                               ptr(frustum), ptr(observed), ptr(invalid), s), "mh_cull_vertices")
-    check(lib.mh_cull_triangles(ptr(tri), T, V, ptr(observed), ptr(invalid), ptr(keep), s), "mh_cull_triangles")
+    launch("mh_cull_vertices", ptr(vertices), V, w2c_p, K_p, H, W, ptr(rendered_depth), ptr(depth_gt), float(eps), ptr(frustum),
+           ptr(observed), ptr(invalid))
+    launch("mh_cull_triangles", ptr(tri), T, V, ptr(observed), ptr(invalid), ptr(keep))
     keep = keep.bool()
     kept = tri[keep].long()                                        # the host waits here
     used = torch.zeros(V, dtype=torch.bool, device=dev)
@@ -148,8 +146,7 @@ def area_weights(vertices: torch.Tensor, triangles: torch.Tensor):
     V, T = vertices.shape[0], tri.shape[0]
     areas = torch.empty(T, dtype=torch.float32, device=vertices.device)
     qarea = torch.empty(T + 1, dtype=torch.int64, device=vertices.device)
-    check(_lib.load().mh_mesh_area_weights(ptr(vertices), V, ptr(tri), T, ptr(areas), ptr(qarea), stream()),
-          "mh_mesh_area_weights")
+    launch("mh_mesh_area_weights", ptr(vertices), V, ptr(tri), T, ptr(areas), ptr(qarea))
     return areas, torch.cumsum(qarea[:T], 0)
 
 
@@ -177,8 +174,7 @@ def sample_surface(vertices: torch.Tensor, triangles: torch.Tensor, count: int, 
         raise MorpheusHipError("sample_surface: the mesh has zero total area")
     points = torch.empty(count, 3, dtype=torch.float32, device=dev)
     face = torch.empty(count, dtype=torch.int32, device=dev)
-    check(_lib.load().mh_sample_surface(ptr(vertices), V, ptr(tri), T, ptr(cum), ptr(uniforms), count, ptr(points), ptr(face),
-                                        stream()), "mh_sample_surface")
+    launch("mh_sample_surface", ptr(vertices), V, ptr(tri), T, ptr(cum), ptr(uniforms), count, ptr(points), ptr(face))
     return points, face
 
 
@@ -189,7 +185,7 @@ def transform_points(points: torch.Tensor, T) -> torch.Tensor:
     _points("points", points)
     Th, T_p = _doubles(np.asarray(T, dtype=np.float64)[:3])
     out = torch.empty_like(points)
-    check(_lib.load().mh_icp_transform(ptr(points), points.shape[0], T_p, ptr(out), stream()), "mh_icp_transform")
+    launch("mh_icp_transform", ptr(points), points.shape[0], T_p, ptr(out))
     return out
 
 
@@ -205,8 +201,7 @@ def icp_sums(moved: torch.Tensor, target: torch.Tensor, idx: torch.Tensor, d2: t
     lib = _lib.load()
     sums = torch.zeros(17, dtype=torch.float64, device=moved.device)
     ws = torch.empty(lib.mh_icp_workspace_bytes(), dtype=torch.uint8, device=moved.device)
-    check(lib.mh_icp_sums(ptr(moved), N, ptr(target), target.shape[0], ptr(idx), ptr(d2), ptr(ws), ptr(sums), stream()),
-          "mh_icp_sums")
+    launch("mh_icp_sums", ptr(moved), N, ptr(target), target.shape[0], ptr(idx), ptr(d2), ptr(ws), ptr(sums))
     return sums
 
 

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MorpheusHipError, check, ptr, require_gpu, stream
+from ._lib import MorpheusHipError, launch, ptr, require_gpu
 
 MODES = {"color": 0, "normal": 1, "shaded": 2}
 MAX_SIDE = 16384
@@ -45,8 +45,7 @@ def vertex_normal_sums(vertices: torch.Tensor, triangles: torch.Tensor):
     V, T = vertices.shape[0], tri.shape[0]
     acc = torch.empty(3 * V + 1, dtype=torch.int64, device=vertices.device)
     normals = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
-    check(_lib.load().mh_mesh_vertex_normals(ptr(vertices), V, ptr(tri), T, ptr(acc), ptr(normals), stream()),
-          "mh_mesh_vertex_normals")
+    launch("mh_mesh_vertex_normals", ptr(vertices), V, ptr(tri), T, ptr(acc), ptr(normals))
     return normals, acc
 
 
@@ -117,13 +116,11 @@ def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optiona
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     tri_id = torch.empty(H, W, dtype=torch.int32, device=dev)
     image = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
-    s = stream()
-    check(lib.mh_raster_depth(ptr(vertices), V, ptr(tri), T, w2c_p, fx, fy, cx, cy, H, W, float(near), int(small_area),
-                              ptr(ws), ptr(clipped), s), "mh_raster_depth")
+    launch("mh_raster_depth", ptr(vertices), V, ptr(tri), T, w2c_p, fx, fy, cx, cy, H, W, float(near), int(small_area), ptr(ws),
+           ptr(clipped))
     bg = [float(b) for b in background]
-    check(lib.mh_raster_resolve(ptr(vertices), V, ptr(tri), T, ptr(colors), ptr(normals), w2c_p, fx, fy, cx, cy, H, W,
-                                MODES[mode], float(ambient), bg[0], bg[1], bg[2], ptr(ws), ptr(depth), ptr(tri_id),
-                                ptr(image), s), "mh_raster_resolve")
+    launch("mh_raster_resolve", ptr(vertices), V, ptr(tri), T, ptr(colors), ptr(normals), w2c_p, fx, fy, cx, cy, H, W, MODES[mode],
+           float(ambient), bg[0], bg[1], bg[2], ptr(ws), ptr(depth), ptr(tri_id), ptr(image))
     return {"depth": depth, "tri_id": tri_id, "image": image, "clipped": clipped}
 
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream
+from ._lib import check, launch, ptr, require_gpu, stream
 from .packing import field_joint_packer, field_packer, warp_joint_packer, warp_packer
 
 
@@ -73,6 +73,15 @@ class KernelTimer:
 
 _STREAM_OBJECTS: dict = {}
 TIMER = KernelTimer()
+
+
+def _timed(name: str, *args, key: Optional[str] = None):
+    """launch(name, *args), timed under `key` (default: the entry point's own name) while TIMER is enabled"""
+    if not TIMER.enabled:
+        return launch(name, *args)
+    e = TIMER.start()
+    launch(name, *args)
+    TIMER.stop(key or name, e)
 
 
 _I32_CACHE = {}
@@ -150,9 +159,7 @@ def _bin_points(lib, x, bound):
     ws = torch.empty(lib.mh_grid_bin_workspace_ints(), dtype=torch.int32, device=dev)
     perm = _scratch(M, dev, torch.int32)
     bstart = torch.empty(lib.mh_grid_bin_index_ints(), dtype=torch.int32, device=dev)
-    _e = TIMER.start()
-    check(lib.mh_grid_bin_points(ptr(x), M, bound, ptr(ws), ptr(perm), ptr(bstart), stream()), "mh_grid_bin_points")
-    TIMER.stop("mh_grid_bin_points", _e)
+    _timed("mh_grid_bin_points", ptr(x), M, bound, ptr(ws), ptr(perm), ptr(bstart))
     return perm, bstart
 
 
@@ -216,14 +223,11 @@ def _grid_fwd(lib, x, embs, o_p, r_p, L, n_levels, bound, group):
         binned = _bin_points(lib, x, bound)
     for emb in embs:
         out = _scratch(M * L * 2, x.device).view(M, L * 2)
-        _e = TIMER.start()
         if binned is not None:
-            check(lib.mh_grid_encode_fwd_binned(ptr(x), ptr(emb), o_p, r_p, ptr(binned[0]), ptr(binned[1]), ptr(out), M, L,
-                                                n_levels, float(bound), stream()), "mh_grid_encode_fwd_binned")
+            _timed("mh_grid_encode_fwd_binned", ptr(x), ptr(emb), o_p, r_p, ptr(binned[0]), ptr(binned[1]), ptr(out), M, L,
+                   n_levels, float(bound))
         else:
-            check(lib.mh_grid_encode_fwd(ptr(x), ptr(emb), o_p, r_p, ptr(out), M, L, n_levels, float(bound), int(group), stream()),
-                  "mh_grid_encode_fwd")
-        TIMER.stop("mh_grid_encode_fwd_binned" if binned is not None else "mh_grid_encode_fwd", _e)
+            _timed("mh_grid_encode_fwd", ptr(x), ptr(emb), o_p, r_p, ptr(out), M, L, n_levels, float(bound), int(group))
         outs.append(out)
     return outs, binned
 
@@ -253,19 +257,12 @@ def _grid_bwd(lib, x, embs, grads, o_p, r_p, L, n_levels, bound, need_dx, gmax_p
             acc_dx = need_dx and g_x_total is not None
             g_x = g_x_total if acc_dx else (torch.empty_like(x) if need_dx else None)
             emb_acc = torch.empty(emb.numel(), dtype=torch.int64, device=emb.device)     # the kernel's fixed-point table sum
-            _e = TIMER.start()
-            check(lib.mh_grid_encode_bwd_binned(ptr(grad), ptr(x), ptr(emb), o_p, r_p, ptr(binned[0]), ptr(binned[1]),
-                                                g_emb_p, ptr(emb_acc), ptr(g_x), int(acc_dx), M, L, n_levels, bound,
-                                                None if gmax_ptrs is None else gmax_ptrs[k], stream()),
-                  "mh_grid_encode_bwd_binned")
-            TIMER.stop("mh_grid_encode_bwd_binned", _e)
+            _timed("mh_grid_encode_bwd_binned", ptr(grad), ptr(x), ptr(emb), o_p, r_p, ptr(binned[0]), ptr(binned[1]), g_emb_p,
+                   ptr(emb_acc), ptr(g_x), int(acc_dx), M, L, n_levels, bound, None if gmax_ptrs is None else gmax_ptrs[k])
             g_x_total = g_x
         else:
             g_x = torch.empty_like(x) if need_dx else None
-            _e = TIMER.start()
-            check(lib.mh_grid_encode_bwd(ptr(grad), ptr(x), ptr(emb), o_p, r_p, g_emb_p, ptr(g_x), M, L, n_levels,
-                                         bound, stream()), "mh_grid_encode_bwd")
-            TIMER.stop("mh_grid_encode_bwd", _e)
+            _timed("mh_grid_encode_bwd", ptr(grad), ptr(x), ptr(emb), o_p, r_p, g_emb_p, ptr(g_x), M, L, n_levels, bound)
             if need_dx:
                 g_x_total = g_x if g_x_total is None else g_x_total + g_x
         g_embs.append(g_emb)
@@ -323,7 +320,6 @@ class _Composite(torch.autograd.Function):
     def forward(ctx, sigma, t_starts, t_ends, rgb, ray_start, ray_cnt, padded=False):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(sigma, t_starts, t_ends, rgb, ray_start, ray_cnt)
-        lib = _lib.load()
         sigma, t_starts, t_ends = sigma.detach().contiguous(), t_starts.contiguous(), t_ends.contiguous()
         rgbc = rgb.detach().contiguous()
         N, M = ray_start.shape[0], sigma.shape[0]
@@ -334,26 +330,20 @@ class _Composite(torch.autograd.Function):
         weights = torch.zeros(M, device=dev) if padded else torch.empty(M, device=dev)
         opacity, depth = torch.empty(N, device=dev), torch.empty(N, device=dev)
         color = torch.empty(N, 3, device=dev)
-        _e = TIMER.start()
-        check(lib.mh_composite_fwd(ptr(sigma), ptr(t_starts), ptr(t_ends), ptr(rgbc), ptr(ray_start), ptr(ray_cnt),
-                                   ptr(weights), ptr(opacity), ptr(depth), ptr(color), N, stream()), "mh_composite_fwd")
-        TIMER.stop("mh_composite_fwd", _e)
+        _timed("mh_composite_fwd", ptr(sigma), ptr(t_starts), ptr(t_ends), ptr(rgbc), ptr(ray_start), ptr(ray_cnt), ptr(weights),
+               ptr(opacity), ptr(depth), ptr(color), N)
         ctx.save_for_backward(sigma, t_starts, t_ends, rgbc, ray_start, ray_cnt, weights)
         return weights, opacity, depth, color
 
     @staticmethod
     def backward(ctx, g_w, g_o, g_d, g_c):
-        lib = _lib.load()
         sigma, ts, te, rgb, ray_start, ray_cnt, weights = ctx.saved_tensors
         N = ray_start.shape[0]
         c = lambda t: None if t is None else t.contiguous()
         d_sigma = torch.zeros_like(sigma) if ctx.padded else torch.empty_like(sigma)
         d_rgb = torch.zeros_like(rgb) if ctx.padded else torch.empty_like(rgb)
-        _e = TIMER.start()
-        check(lib.mh_composite_bwd(ptr(sigma), ptr(ts), ptr(te), ptr(rgb), ptr(ray_start), ptr(ray_cnt), ptr(weights),
-                                   ptr(c(g_w)), ptr(c(g_o)), ptr(c(g_d)), ptr(c(g_c)), ptr(d_sigma), ptr(d_rgb), N,
-                                   stream()), "mh_composite_bwd")
-        TIMER.stop("mh_composite_bwd", _e)
+        _timed("mh_composite_bwd", ptr(sigma), ptr(ts), ptr(te), ptr(rgb), ptr(ray_start), ptr(ray_cnt), ptr(weights), ptr(c(g_w)),
+               ptr(c(g_o)), ptr(c(g_d)), ptr(c(g_c)), ptr(d_sigma), ptr(d_rgb), N)
         return d_sigma, None, None, d_rgb, None, None, None
 
 
@@ -371,32 +361,25 @@ def packed_info(ray_indices: torch.Tensor, n_rays: int):
 
 # ------------------------------------------------------------------------------------ sampler / rays
 def generate_rays(fx, fy, cx, cy, c2w, H, W, device):
-    lib = _lib.load()
     c2w = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(4, 4))
     o = torch.empty(H * W, 3, device=device)
     d = torch.empty(H * W, 3, device=device)
     require_gpu(o)
-    _e = TIMER.start()
-    check(lib.mh_generate_rays(float(fx), float(fy), float(cx), float(cy), c2w.ctypes.data_as(ctypes.c_void_p), H, W,
-                               ptr(o), ptr(d), stream()), "mh_generate_rays")
-    TIMER.stop("mh_generate_rays", _e)
+    _timed("mh_generate_rays", float(fx), float(fy), float(cx), float(cy), c2w.ctypes.data_as(ctypes.c_void_p), H, W, ptr(o),
+           ptr(d))
     return o, d
 
 
 def sample_uniform(rays_o, rays_d, jitter, S: int, bound: float, with_xyz: bool = False):
     """-> ray_idx int32 [N*S], t_starts, t_ends, xyz|None, ray_start, ray_cnt (no_grad, like morpheus.py:628)."""
     require_gpu(rays_o, rays_d, jitter)
-    lib = _lib.load()
     o, d, j = rays_o.detach().contiguous(), rays_d.detach().contiguous(), _ray_jitter(jitter, rays_o.shape[0])
     N, dev = o.shape[0], o.device
     ri = torch.empty(N * S, dtype=torch.int32, device=dev)
     ts, te = torch.empty(N * S, device=dev), torch.empty(N * S, device=dev)
     xyz = torch.empty(N * S, 3, device=dev) if with_xyz else None
     rs, rc = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
-    _e = TIMER.start()
-    check(lib.mh_sample_uniform(ptr(o), ptr(d), ptr(j), N, S, float(bound), ptr(ri), ptr(ts), ptr(te), ptr(xyz), ptr(rs),
-                                ptr(rc), stream()), "mh_sample_uniform")
-    TIMER.stop("mh_sample_uniform", _e)
+    _timed("mh_sample_uniform", ptr(o), ptr(d), ptr(j), N, S, float(bound), ptr(ri), ptr(ts), ptr(te), ptr(xyz), ptr(rs), ptr(rc))
     return ri, ts, te, xyz, rs, rc
 
 
@@ -405,7 +388,6 @@ def rays_sample_uniform(fx, fy, cx, cy, c2w, H: int, W: int, pix, jitter, S: int
     (j*W+i) on the device, the draw of datasets/dataset.py:412-423; None = the whole image.
     -> rays_o, rays_d [N,3], then the `sample_uniform` tuple."""
     require_gpu(jitter)
-    lib = _lib.load()
     c2w = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(4, 4))
     j, dev = jitter.contiguous(), jitter.device
     N = j.shape[0]
@@ -421,11 +403,8 @@ def rays_sample_uniform(fx, fy, cx, cy, c2w, H: int, W: int, pix, jitter, S: int
     ts, te = torch.empty(N * S, device=dev), torch.empty(N * S, device=dev)
     xyz = torch.empty(N * S, 3, device=dev) if with_xyz else None
     rs, rc = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
-    _e = TIMER.start()
-    check(lib.mh_rays_sample_uniform(float(fx), float(fy), float(cx), float(cy), c2w.ctypes.data_as(ctypes.c_void_p), H, W,
-                                     ptr(pix), ptr(j), N, S, float(bound), ptr(o), ptr(d), ptr(ri), ptr(ts), ptr(te),
-                                     ptr(xyz), ptr(rs), ptr(rc), stream()), "mh_rays_sample_uniform")
-    TIMER.stop("mh_rays_sample_uniform", _e)
+    _timed("mh_rays_sample_uniform", float(fx), float(fy), float(cx), float(cy), c2w.ctypes.data_as(ctypes.c_void_p), H, W,
+           ptr(pix), ptr(j), N, S, float(bound), ptr(o), ptr(d), ptr(ri), ptr(ts), ptr(te), ptr(xyz), ptr(rs), ptr(rc))
     return o, d, ri, ts, te, xyz, rs, rc
 
 
@@ -460,10 +439,8 @@ def march_rays(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.
         cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)     # [ray_cnt | overflow flag]
         cnt = cnt_ovf[:N]
         slots = torch.empty(2, N, cap, device=dev)
-        _e = TIMER.start()
-        check(lib.mh_march_slots(ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt),
-                                 ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N, stream()), "mh_march_slots")
-        TIMER.stop("mh_march_slots", _e)
+        _timed("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt),
+               ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
         csum = torch.cumsum(cnt_ovf, 0, dtype=torch.int32)              # last element = M + overflow flag
         start = (csum[:N] - cnt).contiguous()
         M, tot = csum[N - 1:].tolist()                                  # the one device->host sync
@@ -475,10 +452,7 @@ def march_rays(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.
     ri = torch.empty(M, dtype=torch.int32, device=dev)
     ts, te = torch.empty(M, device=dev), torch.empty(M, device=dev)
     if M > 0:
-        _e = TIMER.start()
-        check(lib.mh_march_pack(ptr(start), ptr(cnt), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te),
-                                stream()), "mh_march_pack")
-        TIMER.stop("mh_march_pack", _e)
+        _timed("mh_march_pack", ptr(start), ptr(cnt), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
     return ri, ts, te, start, cnt.contiguous()
 
 
@@ -493,8 +467,8 @@ def march_count(rays_o, rays_d, jitter, step: float, bound: float, binary: torch
     cap = int(lib.mh_march_cap(float(step), float(bound)))
     cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
     slots = torch.empty(2, N, cap, device=dev)
-    check(lib.mh_march_slots(ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt_ovf),
-                             ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N, stream()), "mh_march_slots")
+    launch("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt_ovf),
+           ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
     return cnt_ovf[:N].sum(dtype=torch.int32)
 
 
@@ -516,10 +490,8 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
     cnt = cnt_ovf[:N]
     slots = torch.empty(2, N, cap, device=dev)
-    _e = TIMER.start()
-    check(lib.mh_march_slots(ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt),
-                             ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N, stream()), "mh_march_slots")
-    TIMER.stop("mh_march_slots", _e)
+    _timed("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt), ptr(slots[0]),
+           ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
     csum = torch.cumsum(cnt, 0, dtype=torch.int32)
     start = (csum - cnt).contiguous()
     total = csum[N - 1]
@@ -528,10 +500,7 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     overflow = ((total > capacity) | (cnt_ovf[N] != 0)).to(torch.int32)
     ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
     ts, te = torch.zeros(capacity, device=dev), torch.zeros(capacity, device=dev)
-    _e = TIMER.start()
-    check(lib.mh_march_pack(ptr(start), ptr(cnt_c), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te), stream()),
-          "mh_march_pack")
-    TIMER.stop("mh_march_pack", _e)
+    _timed("mh_march_pack", ptr(start), ptr(cnt_c), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
     return ri, ts, te, start, cnt_c, n_valid, overflow
 
 
@@ -541,15 +510,13 @@ class _FdTaps(torch.autograd.Function):
     def forward(ctx, x, topo, eps, bound):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(x, topo)
-        lib = _lib.load()
         xc = x.detach().contiguous().float()
         M, dev = xc.shape[0], xc.device
         tc = None if topo is None else topo.detach().contiguous().float()
         C = 0 if tc is None else tc.shape[1]
         taps = _scratch(6 * M * 3, dev).view(6 * M, 3)
         topo6 = torch.empty(6 * M, C, device=dev) if tc is not None else torch.empty(0, device=dev)
-        check(lib.mh_fd_taps(ptr(xc), ptr(tc), C, float(eps), float(bound), M, ptr(taps), ptr(topo6 if tc is not None else None),
-                             stream()), "mh_fd_taps")
+        launch("mh_fd_taps", ptr(xc), ptr(tc), C, float(eps), float(bound), M, ptr(taps), ptr(topo6 if tc is not None else None))
         ctx.save_for_backward(xc)
         ctx.meta = (float(eps), float(bound), C, topo is not None)
         if not ctx.needs_input_grad[0]:
@@ -560,7 +527,6 @@ class _FdTaps(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_taps, g_topo6):
-        lib = _lib.load()
         (xc,) = ctx.saved_tensors
         eps, bound, C, has_topo = ctx.meta
         M, dev = xc.shape[0], xc.device
@@ -569,9 +535,8 @@ class _FdTaps(torch.autograd.Function):
         g_x = torch.empty(M, 3, device=dev) if want_x else None
         g_t = torch.empty(M, C, device=dev) if want_t else None
         if want_x or want_t:
-            check(lib.mh_fd_taps_bwd(ptr(xc), ptr(g_taps.contiguous() if want_x else None),
-                                     ptr(g_topo6.contiguous() if want_t else None), C, eps, bound, M, ptr(g_x), ptr(g_t), stream()),
-                  "mh_fd_taps_bwd")
+            launch("mh_fd_taps_bwd", ptr(xc), ptr(g_taps.contiguous() if want_x else None),
+                   ptr(g_topo6.contiguous() if want_t else None), C, eps, bound, M, ptr(g_x), ptr(g_t))
         return g_x, g_t, None, None
 
 
@@ -586,22 +551,20 @@ class _FdNormal(torch.autograd.Function):
     def forward(ctx, sdf6, eps):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(sdf6)
-        lib = _lib.load()
         s = sdf6.detach().contiguous().float()
         M, dev = s.shape[0], s.device
         normal, raw = torch.empty(M, 3, device=dev), torch.empty(M, 3, device=dev)
-        check(lib.mh_fd_normal_fwd(ptr(s), float(eps), M, ptr(normal), ptr(raw), stream()), "mh_fd_normal_fwd")
+        launch("mh_fd_normal_fwd", ptr(s), float(eps), M, ptr(normal), ptr(raw))
         ctx.save_for_backward(s)
         ctx.eps = float(eps)
         return normal, raw
 
     @staticmethod
     def backward(ctx, g_n, g_r):
-        lib = _lib.load()
         (s,) = ctx.saved_tensors
         g = torch.empty_like(s)
         c = lambda t: None if t is None else t.contiguous()
-        check(lib.mh_fd_normal_bwd(ptr(s), ptr(c(g_n)), ptr(c(g_r)), ctx.eps, s.shape[0], ptr(g), stream()), "mh_fd_normal_bwd")
+        launch("mh_fd_normal_bwd", ptr(s), ptr(c(g_n)), ptr(c(g_r)), ctx.eps, s.shape[0], ptr(g))
         return g, None
 
 
@@ -615,20 +578,17 @@ class _MultiCode(torch.autograd.Function):
     def forward(ctx, t, v0, v1, v2):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(t, v0, v1, v2)
-        lib = _lib.load()
         tc = t.detach().reshape(-1).contiguous().float()
         vs = [v.detach().contiguous() for v in (v0, v1, v2)]           # [1, C, size, 1]: contiguous == [C, size]
         C, sizes, F = vs[0].shape[1], [v.shape[2] for v in vs], tc.shape[0]
         out = torch.empty(F, 3 * C, device=tc.device)
-        check(lib.mh_multicode_fwd(ptr(tc), ptr(vs[0]), ptr(vs[1]), ptr(vs[2]), sizes[0], sizes[1], sizes[2], C, F, ptr(out),
-                                   stream()), "mh_multicode_fwd")
+        launch("mh_multicode_fwd", ptr(tc), ptr(vs[0]), ptr(vs[1]), ptr(vs[2]), sizes[0], sizes[1], sizes[2], C, F, ptr(out))
         ctx.save_for_backward(tc)
         ctx.meta = (C, sizes, [tuple(v.shape) for v in vs])
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = _lib.load()
         (tc,) = ctx.saved_tensors
         C, sizes, shapes = ctx.meta
         flat = torch.zeros(C * sum(sizes), device=tc.device)
@@ -636,8 +596,8 @@ class _MultiCode(torch.autograd.Function):
         for sz in sizes:
             gs.append(flat[o:o + C * sz])
             o += C * sz
-        check(lib.mh_multicode_bwd(ptr(tc), ptr(g_out.contiguous()), ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), sizes[0], sizes[1],
-                                   sizes[2], C, tc.shape[0], stream()), "mh_multicode_bwd")
+        launch("mh_multicode_bwd", ptr(tc), ptr(g_out.contiguous()), ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), sizes[0], sizes[1],
+               sizes[2], C, tc.shape[0])
         return (None, *[g.view(sh) for g, sh in zip(gs, shapes)])
 
 
@@ -652,26 +612,24 @@ class _SdfLosses(torch.autograd.Function):
     def forward(ctx, pred_sdf, ts, te, ray_idx, rays_depth, rays_mask, trunc, n_valid=None):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(pred_sdf, ts, te, ray_idx, rays_depth, rays_mask, n_valid)
-        lib = _lib.load()
         p = pred_sdf.detach().contiguous().float()
         dep = rays_depth.detach().reshape(-1).contiguous().float()
         msk = None if rays_mask is None else rays_mask.detach().reshape(-1).contiguous().float()
         sums = torch.empty(3, device=p.device)
         nv = None if n_valid is None else n_valid.detach().reshape(1).to(torch.int32).contiguous()
-        check(lib.mh_sdf_losses_fwd(ptr(p), ptr(ts), ptr(te), ptr(ray_idx), ptr(dep), ptr(msk), float(trunc), p.shape[0], ptr(nv),
-                                    ptr(sums), stream()), "mh_sdf_losses_fwd")
+        launch("mh_sdf_losses_fwd", ptr(p), ptr(ts), ptr(te), ptr(ray_idx), ptr(dep), ptr(msk), float(trunc), p.shape[0], ptr(nv),
+               ptr(sums))
         ctx.save_for_backward(p, ts, te, ray_idx, dep, msk, sums, nv)
         ctx.trunc = float(trunc)
         return sums[0] / sums[2], sums[1] / sums[2]
 
     @staticmethod
     def backward(ctx, g_fs, g_sl):
-        lib = _lib.load()
         p, ts, te, ray_idx, dep, msk, sums, nv = ctx.saved_tensors
         g = torch.empty_like(p)
         c = lambda t: None if t is None else t.reshape(1).contiguous().float()
-        check(lib.mh_sdf_losses_bwd(ptr(p), ptr(ts), ptr(te), ptr(ray_idx), ptr(dep), ptr(msk), ctx.trunc, p.shape[0], ptr(nv),
-                                    ptr(sums), ptr(c(g_fs)), ptr(c(g_sl)), ptr(g), stream()), "mh_sdf_losses_bwd")
+        launch("mh_sdf_losses_bwd", ptr(p), ptr(ts), ptr(te), ptr(ray_idx), ptr(dep), ptr(msk), ctx.trunc, p.shape[0], ptr(nv),
+               ptr(sums), ptr(c(g_fs)), ptr(c(g_sl)), ptr(g))
         return g, None, None, None, None, None, None, None
 
 
@@ -688,22 +646,20 @@ class _SamplePositions(torch.autograd.Function):
     def forward(ctx, rays_o, rays_d, ray_idx, ts, te, ray_start, ray_cnt):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(rays_o, rays_d, ray_idx, ts, te)
-        lib = _lib.load()
         o, d = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
         M = ts.shape[0]
         xyz = torch.empty(M, 3, device=o.device)
-        check(lib.mh_sample_positions(ptr(o), ptr(d), ptr(ray_idx), ptr(ts), ptr(te), M, ptr(xyz), stream()), "mh_sample_positions")
+        launch("mh_sample_positions", ptr(o), ptr(d), ptr(ray_idx), ptr(ts), ptr(te), M, ptr(xyz))
         ctx.save_for_backward(ts, te, ray_start, ray_cnt)
         ctx.n = o.shape[0]
         return xyz
 
     @staticmethod
     def backward(ctx, g_xyz):
-        lib = _lib.load()
         ts, te, ray_start, ray_cnt = ctx.saved_tensors
         g_o, g_d = torch.empty(ctx.n, 3, device=ts.device), torch.empty(ctx.n, 3, device=ts.device)
-        check(lib.mh_sample_positions_bwd(ptr(g_xyz.contiguous()), ptr(ts), ptr(te), ptr(ray_start), ptr(ray_cnt), ctx.n, ptr(g_o),
-                                          ptr(g_d), stream()), "mh_sample_positions_bwd")
+        launch("mh_sample_positions_bwd", ptr(g_xyz.contiguous()), ptr(ts), ptr(te), ptr(ray_start), ptr(ray_cnt), ctx.n, ptr(g_o),
+               ptr(g_d))
         return g_o, g_d, None, None, None, None, None
 
 
@@ -740,11 +696,8 @@ def _wgrad(lib, acts, dpre, acts_tile, dpre_tile, act_off, dpre_off, in_pad, out
     # an empty query (n_tiles == 0) returns MH_OK without writing: the token gradient must then be zeros, not heap contents
     raw = torch.empty(dw_len + db_len, device=dev) if n_tiles > 0 else torch.zeros(dw_len + db_len, device=dev)
     dw_raw, db_raw = raw[:dw_len], raw[dw_len:]
-    _e = TIMER.start()
-    fn = lib.mh_mlp_wgrad_b3 if b3 else lib.mh_mlp_wgrad
-    check(fn(ptr(acts), ptr(dpre), acts_tile, dpre_tile, n_layers, a_p, d_p, i_p, o_p, il_p, ol_p, ptr(ws), ptr(dw_raw), ptr(db_raw),
-             n_tiles, stream()), "mh_mlp_wgrad")
-    TIMER.stop("mh_mlp_wgrad[" + tag + "]", _e)
+    _timed("mh_mlp_wgrad_b3" if b3 else "mh_mlp_wgrad", ptr(acts), ptr(dpre), acts_tile, dpre_tile, n_layers, a_p, d_p, i_p, o_p, il_p,
+           ol_p, ptr(ws), ptr(dw_raw), ptr(db_raw), n_tiles, key="mh_mlp_wgrad[" + tag + "]")
     return raw          # dw_raw | db_raw, tile-row order (packing.JointPacker.unpack_grads maps it back)
 
 
@@ -856,7 +809,6 @@ class _PackOperands(torch.autograd.Function):
         if b3:
             # bf16x3 forward fragments (csrc/mlp_b3.hip): the same weights gathered in the 32x32x16 fragment order, then cut
             # into [hi | mid | lo] bf16 planes per layer by one launch
-            lib = _lib.load()
             w3 = torch.zeros((jp.fwd3_total_f4 + jp.bwd3_total_f4) * 4, device=flat.device)
             for key, layers, base in (("fwd3", jp.b3_layers, 0), ("bwd3", jp.b3T_layers, jp.fwd3_total_f4)):
                 if key == "bwd3" and not jp.sliced_bwd_for(b3):
@@ -865,7 +817,7 @@ class _PackOperands(torch.autograd.Function):
                 so, sp = _i32arr([l[0] for l in layers])
                 no, np_ = _i32arr([l[1] for l in layers])
                 do, dp = _i32arr([l[2] + base for l in layers])
-                check(lib.mh_b3_slice(ptr(src), ptr(w3), len(layers), sp, np_, dp, stream()), "mh_b3_slice")
+                launch("mh_b3_slice", ptr(src), ptr(w3), len(layers), sp, np_, dp)
         else:
             w3 = fpack.new_empty(0)
         token = fpack.new_empty(jp.raw_len)
@@ -952,14 +904,12 @@ class _WarpMLP(torch.autograd.Function):
         deform, topo = torch.empty(M, 3, device=dev), torch.empty(M, 2, device=dev)
         b0d, b0t = bias0_d.detach().contiguous(), bias0_t.detach().contiguous()
         slot_c = None if slot is None else slot.contiguous()
-        _e = TIMER.start()
         if opnd.w3 is not None:
-            check(lib.mh_warp_fwd_b3(ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
-                                     n_bands, ptr(deform), ptr(topo), ptr(acts), M, stream()), "mh_warp_fwd_b3")
+            _timed("mh_warp_fwd_b3", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
+                   n_bands, ptr(deform), ptr(topo), ptr(acts), M, key="mh_warp_fwd")
         else:
-            check(lib.mh_warp_fwd(ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), n_bands,
-                                  ptr(deform), ptr(topo), ptr(acts), M, stream()), "mh_warp_fwd")
-        TIMER.stop("mh_warp_fwd", _e)
+            _timed("mh_warp_fwd", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), n_bands,
+                   ptr(deform), ptr(topo), ptr(acts), M)
         ctx.b3, ctx.mode = opnd.wT3 is not None, opnd.mode
         if ctx.b3:
             wdT, wtT = opnd.wT3
@@ -979,18 +929,15 @@ class _WarpMLP(torch.autograd.Function):
         dpre = _scratch(lib.mh_warp_dpre_floats(M), dev)
         g_x = torch.empty(M, 3, device=dev) if ctx.needs_input_grad[0] else None   # NULL -> the kernel skips the W0^T stage
         c = lambda t: None if t is None else t.contiguous()
-        _e = TIMER.start()
         gd, gt = c(g_deform), c(g_topo)
         # b3, large batches: dPre4 (16 KB of a tile's 172) is not parked, the layer-4 weight-gradient launches make it again from
         # the incoming gradient, the ReLU sign words and the T5 slices -- the same bits (include/morpheus_hip.h: mh_warp_wgrad_b3)
         regen = bool(ctx.b3 and REGEN_DPRE4 and lib.mh_warp_regen_dpre4(M))
         if ctx.b3:
-            check(lib.mh_warp_bwd_data_b3(ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre), ptr(g_x), M,
-                                          int(regen), stream()), "mh_warp_bwd_data")
+            _timed("mh_warp_bwd_data_b3", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre),
+                   ptr(g_x), M, int(regen), key="mh_warp_bwd_data")
         else:
-            check(lib.mh_warp_bwd_data(ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre), ptr(g_x), M,
-                                       stream()), "mh_warp_bwd_data")
-        TIMER.stop("mh_warp_bwd_data", _e)
+            _timed("mh_warp_bwd_data", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre), ptr(g_x), M)
         if ctx.b3:
             jp = ctx.jp
             ws = torch.empty(max(lib.mh_warp_wgrad_workspace_floats(M), 1), device=dev)
@@ -998,10 +945,8 @@ class _WarpMLP(torch.autograd.Function):
             raw_len = dw_len + sum(_WARP_WG[3])
             assert raw_len == jp.raw_len
             raw = torch.empty(raw_len, device=dev) if M > 0 else torch.zeros(raw_len, device=dev)      # (an empty call writes nothing)
-            _e = TIMER.start()
-            check(lib.mh_warp_wgrad_b3(ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), ptr(ws), ptr(raw[:dw_len]),
-                                       ptr(raw[dw_len:]), M, stream()), "mh_warp_wgrad_b3")
-            TIMER.stop("mh_mlp_wgrad[warp]", _e)
+            _timed("mh_warp_wgrad_b3", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), ptr(ws),
+                   ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
         else:
             raw = _wgrad(lib, acts, dpre, WARP_ACT_ROWS * 32, WARP_DPRE_ROWS * 32, _WARP_WG[0], _WARP_WG[1], _WARP_WG[2],
                          _WARP_WG[3], n_tiles, dev, "warp", b3=False, in_live=_WARP_WG[4], out_live=_WARP_WG[5])
@@ -1052,14 +997,12 @@ def _field_fwd(lib, xc, fs, fc, tp, beta_c, n_bands, with_color, opnd, need_grad
     acts = _scratch(lib.mh_field_acts_floats(M), dev) if need_grad else None
     sdf, sigma = torch.empty(M, device=dev), torch.empty(M, device=dev)
     albedo = torch.empty(M, 3, device=dev) if with_color else None
-    _e = TIMER.start()
     if opnd.w3 is not None:
-        check(lib.mh_field_fwd_b3(ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(opnd.w3[0]), ptr(b), ptr(beta_c), n_bands,
-                  int(bool(with_color)), ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M, stream()), "mh_field_fwd_b3")
+        _timed("mh_field_fwd_b3", ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(opnd.w3[0]), ptr(b), ptr(beta_c), n_bands,
+               int(bool(with_color)), ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M, key="mh_field_fwd")
     else:
-        check(lib.mh_field_fwd(ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(w), ptr(b), ptr(beta_c), n_bands, int(bool(with_color)),
-                               ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M, stream()), "mh_field_fwd")
-    TIMER.stop("mh_field_fwd", _e)
+        _timed("mh_field_fwd", ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(w), ptr(b), ptr(beta_c), n_bands, int(bool(with_color)),
+               ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M)
     return sdf, sigma, albedo, acts
 
 
@@ -1106,13 +1049,10 @@ def _field_bwd(lib, xc, wT, beta_c, acts, sdf, albedo, g_sdf, g_sigma, g_albedo,
     if raw_into is None:      # an empty query returns MH_OK without writing: the gradient must then be zeros, not heap contents
         raw = torch.empty(jp.raw_len + 1, device=dev) if M > 0 else torch.zeros(jp.raw_len + 1, device=dev)
     c = lambda t: None if t is None else t.contiguous()
-    _e = TIMER.start()
-    fused = lib.mh_field_bwd_fused_b3 if b3 else lib.mh_field_bwd_fused
-    check(fused(ptr(xc), ptr(sdf), ptr(albedo if with_color else None), ptr(c(g_sdf)), ptr(c(g_sigma)), ptr(c(g_albedo)), ptr(wT),
-                                 ptr(beta_c), n_bands, int(with_color), ptr(acts), ptr(dgeo), ptr(ws),
-                                 ptr(raw) if raw_into is None else ctypes.c_void_p(raw_into), int(raw_into is not None), ptr(g_xc),
-                                 ptr(g_fs), ptr(g_fc), ptr(g_tp), ptr(gmax), M, stream()), "mh_field_bwd_fused")
-    TIMER.stop("mh_field_bwd_fused", _e)
+    _timed("mh_field_bwd_fused_b3" if b3 else "mh_field_bwd_fused", ptr(xc), ptr(sdf), ptr(albedo if with_color else None), ptr(c(g_sdf)),
+           ptr(c(g_sigma)), ptr(c(g_albedo)), ptr(wT), ptr(beta_c), n_bands, int(with_color), ptr(acts), ptr(dgeo), ptr(ws),
+           ptr(raw) if raw_into is None else ctypes.c_void_p(raw_into), int(raw_into is not None), ptr(g_xc), ptr(g_fs), ptr(g_fc),
+           ptr(g_tp), ptr(gmax), M, key="mh_field_bwd_fused")
     return g_xc, g_fs, g_fc, g_tp, raw, gmax
 
 
@@ -1239,14 +1179,13 @@ class _WeightNormAll(torch.autograd.Function):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         vs, gs = vg[:n], vg[n:]
         require_gpu(*vg)
-        lib = _lib.load()
         vs_c = [v.detach().contiguous() for v in vs]
         gs_c = [g.detach().contiguous() for g in gs]
         ws = [torch.empty_like(v) for v in vs_c]
         PA, IA = ctypes.c_void_p * n, ctypes.c_int32 * n
         rows, cols = IA(*[v.shape[0] for v in vs_c]), IA(*[v.shape[1] for v in vs_c])
-        check(lib.mh_weight_norm_fwd(n, PA(*[ptr(v) for v in vs_c]), PA(*[ptr(g) for g in gs_c]), PA(*[ptr(w) for w in ws]),
-                                     rows, cols, stream()), "mh_weight_norm_fwd")
+        launch("mh_weight_norm_fwd", n, PA(*[ptr(v) for v in vs_c]), PA(*[ptr(g) for g in gs_c]), PA(*[ptr(w) for w in ws]), rows,
+               cols)
         ctx.save_for_backward(*vs_c, *gs_c)
         ctx.n = n
         return tuple(ws)
@@ -1254,7 +1193,6 @@ class _WeightNormAll(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gw):
         n = ctx.n
-        lib = _lib.load()
         saved = ctx.saved_tensors
         vs, gs = saved[:n], saved[n:]
         gw_c = [None if g is None else g.contiguous() for g in gw]
@@ -1262,9 +1200,8 @@ class _WeightNormAll(torch.autograd.Function):
         dgs = [torch.empty_like(g) for g in gs]
         PA, IA = ctypes.c_void_p * n, ctypes.c_int32 * n
         rows, cols = IA(*[v.shape[0] for v in vs]), IA(*[v.shape[1] for v in vs])
-        check(lib.mh_weight_norm_bwd(n, PA(*[ptr(v) for v in vs]), PA(*[ptr(g) for g in gs]), PA(*[ptr(g) for g in gw_c]),
-                                     PA(*[ptr(t) for t in dvs]), PA(*[ptr(t) for t in dgs]), rows, cols, stream()),
-              "mh_weight_norm_bwd")
+        launch("mh_weight_norm_bwd", n, PA(*[ptr(v) for v in vs]), PA(*[ptr(g) for g in gs]), PA(*[ptr(g) for g in gw_c]),
+               PA(*[ptr(t) for t in dvs]), PA(*[ptr(t) for t in dgs]), rows, cols)
         return (None, *dvs, *dgs)
 
 
@@ -1294,7 +1231,7 @@ class _MaskedMean(torch.autograd.Function):
         nv = None if n_valid is None else n_valid.detach().reshape(1).to(torch.int32).contiguous()
         ws = torch.empty(lib.mh_masked_mean_workspace_floats(), device=a_c.device)
         out = torch.empty(2, device=a_c.device)
-        check(lib.mh_masked_mean_fwd(kind, ptr(a_c), ptr(b_c), ptr(w_c), M, C, ptr(nv), ptr(ws), ptr(out), stream()), "mh_masked_mean_fwd")
+        launch("mh_masked_mean_fwd", kind, ptr(a_c), ptr(b_c), ptr(w_c), M, C, ptr(nv), ptr(ws), ptr(out))
         ctx.save_for_backward(a_c, b_c, w_c, nv, out)
         ctx.kind, ctx.shape = kind, a.shape
         return out[0]
@@ -1303,7 +1240,6 @@ class _MaskedMean(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return None, None, None, None, None
-        lib = _lib.load()
         a_c, b_c, w_c, nv, out = ctx.saved_tensors
         M = a_c.shape[0]
         C = max(a_c.numel() // max(M, 1), 1)
@@ -1311,8 +1247,8 @@ class _MaskedMean(torch.autograd.Function):
         g_a = torch.empty_like(a_c) if want_a else None
         g_b = torch.empty_like(b_c) if want_b else None
         if want_a or want_b:
-            check(lib.mh_masked_mean_bwd(ctx.kind, ptr(a_c), ptr(b_c), ptr(w_c), M, C, ptr(nv), ptr(out), ptr(g.reshape(1).contiguous().float()),
-                                         ptr(g_a), ptr(g_b), stream()), "mh_masked_mean_bwd")
+            launch("mh_masked_mean_bwd", ctx.kind, ptr(a_c), ptr(b_c), ptr(w_c), M, C, ptr(nv), ptr(out),
+                   ptr(g.reshape(1).contiguous().float()), ptr(g_a), ptr(g_b))
         return None, g_a, g_b, None, None
 
 
@@ -1329,13 +1265,12 @@ class _OrthoPerturb(torch.autograd.Function):
     def forward(ctx, x, normals, phi, scale):
         ctx.set_materialize_grads(False)
         require_gpu(x, normals, phi)
-        lib = _lib.load()
         x_c, n_c = x.detach().contiguous().float(), normals.detach().contiguous().float()
         p_c = phi.detach().reshape(-1).contiguous().float()
         M = x_c.shape[0]
         assert x_c.shape == (M, 3) and n_c.shape == (M, 3) and p_c.numel() == M
         out = torch.empty_like(x_c)
-        check(lib.mh_ortho_perturb_fwd(ptr(x_c), ptr(n_c), ptr(p_c), float(scale), M, ptr(out), stream()), "mh_ortho_perturb_fwd")
+        launch("mh_ortho_perturb_fwd", ptr(x_c), ptr(n_c), ptr(p_c), float(scale), M, ptr(out))
         ctx.save_for_backward(n_c, p_c)
         ctx.scale = float(scale)
         return out
@@ -1347,10 +1282,9 @@ class _OrthoPerturb(torch.autograd.Function):
         n_c, p_c = ctx.saved_tensors
         g_n = None
         if ctx.needs_input_grad[1]:
-            lib = _lib.load()
             g_c = g.contiguous().float()
             g_n = torch.empty_like(n_c)
-            check(lib.mh_ortho_perturb_bwd(ptr(n_c), ptr(p_c), ptr(g_c), ctx.scale, n_c.shape[0], ptr(g_n), stream()), "mh_ortho_perturb_bwd")
+            launch("mh_ortho_perturb_bwd", ptr(n_c), ptr(p_c), ptr(g_c), ctx.scale, n_c.shape[0], ptr(g_n))
         return (g if ctx.needs_input_grad[0] else None), g_n, None, None
 
 
@@ -1365,13 +1299,12 @@ class _SmoothPoints(torch.autograd.Function):
     def forward(ctx, depth, off, rays_o, rays_d):
         ctx.set_materialize_grads(False)
         require_gpu(depth, off, rays_o, rays_d)
-        lib = _lib.load()
         d_c, f_c = depth.detach().reshape(-1).contiguous().float(), off.detach().reshape(-1).contiguous().float()
         o_c, r_c = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
         N, K = d_c.shape[0], f_c.shape[0]
         assert o_c.shape == (N, 3) and r_c.shape == (N, 3)
         pts, keep = torch.empty(K * N, 3, device=d_c.device), torch.empty(K * N, device=d_c.device)
-        check(lib.mh_smooth_points_fwd(ptr(d_c), ptr(f_c), ptr(o_c), ptr(r_c), N, K, ptr(pts), ptr(keep), stream()), "mh_smooth_points_fwd")
+        launch("mh_smooth_points_fwd", ptr(d_c), ptr(f_c), ptr(o_c), ptr(r_c), N, K, ptr(pts), ptr(keep))
         ctx.save_for_backward(d_c, f_c, r_c)
         ctx.depth_shape = depth.shape
         ctx.mark_non_differentiable(keep)
@@ -1388,8 +1321,8 @@ class _SmoothPoints(torch.autograd.Function):
         g_o = torch.empty(N, 3, device=g.device) if need_o else None
         g_d = torch.empty(N, 3, device=g.device) if need_d else None
         if need_depth or need_o or need_d:
-            check(_lib.load().mh_smooth_points_bwd(ptr(g.contiguous().float()), ptr(d_c), ptr(f_c), ptr(r_c), N, K, ptr(g_depth), ptr(g_o),
-                                                   ptr(g_d), stream()), "mh_smooth_points_bwd")
+            launch("mh_smooth_points_bwd", ptr(g.contiguous().float()), ptr(d_c), ptr(f_c), ptr(r_c), N, K, ptr(g_depth), ptr(g_o),
+                   ptr(g_d))
         return (None if g_depth is None else g_depth.view(ctx.depth_shape)), None, g_o, g_d
 
 
@@ -1408,7 +1341,7 @@ class _BgBlend(torch.autograd.Function):
         N = c_c.shape[0]
         assert c_c.shape == (N, 3) and b_c.shape == (N, 3) and o_c.shape[0] == N
         image = torch.empty_like(c_c)
-        check(_lib.load().mh_bg_blend_fwd(ptr(c_c), ptr(o_c), ptr(b_c), N, ptr(image), stream()), "mh_bg_blend_fwd")
+        launch("mh_bg_blend_fwd", ptr(c_c), ptr(o_c), ptr(b_c), N, ptr(image))
         ctx.save_for_backward(o_c, b_c)
         ctx.opacity_shape = opacity.shape
         return image
@@ -1424,7 +1357,7 @@ class _BgBlend(torch.autograd.Function):
         g_o = torch.empty(N, device=g.device) if need_o else None
         g_b = torch.empty(N, 3, device=g.device) if need_b else None
         if need_o or need_b:
-            check(_lib.load().mh_bg_blend_bwd(ptr(g_c), ptr(o_c), ptr(b_c), N, ptr(g_o), ptr(g_b), stream()), "mh_bg_blend_bwd")
+            launch("mh_bg_blend_bwd", ptr(g_c), ptr(o_c), ptr(b_c), N, ptr(g_o), ptr(g_b))
         return (g_c if need_c else None), (None if g_o is None else g_o.view(ctx.opacity_shape)), g_b
 
 
@@ -1438,14 +1371,13 @@ class _PoseApply(torch.autograd.Function):
     def forward(ctx, rays_o, rays_d, pose, frame_of_row, n_per_row):
         ctx.set_materialize_grads(False)
         require_gpu(rays_o, rays_d, pose, frame_of_row)
-        lib = _lib.load()
         o_c, d_c = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
         p_c = pose.detach().contiguous().float()
         f_c = frame_of_row.detach().reshape(-1).long().contiguous()
         B = f_c.numel()
         assert o_c.shape == (B * n_per_row, 3) and d_c.shape == o_c.shape and p_c.dim() == 2 and p_c.shape[1] == 6
         o_out, d_out = torch.empty_like(o_c), torch.empty_like(d_c)
-        check(lib.mh_pose_apply_fwd(ptr(o_c), ptr(d_c), ptr(p_c), ptr(f_c), B, n_per_row, ptr(o_out), ptr(d_out), stream()), "mh_pose_apply_fwd")
+        launch("mh_pose_apply_fwd", ptr(o_c), ptr(d_c), ptr(p_c), ptr(f_c), B, n_per_row, ptr(o_out), ptr(d_out))
         ctx.save_for_backward(d_c, p_c, f_c)
         ctx.n_per_row = n_per_row
         return o_out, d_out
@@ -1461,8 +1393,8 @@ class _PoseApply(torch.autograd.Function):
         g_d = None if g_d is None else g_d.contiguous().float()
         ws = torch.empty(max(lib.mh_pose_bwd_workspace_floats(B, ctx.n_per_row), 1), device=d_c.device)
         g_pose = torch.empty_like(p_c)
-        check(lib.mh_pose_apply_bwd(ptr(d_c), ptr(p_c), ptr(f_c), B, ctx.n_per_row, p_c.shape[0], ptr(g_o), ptr(g_d), ptr(ws), ptr(g_pose),
-                                    stream()), "mh_pose_apply_bwd")
+        launch("mh_pose_apply_bwd", ptr(d_c), ptr(p_c), ptr(f_c), B, ctx.n_per_row, p_c.shape[0], ptr(g_o), ptr(g_d), ptr(ws),
+               ptr(g_pose))
         return None, None, g_pose, None, None
 
 
@@ -1478,15 +1410,14 @@ class _RenderLoss(torch.autograd.Function):
     def forward(ctx, pred_rgb, pred_depth, opacity, image, depth, mask, bg, rays_o, rays_d, w_rgb, w_mask, w_depth):
         ctx.set_materialize_grads(False)
         require_gpu(pred_rgb, pred_depth, opacity, image, depth, mask, bg, rays_o, rays_d)
-        lib = _lib.load()
         c = lambda t, *shape: t.detach().reshape(*shape).contiguous().float()
         N = pred_depth.numel()
         pr, pd, op = c(pred_rgb, N, 3), c(pred_depth, N), c(opacity, N)
         im, dp, mk, bgc = c(image, 3, N), c(depth, N), c(mask, N), c(bg, N, 3)
         ro, rd = c(rays_o, N, 3), c(rays_d, N, 3)
         gt_rgb, valid, out = torch.empty(3, N, device=pr.device), torch.empty(N, device=pr.device), torch.empty(4, device=pr.device)
-        check(lib.mh_render_loss_fwd(ptr(pr), ptr(pd), ptr(op), ptr(im), ptr(dp), ptr(mk), ptr(bgc), ptr(ro), ptr(rd), N, w_rgb, w_mask,
-                                     w_depth, ptr(gt_rgb), ptr(valid), ptr(out), stream()), "mh_render_loss_fwd")
+        launch("mh_render_loss_fwd", ptr(pr), ptr(pd), ptr(op), ptr(im), ptr(dp), ptr(mk), ptr(bgc), ptr(ro), ptr(rd), N, w_rgb,
+               w_mask, w_depth, ptr(gt_rgb), ptr(valid), ptr(out))
         ctx.save_for_backward(pr, pd, op, gt_rgb, dp, mk, valid)
         ctx.w = (float(w_rgb), float(w_mask), float(w_depth))
         ctx.shapes = (pred_rgb.shape, pred_depth.shape, opacity.shape)
@@ -1498,7 +1429,6 @@ class _RenderLoss(torch.autograd.Function):
     def backward(ctx, g, _g_terms, _g_gt, _g_valid):
         if g is None:
             return (None,) * 12
-        lib = _lib.load()
         pr, pd, op, gt_rgb, dp, mk, valid = ctx.saved_tensors
         N = pd.numel()
         need = ctx.needs_input_grad
@@ -1506,9 +1436,8 @@ class _RenderLoss(torch.autograd.Function):
         g_dep = torch.empty_like(pd) if need[1] else None
         g_op = torch.empty_like(op) if need[2] else None
         if need[0] or need[1] or need[2]:
-            check(lib.mh_render_loss_bwd(ptr(pr), ptr(pd), ptr(op), ptr(gt_rgb), ptr(dp), ptr(mk), ptr(valid), N, *ctx.w,
-                                         ptr(g.reshape(1).contiguous().float()), ptr(g_rgb), ptr(g_dep), ptr(g_op), stream()),
-                  "mh_render_loss_bwd")
+            launch("mh_render_loss_bwd", ptr(pr), ptr(pd), ptr(op), ptr(gt_rgb), ptr(dp), ptr(mk), ptr(valid), N, *ctx.w,
+                   ptr(g.reshape(1).contiguous().float()), ptr(g_rgb), ptr(g_dep), ptr(g_op))
         s = ctx.shapes
         return (None if g_rgb is None else g_rgb.view(s[0]), None if g_dep is None else g_dep.view(s[1]),
                 None if g_op is None else g_op.view(s[2]), None, None, None, None, None, None, None, None, None)

@@ -25,8 +25,7 @@ from typing import Iterable, List
 
 import torch
 
-from . import _lib
-from ._lib import MorpheusHipError, check, ptr, stream
+from ._lib import MorpheusHipError, launch, ptr
 from .dist import GradBucket
 
 
@@ -131,7 +130,6 @@ class FlatAdam(torch.optim.Optimizer):
             raise NotImplementedError("FlatAdam.step takes no closure")
         if not self.flat_p.is_cuda:
             raise MorpheusHipError("FlatAdam steps on an MI355X only; there is no CPU path")
-        lib = _lib.load()
         self.bucket.collect()       # no-op when allreduce_mean() already gathered the gradients
         # the kernels below write the parameters through raw pointers: move their version counters as an in-place torch update
         # would (the model's step cache -- model.scene_representation._step_cache -- reads them to see that a step has ended)
@@ -155,10 +153,9 @@ class FlatAdam(torch.optim.Optimizer):
                 self._seg_scratch = torch.empty(2 * ns, dtype=torch.float32, device=dev)
             seg_flags = self.bucket.grad_counts[self._seg_flag_index]
             self.bucket.missing = set()
-            check(lib.mh_adam_step_dev(ptr(self.flat_p), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n, ns,
-                                       self._kseg_end_c, lrs, ptr(seg_flags), ptr(self._steps_dev), ptr(self._seg_scratch),
-                                       float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), stream()),
-                  "mh_adam_step_dev")
+            launch("mh_adam_step_dev", ptr(self.flat_p), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
+                   ns, self._kseg_end_c, lrs, ptr(seg_flags), ptr(self._steps_dev), ptr(self._seg_scratch), float(g0["betas"][0]),
+                   float(g0["betas"][1]), float(g0["eps"]))
             return
         # torch.optim.Adam skips a parameter whose gradient is None: no moment decay, no move, no step increment
         no_grad = self.bucket.missing
@@ -170,9 +167,9 @@ class FlatAdam(torch.optim.Optimizer):
                 self._steps[pi] += 1
                 steps.append(self._steps[pi])
         self.bucket.missing = set()
-        check(lib.mh_adam_step(ptr(self.flat_p), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n, ns,
-                               self._kseg_end_c, lrs, (ctypes.c_int64 * ns)(*steps), float(g0["betas"][0]),
-                               float(g0["betas"][1]), float(g0["eps"]), stream()), "mh_adam_step")
+        launch("mh_adam_step", ptr(self.flat_p), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n, ns,
+               self._kseg_end_c, lrs, (ctypes.c_int64 * ns)(*steps), float(g0["betas"][0]), float(g0["betas"][1]),
+               float(g0["eps"]))
 
 
 class FlatEMA:

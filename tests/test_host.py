@@ -70,6 +70,88 @@ def test_argument_validation_without_gpu(lib):
     assert lib.mh_graph_count_memset_nodes(None, None, None, None) == 1 and lib.mh_graph_replace_memset_nodes(None, None) == 1
 
 
+def _declared_parameter_counts(hdr):
+    """name -> number of parameters of every `mh_` declaration of the header text, counted without morpheus_amd._lib's parser:
+    comments cut, then the commas at parenthesis depth 0 of each parameter list"""
+    code = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    counts = {}
+    for m in re.finditer(r"\b(mh_[a-zA-Z0-9_]+)\s*\(", code):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(code[i], 0)
+            commas += code[i] == "," and depth == 1
+            i += 1
+        params = code[m.end():i - 1].strip()
+        counts[m.group(1)] = 0 if params == "void" else commas + 1
+    return counts
+
+
+def test_signatures_are_bound_from_the_header(lib):
+    """include/morpheus_hip.h is the only description of an entry point: literal pins of the parsed signature for one entry point
+    per type and awkward layout, and every function of the loaded library carries as many argtypes as its declaration has
+    parameters (ctypes' default for an unbound function -- int arguments, int result -- must be impossible)."""
+    from morpheus_amd import _lib
+    P, I32, I64, F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    pins = {"mh_status_string": (ctypes.c_char_p, [I32]),                                   # `const char *` result
+            "mh_grid_stage_min_points": (I64, [I64]),                                       # int64_t both ways
+            "mh_raster_resolve": (I32, [P, I64, P, I64, P, P, P, F, F, F, F, I32, I32, I32, F, F, F, F, P, P, P, P, P]),
+            "mh_cull_vertices": (I32, [P, I64, P, P, I32, I32, P, P, F, P, P, P, P]),       # `const double *` host pointers
+            "mh_grid_encode_bwd_binned": (I32, [P] * 10 + [I32, I64, I32, I32, F, P, P]),   # `int64_t *`, `const uint32_t *`
+            "mh_icp_workspace_bytes": (I64, [])}                                            # `(void)`
+    for name, (res, args) in pins.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    counts = _declared_parameter_counts(open(os.path.join(ROOT, "include", "morpheus_hip.h")).read())
+    assert set(counts) == set(_lib.EXPORTS) and len(counts) >= 95
+    assert counts["mh_raster_resolve"] == 23 and counts["mh_abi_version"] == 0
+    for name, n in counts.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, name
+    assert _lib.EXPORTS[:2] == ("mh_abi_version", "mh_status_string")                       # header order
+
+
+def test_header_parser_refuses_what_it_cannot_type(lib):
+    """A declaration outside the parser's closed type table, or one it cannot read at all, raises and names the declaration; so
+    does a library whose ABI version is not the header's.  Fed with text: the real header is not touched."""
+    from morpheus_amd import _lib
+    head = "#define MH_ABI_VERSION 9   /* history */\nint mh_abi_version(void);\n"
+    abi, sigs = _lib.parse_header(head + "double mh_ok(const double *a, double b, /* why */ float c, int d);  // trailing\n")
+    assert abi == 9 and list(sigs) == ["mh_abi_version", "mh_ok"]
+    assert sigs["mh_ok"] == (ctypes.c_double, [ctypes.c_void_p, ctypes.c_double, ctypes.c_float, ctypes.c_int32])
+    for bad in ("int mh_bad(size_t n);", "int mh_bad(struct mh_box b);", "int mh_bad(unsigned int a);", "int mh_bad(int);",
+                "int mh_bad();", "void mh_bad(int a);", "float *mh_bad(void);", "int mh_bad(int (*cb)(int));",
+                "struct mh_bad { int a; };"):
+        with pytest.raises(_lib.MorpheusHipError, match="mh_bad"):
+            _lib.parse_header(head + bad)
+    with pytest.raises(_lib.MorpheusHipError, match="MH_ABI_VERSION"):
+        _lib.parse_header("int mh_abi_version(void);")
+    hdr = open(os.path.join(ROOT, "include", "morpheus_hip.h")).read()
+    assert hdr.count("#define MH_ABI_VERSION 9 ") == 1
+    with pytest.raises(_lib.MorpheusHipError, match=r"ABI version 9, include/morpheus_hip\.h declares 10"):
+        _lib.bind(ctypes.CDLL(_lib.SO), hdr.replace("#define MH_ABI_VERSION 9 ", "#define MH_ABI_VERSION 10 "))
+    assert set(_lib.bind(ctypes.CDLL(_lib.SO))) == set(_lib.EXPORTS)                        # a side handle gets the same table
+
+
+def test_launch_names_the_entry_point_it_called(lib, monkeypatch):
+    """_lib.launch / ops._timed append the stream, check the status and name the function they CALLED (a hand-written label had
+    drifted: mh_mlp_wgrad_b3 was reported as mh_mlp_wgrad).  Host-validated bad arguments: no device, no launch."""
+    from morpheus_amd import _lib, ops
+    monkeypatch.setattr(_lib, "_CUR_DEVICE", lambda: 0)                                      # the current stream without a device
+    monkeypatch.setattr(_lib, "_RAW_STREAM", lambda device: None)
+    assert _lib.stream() is None
+    _lib.launch("mh_composite_fwd", *([None] * 10), 0)                                      # an empty input is fine
+    with pytest.raises(_lib.MorpheusHipError, match=r"^mh_composite_fwd: invalid argument .*\(status 1\)$"):
+        _lib.launch("mh_composite_fwd", *([None] * 10), 5)
+    assert not ops.TIMER.enabled
+    with pytest.raises(_lib.MorpheusHipError, match=r"^mh_warp_fwd_b3: invalid argument"):    # the function, not the timer key
+        ops._timed("mh_warp_fwd_b3", *([None] * 8), 7, None, None, None, 128, key="mh_warp_fwd")
+    with pytest.raises(KeyError):
+        _lib.launch("mh_no_such_entry_point")
+    with pytest.raises(_lib.MorpheusHipError, match=r"^label: invalid argument"):            # the plain form tools and tests use
+        ops.check(lib.mh_composite_fwd(*([None] * 10), 5, None), "label")
+    assert ops.launch is _lib.launch and ops.stream is not None and ops.ptr(None) is None
+
+
 def test_no_cpu_fallback():
     from morpheus_amd import harness, ops
     from morpheus_amd._lib import MorpheusHipError

@@ -10,11 +10,11 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from morpheus_amd import _lib
 lib = ctypes.CDLL(os.path.join(ROOT, "morpheus_amd", "_build", "libmorpheus_trace.so"))
-P, I32, I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-lib.mh_warp_fwd.argtypes = [P] * 8 + [I32, P, P, P, I64, P]
-lib.mh_warp_acts_floats.restype = I64
-lib.mh_warp_acts_floats.argtypes = [I64]
+_lib.bind(lib)                                      # the header's signatures; mh_trace_read is a trace-only export
+lib.mh_trace_read.argtypes = [ctypes.c_void_p]
 M = 128 * 128 * 128
 dev = "cuda"
 g = torch.Generator(device=dev).manual_seed(0)
