@@ -443,6 +443,19 @@ int mh_mc_count(const float *vol, int32_t nx, int32_t ny, int32_t nz, float iso,
 int mh_mc_emit(const float *vol, int32_t nx, int32_t ny, int32_t nz, float iso, void *workspace, float *vertices,
                int32_t *triangles, void *stream);
 
+/* The masked pair, for a volume with unobserved points (TSDF fusion below): weight [nx][ny][nz] fp32, a point is observed when
+ * weight > 0 (a NaN weight is not).  A cell exists only when all eight of its corners are observed; such a cell gives the
+ * triangles the unmasked pair gives it.  A vertex exists on a crossed edge only when at least one of the (up to four) cells
+ * around the edge exists -- so both of its ends are observed -- and is written as above.  Order, winding and determinism as
+ * above; with every weight positive the masked pair returns exactly the bytes of the unmasked pair.  Same protocol:
+ * mh_mc_masked_workspace_bytes (larger: one byte per point more), mh_mc_count_masked (reads weight), mh_mc_emit_masked (same
+ * vol, iso and workspace as the mh_mc_count_masked before it). */
+int64_t mh_mc_masked_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int mh_mc_count_masked(const float *vol, const float *weight, int32_t nx, int32_t ny, int32_t nz, float iso, void *workspace,
+                       int64_t *counts, void *stream);
+int mh_mc_emit_masked(const float *vol, int32_t nx, int32_t ny, int32_t nz, float iso, void *workspace, float *vertices,
+                      int32_t *triangles, void *stream);
+
 /* ---- mesh rendering (render_all_meshes, morpheus.py:418-470: an Open3D window per frame there; csrc/raster.hip) -----------
  * A triangle rasteriser over the arrays mh_mc_emit writes: vertices [V,3] fp32 world space, triangles [T,3] int32, optional
  * colors [V,3] and normals [V,3] fp32.  Every fp32 expression below is evaluated operator by operator, round to nearest, no
@@ -569,6 +582,65 @@ int64_t mh_icp_workspace_bytes(void);
 int mh_icp_transform(const float *src, int64_t N, const double *T_host, float *out, void *stream);
 int mh_icp_sums(const float *p, int64_t N, const float *target, int64_t Nt, const int32_t *idx, const float *d2,
                 void *workspace, double *sums, void *stream);
+
+/* ---- TSDF fusion (run_tsdf_fusion / back_proj_frame, tools/vis.py:251-361 of the reference: Open3D's ScalableTSDFVolume on the
+ * host there; csrc/tsdf.hip) ----------------------------------------------------------------------------------------------------
+ * RGB-D frames are fused into a truncated signed distance volume whose zero set mh_mc_*_masked extracts.  The rules restate
+ * Open3D's UniformTSDFVolume::Integrate / ScalableTSDFVolume as documented and remembered; Open3D was not available, so
+ * agreement with it is NOT verified.  Every fp32 expression below is evaluated operator by operator, round to nearest, no FMA,
+ * in the written order (tests/tsdf_oracle.py is written from this text).
+ *   volume: an axis-aligned box at origin (ox, oy, oz) of nbx x nby x nbz blocks of 8^3 voxels, nx = 8 nbx voxels along x (ny,
+ *     nz likewise), nx*ny*nz < 2^31, voxel side voxel_length > 0.  Voxel (i, j, k) stands at p = (ox + ((float)i + 0.5f) *
+ *     voxel_length, oy + ..j.., oz + ..k..).  Dense arrays in C order (k fastest): tsdf [nx][ny][nz] fp32, weight [nx][ny][nz]
+ *     fp32 (the number of frames that updated the voxel), color [3][nx][ny][nz] fp32 in [0, 255] (three planes), active
+ *     [nbx][nby][nbz] uint8 (one byte per block, 0 or 1).  The caller zeroes all four before the first frame.
+ *   frame: depth [H][W] fp32, rgb [H][W][3] uint8, mask [H][W] uint8 or NULL, H, W in [1, 16384].  fx, fy (non-zero), cx, cy
+ *     as in mh_generate_rays and mh_raster_*: the centre of pixel (i, j) = (column, row) is at (i + 0.5, j + 0.5).  Intrinsics
+ *     that put pixel centres at integers (Open3D's) are the same kernels with cx + 0.5, cy + 0.5.
+ *   usable depth: d = depth[j][i] / depth_scale; the pixel is usable when mask is NULL or mask[j][i] != 0, and d > 0 and
+ *     d <= depth_trunc (a NaN or infinite d is not usable).  depth_scale > 0, depth_trunc > 0.
+ *   back-projection (touch, bounds): c2w_host = 12 HOST floats, row-major [3][4] = (R | t), the OpenCV camera-to-world pose.
+ *     xc = ((((float)i + 0.5f) - cx) / fx) * d, yc = ((((float)j + 0.5f) - cy) / fy) * d, zc = d;
+ *     P_r = ((c[r][0]*xc + c[r][1]*yc) + c[r][2]*zc) + c[r][3].  Sampled pixels: i and j multiples of `stride` >= 1.
+ *   touch (mh_tsdf_touch, per frame, before its integration): for every sampled usable pixel and every axis a, with
+ *     L = 8.0f * voxel_length: lo_a = floorf(((P_a - sdf_trunc) - o_a) / L), hi_a = floorf(((P_a + sdf_trunc) - o_a) / L); when
+ *     hi_a >= 0 and lo_a <= nb_a - 1 on all three axes (false for a NaN), every block in [max(lo, 0), min(hi, nb - 1)]^3 gets
+ *     active = 1.  Plain stores of the same byte: order-free.  A block that is not active when a frame is integrated does not
+ *     see that frame.
+ *   integrate (mh_tsdf_integrate, every voxel of every active block): w2c_host = 12 HOST floats, row-major [3][4], the float64
+ *     inverse of the OpenCV camera-to-world pose rounded once, as mh_raster_depth takes it.
+ *     pc_r = ((w[r][0]*px + w[r][1]*py) + w[r][2]*pz) + w[r][3]; skipped unless pc_z > 0.
+ *     u = floorf((fx*pc_x)/pc_z + cx), v = floorf((fy*pc_y)/pc_z + cy); skipped unless 0 <= u < W and 0 <= v < H (false for a
+ *     NaN); the pixel is (i, j) = (u, v); skipped unless it is usable, with depth d.
+ *     a = (((float)i + 0.5f) - cx) / fx, b = (((float)j + 0.5f) - cy) / fy, m = sqrtf((1.0f + a*a) + b*b) (the length of the
+ *     pixel's ray at z = 1);  sdf = (d - pc_z) * m; skipped unless sdf > -sdf_trunc;  q = sdf / sdf_trunc, t = q < 1 ? q : 1.
+ *     With w = weight and w1 = w + 1.0f:  tsdf = (tsdf*w + t) / w1;  color_c = (color_c*w + (float)rgb[j][i][c]) / w1 for the
+ *     three channels;  weight = w1.  One lane owns a voxel and frames are applied in the order of the calls, so a volume is the
+ *     same bytes run to run.  tsdf, weight, color and active are pinned bit for bit by the numpy restatement.
+ *   bounds (mh_tsdf_bounds): bounds = 6 DEVICE int32 {min x, y, z, max x, y, z} of the finite P of the sampled usable pixels, as
+ *     ordered bit patterns (o = bits >= 0 ? bits : bits ^ 0x7fffffff, which orders like the value), folded into what the words
+ *     hold by integer atomic minimum / maximum: the caller starts them at INT32_MAX (3) and INT32_MIN (3), may run any number
+ *     of frames into them and reads them once.  Order-free.
+ *   vertex colours (mh_tsdf_vertex_colors): vertices [V,3] in the index space of mh_mc_emit_masked over tsdf.  Per coordinate
+ *     a: f_a = floorf(x_a) (a vertex with an f_a outside [0, n_a - 1] gets colour 0), r_a = x_a - f_a.  The edge's axis is the
+ *     first a with r_a > 0 and f_a + 1 < n_a, t = r_a there; p0 = the point (f_x, f_y, f_z), p1 = p0 + e_a (p1 = p0, t = 0
+ *     without such an axis).  out_c = ((1.0f - t)*color_c[p0] + t*color_c[p1]) / 255.0f: out [V,3] fp32 in [0, 1].
+ * mh_tsdf_group_blocks: how many blocks along z one workgroup of mh_tsdf_integrate covers (host only; for tests that place box
+ * sizes on the kernel's internal boundaries).  No entry point synchronises with the host.  Bad arguments return MH_ERR_ARG
+ * before any launch; V == 0 returns MH_OK without one; a frame without a usable pixel and a box without an active block are
+ * valid and change nothing. */
+int32_t mh_tsdf_group_blocks(void);
+int mh_tsdf_bounds(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                   const float *c2w_host, float depth_scale, float depth_trunc, int32_t stride, int32_t *bounds, void *stream);
+int mh_tsdf_touch(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                  const float *c2w_host, float depth_scale, float depth_trunc, int32_t stride, float ox, float oy, float oz,
+                  float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz, uint8_t *active, void *stream);
+int mh_tsdf_integrate(const float *depth, const uint8_t *rgb, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy,
+                      float cx, float cy, const float *w2c_host, float depth_scale, float depth_trunc, float ox, float oy, float oz,
+                      float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz, const uint8_t *active, float *tsdf,
+                      float *weight, float *color, void *stream);
+int mh_tsdf_vertex_colors(const float *vertices, int64_t V, const float *color, int32_t nx, int32_t ny, int32_t nz, float *out,
+                          void *stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,33 @@ def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
     return vertices, triangles.long()
 
 
+def marching_cubes_masked(volume: torch.Tensor, weight: torch.Tensor, isovalue: float = 0.0):
+    """marching_cubes over the cells whose eight corners all have weight > 0 (mh_mc_count_masked + mh_mc_emit_masked): a cell
+    with an unobserved corner gives no triangle and owns no vertex.  weight: contiguous fp32 like volume.  With every weight
+    positive the result equals marching_cubes' bit for bit."""
+    require_gpu(volume, weight)
+    for name, a in (("volume", volume), ("weight", weight)):
+        if a.dim() != 3 or a.dtype != torch.float32 or not a.is_contiguous() or a.shape != volume.shape:
+            raise MorpheusHipError(f"marching_cubes_masked takes contiguous float32 [nx,ny,nz] volume and weight of one shape, got "
+                                   f"{name} {a.dtype} {tuple(a.shape)}")
+    lib = _lib.load()
+    nx, ny, nz = volume.shape
+    wbytes = lib.mh_mc_masked_workspace_bytes(nx, ny, nz)
+    if wbytes < 0:
+        raise MorpheusHipError(f"marching_cubes_masked: shape {tuple(volume.shape)} unsupported (each side >= 2, < 2^31 points)")
+    dev = volume.device
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    iso = float(isovalue)
+    launch("mh_mc_count_masked", ptr(volume), ptr(weight), nx, ny, nz, iso, ptr(ws), ptr(counts))
+    V, T = counts.tolist()
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
+    if V or T:
+        launch("mh_mc_emit_masked", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles))
+    return vertices, triangles.long()
+
+
 @torch.no_grad()
 def sdf_volume(model, resolution: int = 128, S: int = 128, t=None, cano: bool = False) -> torch.Tensor:
     """The query of morpheus.py:381-395: model.density on torch.linspace(-1, 1, resolution)^3 in S^3 sub-grids, each

@@ -124,6 +124,48 @@ def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optiona
     return {"depth": depth, "tri_id": tri_id, "image": image, "clipped": clipped}
 
 
+def concat_meshes(geom_list, need_colors: bool = False) -> dict:
+    """Several mesh dicts -> one (vertices, triangles, colors) on the device: each mesh's optional 4 x 4 `transform` (host,
+    float64) is applied to its vertices through mesheval.transform_points, the triangle indices are offset.  colors: None when
+    no mesh has any; a mesh without colours beside coloured ones gets the rasteriser's 0.7 grey."""
+    from .mesheval import transform_points
+    if not geom_list:
+        raise MorpheusHipError("render_mesh_from_view: geom_list is empty")
+    any_colors = need_colors and any(g.get("colors") is not None for g in geom_list)
+    verts, tris, cols, base = [], [], [], 0
+    for g in geom_list:
+        v, t = g["vertices"], g["triangles"]
+        _mesh_arrays(v, t, g.get("colors"))
+        if g.get("transform") is not None and v.shape[0]:
+            v = transform_points(v, g["transform"])
+        verts.append(v)
+        tris.append(t.to(torch.int64) + base)
+        if any_colors:
+            cols.append(g["colors"] if g.get("colors") is not None else torch.full_like(v, 0.7))
+        base += v.shape[0]
+    return {"vertices": torch.cat(verts).contiguous(), "triangles": torch.cat(tris).contiguous(),
+            "colors": torch.cat(cols).contiguous() if any_colors else None}
+
+
+VIEW_MODES = {"gray": "shaded", "color": "color", "normal": "normal"}
+
+
+def render_mesh_from_view(geom_list, c2w, K, H: int, W: int, mode: str = "gray", show_backface: bool = True,
+                          return_result: bool = False, **render_kwargs):
+    """render_mesh_from_view (tools/vis.py:216-248): the meshes of geom_list (mesh dicts, each with an optional 4 x 4
+    `transform`, visualizer.py:222) in one image from the OpenCV pose c2w.  mode: "gray" (shaded, no colours), "color" (the
+    vertex colours, unlit, as Open3D's MeshColorOption.Color), "normal".  -> image float32 [H,W,3] on the device (the
+    reference returns the host array of capture_screen_float_buffer), or render_mesh's whole result with return_result.  Back
+    faces are always drawn (show_backface is accepted for the signature's sake)."""
+    if mode not in VIEW_MODES:
+        raise MorpheusHipError(f"mode must be one of {sorted(VIEW_MODES)}, got {mode!r}")
+    scene = concat_meshes(geom_list, need_colors=(mode == "color"))
+    render_kwargs.setdefault("convention", "opencv")
+    out = render_mesh(scene["vertices"], scene["triangles"], scene["colors"], c2w=c2w, K=K, H=H, W=W, mode=VIEW_MODES[mode],
+                      **render_kwargs)
+    return out if return_result else out["image"]
+
+
 _PLY_NAME = re.compile(r"mesh_(\d+)_(\d+)\.ply$")
 
 

@@ -1,0 +1,307 @@
+"""TSDF fusion on the device: run_tsdf_fusion / back_proj_frame (tools/vis.py:251-361) without Open3D.
+
+The reference fuses the dataset's RGB-D frames into the background mesh of its visualiser (reconstruct_bg_mesh,
+visualizer.py:110-125) with Open3D's ScalableTSDFVolume on the host.  Here the frames are integrated into a dense box of
+voxels by the HIP kernels of csrc/tsdf.hip (mh_tsdf_touch + mh_tsdf_integrate per frame, no host synchronisation between
+frames), the surface comes from the masked marching cubes of csrc/mesh.hip (cells with an unobserved corner give nothing) and
+the vertex colours from mh_tsdf_vertex_colors.  Conventions: include/morpheus_hip.h (TSDF fusion).
+
+Storage is dense inside the box: 20 bytes per voxel and one byte per 8^3 block.  A box that does not fit is refused before
+anything is allocated (volume_bytes / memory_cap_bytes); a pooled block-sparse store is not part of this module.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MorpheusHipError, launch, ptr, require_gpu
+from .chunking import DEFAULT_FRACTION, available_bytes
+
+BLOCK = 8
+BYTES_PER_VOXEL = 20                 # tsdf, weight and three colour planes, fp32
+PIXEL_CENTERS = ("integer", "half")
+INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+
+
+def volume_bytes(dims: Sequence[int]) -> int:
+    """device bytes of a dense volume of dims = (nx, ny, nz) voxels: 20 per voxel + 1 per 8^3 block"""
+    n = int(dims[0]) * int(dims[1]) * int(dims[2])
+    return n * BYTES_PER_VOXEL + n // BLOCK ** 3
+
+
+def memory_cap_bytes(device=None, max_gb: Optional[float] = None) -> float:
+    """max_gb in GB when given; else the rule of chunking.py for parked bytes: min(0.4 of the device, 0.85 of what is free)"""
+    if max_gb is not None:
+        return float(max_gb) * 1e9
+    idx = torch.cuda.current_device() if device is None or getattr(device, "index", None) is None else device.index
+    total = float(torch.cuda.get_device_properties(idx).total_memory)
+    return min(DEFAULT_FRACTION * total, 0.85 * available_bytes(device))
+
+
+def check_box(origin, dims, voxel_length: float, cap_bytes: float) -> None:
+    """Raises MorpheusHipError when the dense box cannot be held: more than 2^31 - 1 voxels (the kernels' index range) or more
+    bytes than cap_bytes."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < BLOCK or any(d % BLOCK for d in (nx, ny, nz)):
+        raise MorpheusHipError(f"TSDF box: dims must be positive multiples of the block side {BLOCK}, got {(nx, ny, nz)}")
+    n, need = nx * ny * nz, volume_bytes((nx, ny, nz))
+    if n >= 2 ** 31 or need > cap_bytes:
+        lo = [float(o) for o in origin]
+        hi = [o + d * float(voxel_length) for o, d in zip(lo, (nx, ny, nz))]
+        why = "more than 2^31 - 1 voxels" if n >= 2 ** 31 else f"{need / 1e9:.2f} GB of dense storage, over the cap of {cap_bytes / 1e9:.2f} GB"
+        raise MorpheusHipError(
+            f"TSDF box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
+            f"{float(voxel_length):g} is {nx} x {ny} x {nz} = {n} voxels: {why}.  Pass a tighter box with bounds=(min, max), or a "
+            f"larger voxel_length (storage falls with its cube); max_gb= raises the cap.")
+
+
+def box_from_bounds(lo, hi, voxel_length: float, margin: float):
+    """-> (origin float64 [3], dims (nx, ny, nz)): the box [lo - margin, hi + margin] grown to whole 8^3 blocks"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise MorpheusHipError(f"TSDF bounds must be finite with max >= min, got {lo.tolist()} .. {hi.tolist()}")
+    origin = lo - margin
+    side = BLOCK * float(voxel_length)
+    blocks = np.maximum(np.ceil((hi + margin - origin) / side), 1).astype(np.int64)
+    return origin, tuple(int(b) * BLOCK for b in blocks)
+
+
+def _tensor(a, device):
+    return a.to(device) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), device=device)
+
+
+def rgb8(rgb, gray_scale: bool = False, intensity_scale: float = 1.0, alpha: float = 0.0, device=None) -> torch.Tensor:
+    """The colour preparation of run_tsdf_fusion / back_proj_frame (tools/vis.py:269-282, 325-332) -> uint8 [H,W,3] on `device`.
+    rgb: uint8 is taken as RGB8; floating point in [0, 1] is scaled by 255 and truncated (clamped to [0, 255] first).
+    gray_scale: the channel mean in all three channels.  Otherwise intensity_scale < 1: rgb * intensity_scale; otherwise
+    alpha > 0: rgb * alpha + (1 - alpha) (a blend toward white).  The input is not modified (the reference scales it in place)."""
+    t = _tensor(rgb, device)
+    if t.dim() != 3 or t.shape[-1] != 3:
+        raise MorpheusHipError(f"rgb must be [H,W,3], got {tuple(t.shape)}")
+    if t.dtype == torch.uint8:
+        if not (gray_scale or intensity_scale < 1.0 or alpha > 0.0):
+            return t.contiguous()
+        t = t.to(torch.float32) / 255.0
+    elif not t.is_floating_point():
+        raise MorpheusHipError(f"rgb must be uint8 or floating point, got {t.dtype}")
+    if gray_scale:
+        t = t.mean(dim=-1, keepdim=True).expand(-1, -1, 3)
+    elif intensity_scale < 1.0:
+        t = t * intensity_scale
+    elif alpha > 0.0:
+        t = t * alpha + (1 - alpha)
+    return (t * 255).clamp(0, 255).to(torch.uint8).contiguous()
+
+
+def mask8(mask, device=None) -> Optional[torch.Tensor]:
+    """mask [H,W] or [H,W,C] (channel 0) -> uint8 [H,W], 1 where mask > 0 (the reference zeroes depth where mask <= 0)"""
+    if mask is None:
+        return None
+    t = _tensor(mask, device)
+    if t.dim() == 3:
+        t = t[:, :, 0]
+    elif t.dim() != 2:
+        raise MorpheusHipError(f"mask must be [H,W] or [H,W,C], got {tuple(t.shape)}")
+    return (t > 0).to(torch.uint8).contiguous()
+
+
+def _intrinsics(K, pixel_centers: str):
+    if pixel_centers not in PIXEL_CENTERS:
+        raise MorpheusHipError(f"pixel_centers must be one of {PIXEL_CENTERS}, got {pixel_centers!r}")
+    K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+    fx, fy, cx, cy = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+    if pixel_centers == "integer":                                 # Open3D's convention: the same kernels, shifted principal point
+        cx, cy = cx + 0.5, cy + 0.5
+    return fx, fy, cx, cy
+
+
+def _pose(c2w):
+    """OpenCV camera-to-world [4,4] or [3,4] -> (c2w, w2c) float32 [3,4] host arrays; the inverse is taken in float64"""
+    c = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
+    if c.shape not in ((4, 4), (3, 4)):
+        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
+    m = np.eye(4, dtype=np.float64)
+    m[:3] = c[:3]
+    return np.ascontiguousarray(m[:3].astype(np.float32)), np.ascontiguousarray(np.linalg.inv(m)[:3].astype(np.float32))
+
+
+def _depth32(depth, device) -> torch.Tensor:
+    t = _tensor(depth, device)
+    if t.dim() != 2:
+        raise MorpheusHipError(f"depth must be [H,W], got {tuple(t.shape)}")
+    return t.to(torch.float32).contiguous()
+
+
+def _host_ptr(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+class TSDFVolume:
+    """A dense truncated signed distance volume on the device.  origin: world position of the box's corner; dims = (nx, ny,
+    nz) voxels, multiples of 8.  Attributes: tsdf, weight [nx,ny,nz] fp32, color [3,nx,ny,nz] fp32 in [0, 255], active
+    [nx/8,ny/8,nz/8] uint8."""
+
+    def __init__(self, voxel_length: float, sdf_trunc: float, origin, dims, device="cuda", max_gb: Optional[float] = None):
+        if not (voxel_length > 0 and sdf_trunc > 0):
+            raise MorpheusHipError(f"voxel_length and sdf_trunc must be positive, got {voxel_length}, {sdf_trunc}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise MorpheusHipError(f"TSDFVolume runs on an MI355X only (device is {device}); there is no CPU path")
+        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
+        self.origin = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
+        self.dims = tuple(int(d) for d in dims)
+        check_box(self.origin, self.dims, voxel_length, memory_cap_bytes(device, max_gb))
+        self.device = device
+        nx, ny, nz = self.dims
+        self.blocks = (nx // BLOCK, ny // BLOCK, nz // BLOCK)
+        self.tsdf = torch.zeros(nx, ny, nz, dtype=torch.float32, device=device)
+        self.weight = torch.zeros(nx, ny, nz, dtype=torch.float32, device=device)
+        self.color = torch.zeros(3, nx, ny, nz, dtype=torch.float32, device=device)
+        self.active = torch.zeros(self.blocks, dtype=torch.uint8, device=device)
+        self.frames = 0
+
+    def integrate(self, depth, color, K, c2w, mask=None, *, depth_scale: float = 1.0, depth_trunc: float = 10.0,
+                  stride: int = 4, pixel_centers: str = "half") -> None:
+        """One frame: depth [H,W], color [H,W,3] (uint8 RGB8, or floating point in [0, 1]), K [3,3], c2w the OpenCV
+        camera-to-world pose, mask [H,W] (pixels with mask <= 0 are not used).  Two launches, no host synchronisation."""
+        fx, fy, cx, cy = _intrinsics(K, pixel_centers)
+        if int(stride) < 1:
+            raise MorpheusHipError(f"stride must be >= 1, got {stride}")
+        d = _depth32(depth, self.device)
+        c = rgb8(color, device=self.device)
+        m = mask8(mask, self.device)
+        H, W = d.shape
+        if c.shape[:2] != (H, W) or (m is not None and m.shape != (H, W)):
+            raise MorpheusHipError(f"depth {tuple(d.shape)}, color {tuple(c.shape)} and mask "
+                                   f"{None if m is None else tuple(m.shape)} must share H and W")
+        require_gpu(d, c, m)
+        c2w_h, w2c_h = _pose(c2w)
+        box = (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
+        launch("mh_tsdf_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale), float(depth_trunc),
+               int(stride), *box, ptr(self.active))
+        launch("mh_tsdf_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(w2c_h), float(depth_scale),
+               float(depth_trunc), *box, ptr(self.active), ptr(self.tsdf), ptr(self.weight), ptr(self.color))
+        self.frames += 1
+
+    def vertex_colors(self, index_vertices: torch.Tensor) -> torch.Tensor:
+        """colours in [0, 1] of marching-cubes vertices given in the volume's index space"""
+        require_gpu(index_vertices)
+        V = index_vertices.shape[0]
+        out = torch.empty(V, 3, dtype=torch.float32, device=self.device)
+        launch("mh_tsdf_vertex_colors", ptr(index_vertices), V, ptr(self.color), *self.dims, ptr(out))
+        return out
+
+    def extract_mesh(self) -> dict:
+        """-> dict(vertices [V,3] fp32 world space, triangles [T,3] int64, colors [V,3] fp32 in [0, 1]): the zero set over the
+        cells whose eight corners were all observed.  One host synchronisation (to size the outputs)."""
+        from .mesh import marching_cubes_masked
+        iv, tri = marching_cubes_masked(self.tsdf, self.weight, 0.0)
+        colors = self.vertex_colors(iv)
+        origin = torch.from_numpy(self.origin).to(self.device)
+        vertices = origin + (iv + 0.5) * self.voxel_length
+        return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+
+
+def frame_bounds(K, c2w_list, depth_list, mask_list=None, *, depth_scale=1.0, depth_trunc=10.0, stride=4,
+                 pixel_centers="integer", device="cuda"):
+    """-> (min float32 [3], max float32 [3]) of the usable back-projected pixels of all frames, or None without one.  One
+    launch per frame and ONE host read for the sequence."""
+    fx, fy, cx, cy = _intrinsics(K, pixel_centers)
+    device = torch.device(device)
+    acc = torch.tensor([INT32_MAX] * 3 + [INT32_MIN] * 3, dtype=torch.int32, device=device)
+    for f, (c2w, depth) in enumerate(zip(c2w_list, depth_list)):
+        d = _depth32(depth, device)
+        m = mask8(None if mask_list is None else mask_list[f], device)
+        require_gpu(d, m)
+        c2w_h, _ = _pose(c2w)
+        launch("mh_tsdf_bounds", ptr(d), ptr(m), d.shape[0], d.shape[1], fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+               float(depth_trunc), int(stride), ptr(acc))
+    return decode_bounds(acc.cpu().numpy())
+
+
+def decode_bounds(words: np.ndarray):
+    """the six ordered int32 words of mh_tsdf_bounds -> (min [3], max [3]) float32, or None when no pixel was usable"""
+    words = np.asarray(words, np.int32)
+    if words[0] == INT32_MAX:
+        return None
+    bits = np.where(words >= 0, words, words ^ np.int32(0x7fffffff)).astype(np.int32)
+    vals = bits.view(np.float32)
+    return vals[:3].copy(), vals[3:].copy()
+
+
+def _empty_mesh(device):
+    return {"vertices": torch.zeros(0, 3, dtype=torch.float32, device=device),
+            "triangles": torch.zeros(0, 3, dtype=torch.int64, device=device),
+            "colors": torch.zeros(0, 3, dtype=torch.float32, device=device)}
+
+
+def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, skip=None, save_path=None, depth_scale=1.0,
+                    depth_trunc=10.0, sdf_trunc=0.04, voxel_length=0.02, gray_scale=False, *, bounds=None,
+                    pixel_centers: str = "integer", stride: int = 4, max_gb: Optional[float] = None, device="cuda",
+                    intensity_scale: float = 1.0, alpha: float = 0.0, return_volume: bool = False):
+    """run_tsdf_fusion (tools/vis.py:315-361) on the device -> dict(vertices, triangles, colors), what meshrender, mesheval and
+    mesh.write_ply take; written as a PLY to save_path when that is given.
+    K [3,3]; c2w_list: OpenCV camera-to-world poses; depth_list [H,W]; rgb_list [H,W,3] in [0, 1] (or uint8); mask_list [H,W] or
+    [H,W,C]: numpy arrays or tensors, none of them modified (the reference scales rgb and zeroes depth in place).  `skip` is
+    accepted and ignored, as in the reference.  pixel_centers: "integer" reads K as Open3D does (pixel centres at integers),
+    "half" as the rest of this library does.  bounds = (min [3], max [3]) fixes the box (grown by sdf_trunc and to whole
+    blocks); without it the box is sized from the frames' own back-projected pixels (one more launch per frame and one host
+    read).  A box over max_gb (default: min(0.4 of the device, 0.85 of what is free)) is refused before anything is allocated.
+    No host synchronisation inside the frame loop."""
+    n = len(c2w_list)
+    if len(depth_list) != n or len(rgb_list) != n or (mask_list is not None and len(mask_list) != n):
+        raise MorpheusHipError(f"run_tsdf_fusion: {n} poses, {len(depth_list)} depth maps, {len(rgb_list)} images"
+                               + ("" if mask_list is None else f", {len(mask_list)} masks"))
+    if not (voxel_length > 0 and sdf_trunc > 0 and depth_scale > 0 and depth_trunc > 0) or int(stride) < 1:
+        raise MorpheusHipError("run_tsdf_fusion: voxel_length, sdf_trunc, depth_scale and depth_trunc must be positive, stride >= 1")
+    _intrinsics(K, pixel_centers)
+    H, W = int(H), int(W)
+    for f in range(n):
+        if tuple(depth_list[f].shape) != (H, W):
+            raise MorpheusHipError(f"run_tsdf_fusion: depth {f} is {tuple(depth_list[f].shape)}, expected {(H, W)}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise MorpheusHipError(f"run_tsdf_fusion runs on an MI355X only (device is {device}); there is no CPU path")
+    if bounds is None:
+        found = frame_bounds(K, c2w_list, depth_list, mask_list, depth_scale=depth_scale, depth_trunc=depth_trunc, stride=stride,
+                             pixel_centers=pixel_centers, device=device) if n else None
+        if found is None:                                          # no frame, or no usable pixel: an empty mesh
+            mesh = _empty_mesh(device)
+            if save_path is not None:
+                _save(save_path, mesh)
+            return (mesh, None) if return_volume else mesh
+        bounds = found
+    origin, dims = box_from_bounds(bounds[0], bounds[1], voxel_length, sdf_trunc)
+    vol = TSDFVolume(voxel_length, sdf_trunc, origin, dims, device=device, max_gb=max_gb)
+    for f in range(n):
+        c = rgb8(rgb_list[f], gray_scale, intensity_scale, alpha, device=device)
+        vol.integrate(depth_list[f], c, K, c2w_list[f], None if mask_list is None else mask_list[f], depth_scale=depth_scale,
+                      depth_trunc=depth_trunc, stride=stride, pixel_centers=pixel_centers)
+    mesh = vol.extract_mesh()
+    if save_path is not None:
+        _save(save_path, mesh)
+    return (mesh, vol) if return_volume else mesh
+
+
+def back_proj_frame(K, H, W, c2w, depth, rgb, save_path=None, mask=None, depth_scale=1.0, depth_trunc=10.0, sdf_trunc=0.04,
+                    voxel_length=0.02, gray_scale=False, intensity_scale=1.0, alpha=0.0, **kwargs):
+    """back_proj_frame (tools/vis.py:251-312): run_tsdf_fusion of one frame, with its colour options (gray_scale, else
+    intensity_scale < 1, else alpha > 0).  The point-cloud form (save_as_pcd) is not provided."""
+    if kwargs.pop("save_as_pcd", False):
+        raise MorpheusHipError("back_proj_frame: save_as_pcd (Open3D's extract_point_cloud) is not provided")
+    return run_tsdf_fusion(K, H, W, [c2w], [depth], [rgb], None if mask is None else [mask], save_path=save_path,
+                           depth_scale=depth_scale, depth_trunc=depth_trunc, sdf_trunc=sdf_trunc, voxel_length=voxel_length,
+                           gray_scale=gray_scale, intensity_scale=intensity_scale, alpha=alpha, **kwargs)
+
+
+def _save(path, mesh) -> None:
+    from .mesh import write_ply
+    d = os.path.dirname(os.fspath(path))
+    if d:
+        os.makedirs(d, exist_ok=True)
+    write_ply(path, mesh["vertices"], mesh["triangles"], mesh["colors"])
