@@ -157,6 +157,43 @@ int mh_march_slots(const float *rays_o, const float *rays_d, const float *jitter
 int mh_march_pack(const int32_t *ray_start, const int32_t *ray_cnt, const float *slot_ts, const float *slot_te, int32_t N,
                   int32_t cap, int32_t *ray_idx, float *t_starts, float *t_ends, void *stream);
 
+/* ---- visibility pruning of packed samples (csrc/visibility.hip) --------------------------------------------------------
+ * What nerfacc's OccGridEstimator.sampling does with sigma_fn / alpha_fn, alpha_thre and early_stop_eps
+ * (render_visibility_from_density / render_visibility_from_alpha of nerfacc 0.5.x).  nerfacc is third-party, un-vendored and
+ * not installed where this library is built: the rules below are restated as recalled and are NOT verified against it
+ * (tools/check_against_nerfacc.py prints the difference of the kept sets on a machine that has it).
+ * Input: the marcher's packed samples -- samples of ray r are [ray_start[r], ray_start[r] + ray_cnt[r]) of the packed arrays
+ * of length M, contiguous and ordered by t -- and one value per sample.  Per sample i of a ray, D = t_ends - t_starts:
+ *   sigma form (alpha_form = 0): x_i = max(sigma_i * D_i, 0); a NaN x_i drops the sample and adds 0 to the sum;
+ *                                alpha_i = -expm1f(-x_i);  T_i = expf(-sum_{j<i} x_j)  (an exclusive sum along the ray).
+ *   alpha form (alpha_form = 1): alpha_i = values_i clamped to [0, 1], a NaN drops the sample and adds 0;
+ *                                T_i = prod_{j<i} (1 - alpha_j), carried as the sum of x_j = -log1pf(-alpha_j)
+ *                                (t_starts / t_ends are not read and may be NULL).
+ *   keep_i = (T_i >= early_stop_eps) && (alpha_i >= *alpha_thre)          (alpha_thre NULL: 0; 0 <= early_stop_eps <= 1)
+ * alpha_thre is a DEVICE scalar: the caller forms min(alpha_thre, mean(occs)) -- the rule nerfacc applies when a sigma_fn or
+ * alpha_fn is given -- on the device and no host read is needed.
+ * The clamp x >= 0 makes T non-increasing along a ray.  That is what lets a wavefront stop reading a ray once the running
+ * sum alone gives T < early_stop_eps: every later sample of that ray is dropped, and its keep bytes are still written (0).
+ * mh_visibility_mask: one wavefront per ray, 64-sample chunks with a carry (the compositor's scan); writes keep [M] uint8 for
+ * every sample a ray owns and kept_cnt [N] int32.  Ranges are clipped to [0, M).
+ * mh_visibility_pack: new_start [N] = the exclusive scan of kept_cnt (the caller's, as for mh_march_pack); copies the kept
+ * samples of ray r, in order, to [new_start[r], new_start[r] + kept_cnt[r]) of out_ray_idx / out_t_starts / out_t_ends
+ * [M_out] and writes src_index [M_out] int32 = the packed position each kept sample had before.  The pruned set's ray_start /
+ * ray_cnt are new_start / kept_cnt.  Writes beyond M_out are suppressed.
+ * Two forms of the same entry points, as for the marcher:
+ *   ragged:          M_out = sum(kept_cnt), read by the host once;
+ *   fixed capacity:  M and M_out are the marcher's capacity, the entries no ray owns are padding the kernels never visit
+ *                    (the caller zeroes keep and the outputs: ray 0, t = 0, src_index 0, the marcher's padding convention),
+ *                    n_valid = sum(kept_cnt) stays on the device, no host synchronisation.  The kept set is a subset of the
+ *                    marched one, so it fits wherever the marched one did.
+ * Bad arguments give MH_ERR_ARG before any launch; N == 0 or M == 0 (or M_out == 0) give MH_OK without one. */
+int mh_visibility_mask(const float *values, int32_t alpha_form, const float *t_starts, const float *t_ends,
+                       const int32_t *ray_start, const int32_t *ray_cnt, int32_t N, int64_t M, float early_stop_eps,
+                       const float *alpha_thre, uint8_t *keep, int32_t *kept_cnt, void *stream);
+int mh_visibility_pack(const uint8_t *keep, const float *t_starts, const float *t_ends, const int32_t *ray_start,
+                       const int32_t *ray_cnt, const int32_t *new_start, int32_t N, int64_t M, int64_t M_out,
+                       int32_t *out_ray_idx, float *out_t_starts, float *out_t_ends, int32_t *src_index, void *stream);
+
 /* ---- glue of the field queries as single launches (csrc/normal.hip) ----------------------------------------------------
  * Finite-difference normals (models/model.py:367-398): mh_fd_taps writes the 6 clamped taps of every sample, point-major
  * (+x,-x,+y,-y,+z,-z; taps [6M,3]) and replicates topo [M,topo_dim] to topo6 [6M,topo_dim] (topo NULL: skipped);

@@ -600,7 +600,8 @@ class scene_representation(nn.Module):
         h = torch.cat([_freq_encode_torch(d, 6, None), _freq_encode_torch(t, 6, self.max_level)], -1)
         return torch.sigmoid(self.bg_net(h))
 
-    def density(self, x, t=None, cano=False, allow_shape=False, return_color=True):
+    def density(self, x, t=None, cano=False, allow_shape=False, return_color=True, *, frame_slots=None):
+        """`frame_slots`: see `_slots` (the renderer's per-row frame slots; None: derived from `t` as before)."""
         topo = app_code = None
         if not (cano or t is None):
             # a single time for all points travels as an expanded scalar: `_slots` sees one frame, no per-sample work
@@ -610,7 +611,7 @@ class scene_representation(nn.Module):
                 if not allow_shape:
                     raise Exception("Shape inconsistent!!!")
                 t = t.reshape(-1)[:1].view(1, 1).expand(x.shape[0], 1)
-            deform, topo, app_code = self.warp(x, t)
+            deform, topo, app_code = self.warp(x, t, frame_slots)
             x = x + deform
         sdf, sigma, albedo = self.get_sigma_albedo(x, topo=topo, app_code=app_code, return_color=return_color)
         return {"sdf": sdf, "sigma": sigma, "albedo": albedo}

@@ -9,8 +9,10 @@ here follow its published 0.5.x behaviour as summarised in SURVEY.md C.9 and are
     uniformly at random plus a quarter of the occupied ones), occs = max(occs*decay, new),
     binaries = occs > min(mean(occs), occ_thre);
   * sampling(...): fixed-step marching of the occupied cells with one stratified near-plane jitter per ray
-    (csrc/sampler.hip:march_kernel); sigma_fn / alpha_thre / early_stop_eps pruning is not applied (the reference
-    passes sigma_fn=None, alpha_thre=0, early_stop_eps=0).
+    (csrc/sampler.hip:march_wave_kernel).  With a sigma_fn or alpha_fn the marched samples are then pruned by visibility
+    (csrc/visibility.hip: T >= early_stop_eps and alpha >= min(alpha_thre, mean(occs)), include/morpheus_hip.h; recalled
+    from nerfacc 0.5.x, NOT verified).  The reference passes sigma_fn=None, alpha_thre=0, early_stop_eps=0: no pruning,
+    the marcher's samples as they are.  Cone marching (cone_angle != 0) is not implemented.
 The heavy part of an update is occ_eval_fn = model.density on up to resolution^3 points, which runs on the HIP kernels.
 """
 from __future__ import annotations
@@ -20,6 +22,17 @@ from typing import Callable, Optional
 import torch
 
 from . import ops
+
+
+def check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps):
+    """the argument rules of visibility pruning shared by every sampler with nerfacc's `.sampling` call shape"""
+    if sigma_fn is not None and alpha_fn is not None:
+        raise ValueError("sampling: give sigma_fn or alpha_fn, not both")
+    if sigma_fn is None and alpha_fn is None and (alpha_thre > 0 or early_stop_eps > 0):
+        raise ValueError("sampling: alpha_thre / early_stop_eps prune by visibility and a density function is required "
+                         "(sigma_fn or alpha_fn); nerfacc silently ignores the thresholds without one")
+    if not (0.0 <= alpha_thre <= 1.0) or not (0.0 <= early_stop_eps <= 1.0):
+        raise ValueError(f"sampling: alpha_thre ({alpha_thre}) and early_stop_eps ({early_stop_eps}) lie in [0, 1]")
 
 
 class OccupancyGrid(torch.nn.Module):
@@ -41,6 +54,7 @@ class OccupancyGrid(torch.nn.Module):
         self.register_buffer("binaries", torch.zeros(1, R, R, R, dtype=torch.bool))
         self._R = R
         self.packed = None       # (ray_start, ray_cnt) of the last sampling() call, consumed by the compositor
+        self.src_index = None    # pruned sampling: the marched position of every returned sample (None: nothing was pruned)
         self.fixed_jitter: Optional[torch.Tensor] = None   # parity runs pin the per-ray jitter
         # Fixed-capacity sampling (None = off: ragged packed samples sized by one device->host sync, as nerfacc does).
         # With a capacity the packed arrays always have that length, the first `n_valid` (a device int) entries are the
@@ -54,10 +68,17 @@ class OccupancyGrid(torch.nn.Module):
     # -- sampling --------------------------------------------------------------------------------
     @torch.no_grad()
     def sampling(self, rays_o, rays_d, sigma_fn=None, render_step_size=1e-3, alpha_thre=0.0, stratified=False,
-                 cone_angle=0.0, early_stop_eps=0.0):
-        if sigma_fn is not None or alpha_thre > 0 or early_stop_eps > 0 or cone_angle != 0.0:
-            raise NotImplementedError("density-based pruning / cone marching are not used by the reference's call "
-                                      "(morpheus.py:629-638) and are not implemented")
+                 cone_angle=0.0, early_stop_eps=0.0, alpha_fn=None):
+        """nerfacc's OccGridEstimator.sampling -> (ray_indices, t_starts, t_ends); `self.packed` = (ray_start, ray_cnt) of what
+        is returned.  sigma_fn / alpha_fn: called as fn(t_starts, t_ends, ray_indices) -> [M] densities / opacities of the
+        marched samples (not called when there is none); the samples with transmittance under early_stop_eps or opacity under
+        min(alpha_thre, mean(occs)) are dropped (ops.visibility_prune), `self.src_index` then holds the marched position of
+        every returned sample.  The defaults are the reference's call (no pruning); nerfacc's own default early_stop_eps is 1e-4.
+        nerfacc silently ignores alpha_thre / early_stop_eps when neither function is given; here that is a ValueError."""
+        if cone_angle != 0.0:
+            raise NotImplementedError("cone marching (cone_angle != 0) is not used by the reference's call "
+                                      "(morpheus.py:629-638) and is not implemented")
+        check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps)
         n = rays_o.shape[0]
         if isinstance(self.fixed_jitter, float):
             u = torch.full((n,), self.fixed_jitter, device=rays_o.device)     # one value for every ray (chunk-invariant)
@@ -78,7 +99,17 @@ class OccupancyGrid(torch.nn.Module):
         else:
             ri, ts, te, rs, rc = ops.march_rays(rays_o, rays_d, u, float(render_step_size), self.bound, binary)
             self.n_valid = None
-        self.packed = (rs, rc)
+        self.packed, self.src_index = (rs, rc), None
+        fn = sigma_fn if sigma_fn is not None else alpha_fn
+        if fn is not None and ts.shape[0] > 0:
+            # nerfacc's rule: the opacity threshold never exceeds the grid's mean occupancy value; formed on the device
+            thre = torch.clamp(self.occs.mean(), max=float(alpha_thre)) if alpha_thre > 0 else None
+            out = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps), thre, alpha_form=sigma_fn is None,
+                                       padded=self.sample_capacity is not None)
+            ri, ts, te, rs, rc, self.src_index = out[:6]
+            if self.sample_capacity is not None:
+                self.n_valid = out[6]
+            self.packed = (rs, rc)
         return ri, ts, te
 
     # -- occupancy update -------------------------------------------------------------------------

@@ -504,6 +504,68 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     return ri, ts, te, start, cnt_c, n_valid, overflow
 
 
+# ------------------------------------------------------------------------------------ visibility pruning (csrc/visibility.hip)
+def visibility_mask(values, t_starts, t_ends, ray_start, ray_cnt, early_stop_eps: float = 0.0, alpha_thre=None,
+                    alpha_form: bool = False, padded: bool = False):
+    """-> keep uint8 [M], kept_cnt int32 [N] (mh_visibility_mask, include/morpheus_hip.h).  values: sigma [M] (alpha_form: the
+    opacities themselves); alpha_thre: None, a float, or a float32 DEVICE scalar (no host read).  padded: the packed arrays are
+    longer than the rays' samples (fixed-capacity sampling); the entries no ray owns read as keep = 0."""
+    require_gpu(values, t_starts, t_ends, ray_start, ray_cnt)
+    v = values.detach().reshape(-1).float().contiguous()
+    ts, te = t_starts.contiguous(), t_ends.contiguous()
+    rs, rc = ray_start.contiguous(), ray_cnt.contiguous()
+    M, N, dev = ts.shape[0], rs.shape[0], ts.device
+    if v.shape[0] != M or te.shape[0] != M or rc.shape[0] != N or rs.dtype != torch.int32 or rc.dtype != torch.int32:
+        raise ValueError(f"visibility_mask: one value per packed sample ({M}) and int32 ray_start / ray_cnt of one length, got "
+                         f"{tuple(values.shape)}, {rs.dtype} [{N}], {rc.dtype} [{rc.shape[0]}]")
+    if alpha_thre is not None and not torch.is_tensor(alpha_thre):
+        alpha_thre = torch.full((), float(alpha_thre), device=dev) if float(alpha_thre) > 0 else None
+    if alpha_thre is not None:
+        require_gpu(alpha_thre)
+        alpha_thre = alpha_thre.detach().reshape(()).float().contiguous()
+    keep = torch.zeros(M, dtype=torch.uint8, device=dev) if padded else torch.empty(M, dtype=torch.uint8, device=dev)
+    kept = torch.zeros(N, dtype=torch.int32, device=dev)
+    _timed("mh_visibility_mask", ptr(v), 1 if alpha_form else 0, ptr(ts), ptr(te), ptr(rs), ptr(rc), N, M, float(early_stop_eps),
+           ptr(alpha_thre), ptr(keep), ptr(kept))
+    return keep, kept
+
+
+def visibility_pack(keep, kept_cnt, t_starts, t_ends, ray_start, ray_cnt, padded: bool = False):
+    """Order-preserving compaction of the packed samples by `keep` (mh_visibility_pack) -> (ray_idx int32 [M'], t_starts [M'],
+    t_ends [M'], ray_start [N], ray_cnt [N], src_index int32 [M']) -- src_index: the packed position each kept sample had, for
+    gathering what was computed on the unpruned set.  Ragged (padded=False): M' = the kept total, ONE device->host read, where
+    the marcher has one too.  padded=True: M' = M (the marcher's capacity), a seventh result n_valid (int32 0-dim, device)
+    counts the kept samples, the rest is the marcher's padding (ray 0, t = 0) that no ray owns; no host synchronisation."""
+    require_gpu(keep, kept_cnt, t_starts, t_ends, ray_start, ray_cnt)
+    ts, te = t_starts.contiguous(), t_ends.contiguous()
+    rs, rc, kc = ray_start.contiguous(), ray_cnt.contiguous(), kept_cnt.contiguous()
+    M, N, dev = ts.shape[0], rs.shape[0], ts.device
+    if keep.dtype != torch.uint8 or keep.shape != (M,) or kc.shape != (N,) or kc.dtype != torch.int32:
+        raise ValueError("visibility_pack: keep uint8 [M] and kept_cnt int32 [N] of visibility_mask expected")
+    keep = keep.contiguous()
+    new = lambda n, dt: torch.zeros(n, dtype=dt, device=dev) if padded else torch.empty(n, dtype=dt, device=dev)
+    if N == 0 or M == 0:
+        out = (new(M, torch.int32), new(M, torch.float32), new(M, torch.float32), kc.clone(), kc.clone(), new(M, torch.int32))
+        return out + (torch.zeros((), dtype=torch.int32, device=dev),) if padded else out
+    csum = torch.cumsum(kc, 0, dtype=torch.int32)
+    start = (csum - kc).contiguous()
+    M_out = M if padded else int(csum[N - 1])                           # ragged: the one device->host sync
+    ri, src = new(M_out, torch.int32), new(M_out, torch.int32)
+    ots, ote = new(M_out, torch.float32), new(M_out, torch.float32)
+    _timed("mh_visibility_pack", ptr(keep), ptr(ts), ptr(te), ptr(rs), ptr(rc), ptr(start), N, M, M_out, ptr(ri), ptr(ots), ptr(ote),
+           ptr(src))
+    out = (ri, ots, ote, start, kc, src)
+    return out + (csum[N - 1],) if padded else out
+
+
+def visibility_prune(values, t_starts, t_ends, ray_start, ray_cnt, early_stop_eps: float = 0.0, alpha_thre=None,
+                     alpha_form: bool = False, padded: bool = False):
+    """visibility_mask + visibility_pack: the packed samples a density (alpha_form: opacity) pass leaves visible
+    -> (ray_idx, t_starts, t_ends, ray_start, ray_cnt, src_index[, n_valid])."""
+    keep, kept = visibility_mask(values, t_starts, t_ends, ray_start, ray_cnt, early_stop_eps, alpha_thre, alpha_form, padded)
+    return visibility_pack(keep, kept, t_starts, t_ends, ray_start, ray_cnt, padded)
+
+
 # ------------------------------------------------------------------------------------ field-query glue (csrc/normal.hip)
 class _FdTaps(torch.autograd.Function):
     @staticmethod
@@ -668,6 +730,20 @@ def sample_positions(rays_o, rays_d, ray_idx, t_starts, t_ends, ray_start, ray_c
     backward is a per-ray segment sum (no sort, no atomics).  ray_idx int32 [M]; ray_start / ray_cnt int32 [N]."""
     return _SamplePositions.apply(rays_o, rays_d, ray_idx.contiguous(), t_starts.contiguous(), t_ends.contiguous(),
                                   ray_start.contiguous(), ray_cnt.contiguous())
+
+
+def sample_positions_nograd(rays_o, rays_d, ray_idx, t_starts, t_ends):
+    """sample_positions' forward alone (mh_sample_positions), for passes that carry no gradient and know no segment table: the
+    density pass of a pruned render is handed nerfacc's (t_starts, t_ends, ray_indices) only."""
+    require_gpu(rays_o, rays_d, ray_idx, t_starts, t_ends)
+    o, d = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
+    ri, ts, te = ray_idx.contiguous(), t_starts.contiguous(), t_ends.contiguous()
+    if ri.dtype != torch.int32:
+        ri = ri.to(torch.int32)
+    M = ts.shape[0]
+    xyz = torch.empty(M, 3, device=o.device)
+    launch("mh_sample_positions", ptr(o), ptr(d), ptr(ri), ptr(ts), ptr(te), M, ptr(xyz))
+    return xyz
 
 
 # ------------------------------------------------------------------------------------ fused MLPs

@@ -20,6 +20,7 @@ import torch
 
 from . import chunking, ops
 from .model import safe_normalize, scene_representation
+from .occgrid import check_prune_args
 
 
 class UniformSampler:
@@ -29,10 +30,16 @@ class UniformSampler:
     def __init__(self, n_samples: int, bound: float, jitter: Optional[torch.Tensor] = None):
         self.n_samples, self.bound, self.jitter = n_samples, float(bound), jitter
         self.packed = None
+        self.src_index = None    # pruned sampling: the position every returned sample had before (None: nothing was pruned)
         self.xyz = None      # sample positions o + d (ts+te)/2 of the last call (same arithmetic as morpheus.py:647)
 
     def sampling(self, rays_o, rays_d, sigma_fn=None, render_step_size=None, alpha_thre=0, stratified=True,
-                 cone_angle=0.0, early_stop_eps=0):
+                 cone_angle=0.0, early_stop_eps=0, alpha_fn=None):
+        """With a sigma_fn / alpha_fn the samples are pruned by visibility as occgrid.OccupancyGrid.sampling prunes them (there
+        is no occupancy field here: alpha_thre is taken as given)."""
+        if cone_angle != 0.0:
+            raise NotImplementedError("cone marching (cone_angle != 0) is not implemented")
+        check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps)
         n = rays_o.shape[0]
         if self.jitter is not None:
             u = self.jitter
@@ -41,7 +48,12 @@ class UniformSampler:
         else:
             u = torch.full((n,), 0.5, device=rays_o.device)
         ri, ts, te, xyz, rs, rc = ops.sample_uniform(rays_o, rays_d, u, self.n_samples, self.bound, with_xyz=True)
-        self.packed, self.xyz = (rs, rc), xyz
+        self.packed, self.xyz, self.src_index = (rs, rc), xyz, None
+        fn = sigma_fn if sigma_fn is not None else alpha_fn
+        if fn is not None and ts.shape[0] > 0:
+            ri, ts, te, rs, rc, self.src_index = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps),
+                                                                      float(alpha_thre), alpha_form=sigma_fn is None)
+            self.packed, self.xyz = (rs, rc), xyz.index_select(0, self.src_index.long())
         return ri, ts, te
 
 
@@ -63,6 +75,10 @@ class HotPathRenderer:
         # frame_batched: each row of the [B, N, .] ray tensors is ONE frame (how the reference's dataset
         # builds every batch) -> per-frame deform-code bias without a host sync.
         self.frame_batched = frame_batched
+        # Opt-in visibility pruning: None (off, the reference's call), or dict(alpha_thre=..., early_stop_eps=...).  When set,
+        # render_rays (and so eval_step) hands the sampler a sigma_fn of its own -- a density-only pass of the model under no_grad
+        # -- and queries, composites and differentiates the samples that pass leaves visible only (_density_fn).
+        self.prune: Optional[dict] = None
 
     # -- helpers of morpheus.py:518-556
     def _const(self, key, build, device):
@@ -143,6 +159,36 @@ class HotPathRenderer:
             pred_depth.append(out["depth"])
         return torch.cat(pred_rgb, dim=1).reshape(B, H, W, 3), torch.cat(pred_depth, dim=1).reshape(B, H, W)
 
+    def _density_fn(self, rays_o, rays_d, rays_t, cano, single_frame, ray_slots=None):
+        """the sigma_fn of a pruned render (self.prune): density of the marched samples without colour, normals or autograd --
+        the warp nets and the sdf net.  Runs inside the step's operand scope (an evaluation render prepares its weight operands
+        once for this pass and the main one) and in row chunks when the call is large (chunking.rows_under_cap of a warp + one
+        field query per row: nothing is parked without autograd, the chunks bound the pass's transient buffers the same way).
+        ray_slots = (t_rows [B], slot per ray [N]) for a batch of several frames, as the main pass has them."""
+        model = self.model
+        o, d = rays_o.detach(), rays_d.detach()
+
+        def sigma_fn(t_starts, t_ends, ray_indices):
+            with torch.no_grad():
+                x = ops.sample_positions_nograd(o, d, ray_indices, t_starts, t_ends)
+                M = x.shape[0]
+                slot = None
+                if single_frame:       # a batch row is one frame: a single row travels as an expanded scalar, as in the main pass
+                    t = rays_t[:1].expand(M, 1)
+                elif ray_slots is not None:
+                    t, slot = rays_t[ray_indices.long()], ray_slots[1][ray_indices.long()].contiguous()
+                else:
+                    t = rays_t[ray_indices.long()]
+                rows = chunking.rows_under_cap(chunking.query_bytes_per_row(not cano, 1), device=x.device, rows=M)
+                out = []
+                for a_ in range(0, M, rows):
+                    fs = None if slot is None else (ray_slots[0], slot[a_:a_ + rows])
+                    out.append(model.density(x[a_:a_ + rows], t=t[a_:a_ + rows], cano=cano, return_color=False,
+                                             frame_slots=fs)["sigma"].reshape(-1))
+                return out[0] if len(out) == 1 else torch.cat(out)
+
+        return sigma_fn
+
     # -- the hot path
     def render_rays(self, rays_o, rays_d, rays_t, rays_id, H, W, perturb=True, bg_color=None, ambient_ratio=1.0,
                     light_d=None, shading="albedo", real_view=True, cano=False, rays_depth=None, rays_mask=None,
@@ -169,10 +215,24 @@ class HotPathRenderer:
         N = rays_o.shape[0]
         results = {}
 
+        single_frame = (not cano) and self.frame_batched and len(prefix) == 2 and prefix[0] == 1
         with torch.no_grad():
-            ray_indices, t_starts_, t_ends_ = self.occupancy_grid.sampling(
-                rays_o, rays_d, sigma_fn=None, render_step_size=cfg["render"]["step_size"], alpha_thre=0,
-                stratified=True, cone_angle=0.0, early_stop_eps=0)
+            if self.prune:
+                unknown = set(self.prune) - {"alpha_thre", "early_stop_eps"}
+                if unknown:
+                    raise ValueError(f"HotPathRenderer.prune: unknown keys {sorted(unknown)} (alpha_thre, early_stop_eps)")
+                pre_slots = None
+                if not single_frame and not cano and self.frame_batched and len(prefix) == 2:      # one slot per batch row
+                    pre_slots = (rays_t.view(*prefix)[:, 0].contiguous(),
+                                 torch.arange(prefix[0], device=rays_o.device, dtype=torch.int32).repeat_interleave(prefix[1]))
+                ray_indices, t_starts_, t_ends_ = self.occupancy_grid.sampling(
+                    rays_o, rays_d, sigma_fn=self._density_fn(rays_o, rays_d, rays_t, cano, single_frame, pre_slots),
+                    render_step_size=cfg["render"]["step_size"], alpha_thre=float(self.prune.get("alpha_thre", 0.0)),
+                    stratified=True, cone_angle=0.0, early_stop_eps=float(self.prune.get("early_stop_eps", 0.0)))
+            else:
+                ray_indices, t_starts_, t_ends_ = self.occupancy_grid.sampling(
+                    rays_o, rays_d, sigma_fn=None, render_step_size=cfg["render"]["step_size"], alpha_thre=0,
+                    stratified=True, cone_angle=0.0, early_stop_eps=0)
         # per-sample light directions are only read by the shaded modes (model.py:515-531), and not at ambient_ratio = 1
         # (real-view steps), where the lambertian factor is exactly 1
         lit = shading != "albedo" and (ambient_ratio != 1 or shading in ("textureless", "normal"))
@@ -188,7 +248,6 @@ class HotPathRenderer:
             entries excluded: one launch each way"""
             return ops.masked_mean("absdiff", a, b, n_valid=n_valid)
 
-        single_frame = (not cano) and self.frame_batched and len(prefix) == 2 and prefix[0] == 1
         ray_idx32 = ray_indices
         _long = []
 

@@ -20,6 +20,9 @@ sites and prints the differences:
   3. the estimator's state_dict keys / shapes / dtypes against `OccupancyGrid.state_dict()` (checkpoint entry 'estimator',
      morpheus.py:341,355).
 
+  4. visibility pruning -- `sampling(sigma_fn=..., alpha_thre=..., early_stop_eps=...)` with one closed-form density through
+     both: the difference of the kept sets (csrc/visibility.hip restates nerfacc's rule from recall).
+
 It cannot run in the build container (no nerfacc, no GPU); tests/test_host.py only checks that it imports and fails with its own
 message there.
 """
@@ -119,6 +122,26 @@ def main(argv=None) -> int:
         print(f"state_dict: {k:12s} nerfacc {None if a is None else (tuple(a.shape), a.dtype)}  this build "
               f"{None if b is None else (tuple(b.shape), b.dtype)}  {'ok' if same else 'DIFFERS'}")
         ok &= same
+
+    # ---- 4. visibility pruning: the same closed-form density through both `sampling(sigma_fn=...)` (include/morpheus_hip.h,
+    # "visibility pruning": T >= early_stop_eps and alpha >= min(alpha_thre, mean(occs)), recalled -- this case pins it)
+    def sigma_fn(t_starts, t_ends, ray_indices):
+        xm = o[ray_indices.long()] + d[ray_indices.long()] * (0.5 * (t_starts + t_ends))[:, None]
+        return 40.0 * torch.exp(-8.0 * (xm.norm(dim=-1) - 0.55).abs())
+
+    grid.occs.copy_(binary.reshape(-1).float())
+    for a_thre, eps in ((0.0, 1e-4), (1e-2, 0.0), (1e-2, 1e-4)):
+        ri_p, ts_p, _ = est.sampling(o, d, sigma_fn=sigma_fn, render_step_size=args.step, alpha_thre=a_thre, stratified=False,
+                                     cone_angle=0.0, early_stop_eps=eps)
+        ri_q, ts_q, _ = grid.sampling(o, d, sigma_fn=sigma_fn, render_step_size=args.step, alpha_thre=a_thre, stratified=False,
+                                      cone_angle=0.0, early_stop_eps=eps)
+        # a sample is (ray, position in the un-pruned lattice): the un-pruned sets of case 1 agree, so compare by (ray, t_start)
+        key = lambda ri, ts: set(zip(ri.tolist(), [round(v, 5) for v in ts.tolist()]))
+        kn, kh = key(ri_p, ts_p), key(ri_q, ts_q)
+        print(f"pruning: alpha_thre {a_thre:g} early_stop_eps {eps:g}: nerfacc keeps {len(kn)} of {ri_n.numel()}, this build "
+              f"{len(kh)} of {ri_h.numel()}; only nerfacc {len(kn - kh)}, only this build {len(kh - kn)}")
+        # samples within rounding of a threshold may fall either way (tests/test_gpu_visibility.py caps them at 0.1 %)
+        ok &= len(kn ^ kh) <= max(1, ri_n.numel() // 1000)
     print("PINNED: nerfacc and this build agree" if ok else "DIFFERENCES FOUND (see above)")
     return 0 if ok else 1
 
