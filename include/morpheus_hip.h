@@ -679,6 +679,88 @@ int mh_tsdf_integrate(const float *depth, const uint8_t *rgb, const uint8_t *mas
 int mh_tsdf_vertex_colors(const float *vertices, int64_t V, const float *color, int32_t nx, int32_t ny, int32_t nz, float *out,
                           void *stream);
 
+/* ---- TSDF fusion, the pooled block-sparse store (csrc/tsdf_sparse.hip) --------------------------------------------------------
+ * The same fusion into a volume that holds only the blocks a frame reached, so that the logical box may have more than 2^31
+ * voxels (Open3D's ScalableTSDFVolume is unbounded; this one is a bounded box with unbounded-looking cost).  The frame, the
+ * usable depth, the back-projection, the voxel position and every fp32 expression of touch and integrate are the dense text's
+ * above, with the GLOBAL voxel index: voxel (i, j, k) of the logical box stands at ox + ((float)i + 0.5f) * voxel_length.
+ * tests/tsdf_sparse_oracle.py is written from this text.
+ *   logical box: nbx x nby x nbz blocks of 8^3 voxels at origin.  Each side has at most 4096 blocks (32768 voxels: (float)i is
+ *     exact and a marching-cubes coordinate (float)i + t still resolves 2^-9 of a voxel), and nbx*nby*nbz < 2^31; the voxel count
+ *     may exceed 2^31 (2048 x 2048 x 1024 voxels is 2^25 blocks).  mh_tsdf_sparse_max_side_blocks returns the 4096.
+ *   index volume: slot [nbx][nby][nbz] int32, C order, 4 bytes a block; the linear block id is (bx*nby + by)*nbz + bz.  -1: no
+ *     storage; s in [0, capacity): the block's voxels are in slot s of the pool.  The one other value, -2, is no storage either
+ *     (a block being won inside mh_tsdf_sparse_touch, or one that found the pool full).  The caller fills it with -1.
+ *   pool: `capacity` >= 1 slots; slot s holds its block's 512 voxels contiguously, voxel (i, j, k) of the block at
+ *     s*512 + (i*8 + j)*8 + k.  Five fp32 planes: tsdf [capacity][512], weight [capacity][512], color [3][capacity][512]
+ *     (10 240 bytes a slot).  slot_block [capacity] int32: the block id of each slot.  counters: 2 DEVICE int32 {the number of
+ *     blocks that were given or refused a slot, the overflow flag}; min(counters[0], capacity) slots are live.  The caller
+ *     zeroes the planes and the counters once, before the first frame.
+ *   the block rule is the dense one: a block gets storage when a frame's touch pass reaches it (the same lo / hi block range,
+ *     clipped to the box in the same way), and that frame is the first it sees; a block without storage when a frame is
+ *     integrated does not see that frame, and reads as tsdf 0, weight 0, colour 0.
+ *   touch (mh_tsdf_sparse_touch): for every block of a pixel's range whose entry is -1, exactly one lane wins it (compare and
+ *     swap, -1 -> -2), takes s = the counter's next value and, when s < capacity, writes slot_block[s] and the entry.  With
+ *     s >= capacity nothing is written but the overflow flag (the entry stays -2, the counter goes on counting, so counters[0]
+ *     is the number of slots the frames so far needed).  Which block gets which slot differs from run to run; nothing an entry
+ *     point returns depends on it: every result below is defined by block coordinates.
+ *   integrate (mh_tsdf_sparse_integrate): walks the live slots (the launch is sized by capacity; mh_tsdf_sparse_group_slots
+ *     slots per workgroup, host only, for tests), decodes the block from slot_block, one lane per voxel, no atomics.
+ *   mh_tsdf_sparse_mark: the touch pass of mh_tsdf_touch (one byte per block, active [nbx][nby][nbz] uint8) over a logical box
+ *     with the limits of this section: run over all frames and summed, it is the number of slots the frames will need.
+ *   mh_tsdf_sparse_to_dense: scatters the live slots into zeroed dense arrays of the dense section's layout (the box must be
+ *     one the dense store takes: fewer than 2^31 voxels) and sets active = 1 for their blocks.
+ *   mh_tsdf_sparse_from_dense: the reverse, into a fresh store (entries -1, counters 0): block b of the dense arrays gets a slot
+ *     when keep is NULL or keep[b] != 0 (keep [nbx][nby][nbz] uint8).  order: NULL, or DEVICE int32 [nbx*nby*nbz], a permutation
+ *     of the block ids: the order in which the blocks are dispatched, hence (loosely) the order of their slots; ids outside the
+ *     box are skipped.  More kept blocks than capacity: the overflow flag, as in touch.
+ *   marching cubes (mh_mc_count_sparse / mh_mc_emit_sparse): the masked pair's rules over the logical box -- a point is
+ *     observed when its block has storage and its weight > 0; a cell exists when its eight corners are observed; a crossed edge
+ *     owns a vertex only when one of the (up to four) cells around it exists; vertex formula, winding and triangles per cell as
+ *     above -- with corner values read through the index volume from the block and its neighbours.  Vertices are in the index
+ *     space of the logical box ((float)i + t with the global i).  sorted_blocks: DEVICE int32 [capacity] whose first
+ *     min(counters[0], capacity) entries are the live slots' block ids in ascending order (the rest is not read).  Order:
+ *     blocks in ascending block id; inside a block vertices by owner point (i*8 + j)*8 + k, then axis x < y < z, triangles by
+ *     cell, then table order.  The same bytes run to run and for every assignment of slots.  For a box the dense store takes,
+ *     the vertex and triangle SETS are those of mh_mc_*_masked over the scattered volume; the order differs (by block there,
+ *     by point here).  mh_mc_sparse_workspace_bytes(capacity): host only, -1 for capacity < 1.  mh_mc_count_sparse writes
+ *     counts = {V, T} (DEVICE int64 [2]) and does NOT wait for them; the caller reads them (with the counters) and refuses
+ *     V or T >= 2^31.  mh_mc_emit_sparse (same arguments and workspace) never writes outside its V and T rows.
+ *   vertex colours (mh_tsdf_sparse_vertex_colors): the dense rule with n_a = 8 nb_a; colour reads go through the index volume
+ *     and give 0 for a block without storage.
+ * No entry point synchronises with the host.  Bad arguments return MH_ERR_ARG before any launch.  A slot read from memory is
+ * used only inside [0, capacity) and a block id only inside the box, so no state of the arrays makes a kernel write outside
+ * them. */
+int32_t mh_tsdf_sparse_group_slots(void);
+int32_t mh_tsdf_sparse_max_side_blocks(void);
+int mh_tsdf_sparse_mark(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                        const float *c2w_host, float depth_scale, float depth_trunc, int32_t stride, float ox, float oy, float oz,
+                        float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz, uint8_t *active, void *stream);
+int mh_tsdf_sparse_touch(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                         const float *c2w_host, float depth_scale, float depth_trunc, int32_t stride, float ox, float oy, float oz,
+                         float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity, int32_t *slot,
+                         int32_t *slot_block, int32_t *counters, void *stream);
+int mh_tsdf_sparse_integrate(const float *depth, const uint8_t *rgb, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy,
+                             float cx, float cy, const float *w2c_host, float depth_scale, float depth_trunc, float ox, float oy,
+                             float oz, float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity,
+                             const int32_t *slot_block, const int32_t *counters, float *tsdf, float *weight, float *color,
+                             void *stream);
+int mh_tsdf_sparse_to_dense(int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity, const int32_t *slot_block,
+                            const int32_t *counters, const float *pool_tsdf, const float *pool_weight, const float *pool_color,
+                            float *tsdf, float *weight, float *color, uint8_t *active, void *stream);
+int mh_tsdf_sparse_from_dense(const float *tsdf, const float *weight, const float *color, const uint8_t *keep, const int32_t *order,
+                              int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity, int32_t *slot, int32_t *slot_block,
+                              int32_t *counters, float *pool_tsdf, float *pool_weight, float *pool_color, void *stream);
+int64_t mh_mc_sparse_workspace_bytes(int32_t capacity);
+int mh_mc_count_sparse(const float *pool_tsdf, const float *pool_weight, const int32_t *slot, const int32_t *sorted_blocks,
+                       const int32_t *counters, int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity, float iso, void *workspace,
+                       int64_t *counts, void *stream);
+int mh_mc_emit_sparse(const float *pool_tsdf, const float *pool_weight, const int32_t *slot, const int32_t *sorted_blocks,
+                      const int32_t *counters, int32_t nbx, int32_t nby, int32_t nbz, int32_t capacity, float iso, void *workspace,
+                      float *vertices, int32_t *triangles, void *stream);
+int mh_tsdf_sparse_vertex_colors(const float *vertices, int64_t V, const float *pool_color, const int32_t *slot, int32_t nbx,
+                                 int32_t nby, int32_t nbz, int32_t capacity, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,42 +11,9 @@
 //                          arrays; a group without an active block returns after its activity bytes
 //   tsdf_vertex_colors_kernel  a lane per marching-cubes vertex
 // Every loop is bounded by the box or the image; every index is formed from clamped integers.
-#include "common.h"
+#include "tsdf_common.h"
 
-#define TSDF_BLOCK 8
 #define TSDF_GROUP 4                                    // blocks per workgroup along z: 32 voxels = one 128-byte line
-#define TSDF_THREADS 256
-#define TSDF_MAX_SIDE 16384
-
-struct TsdfFrame {
-    int32_t H, W;
-    float fx, fy, cx, cy;
-    float m[12];                // touch / bounds: camera-to-world; integrate: world-to-camera.  Row-major [3][4]
-    float depth_scale, depth_trunc;
-};
-
-struct TsdfBox {
-    float ox, oy, oz, voxel_length, sdf_trunc;
-    int32_t nbx, nby, nbz;      // blocks per side
-};
-
-// d = depth / depth_scale when the pixel is usable, else a negative number
-__device__ __forceinline__ float tsdf_depth(const float *__restrict__ depth, const uint8_t *__restrict__ mask, const TsdfFrame &f,
-                                            int i, int j) {
-    const int64_t q = (int64_t)j * f.W + i;
-    if (mask && !mask[q]) return -1.f;
-    const float d = depth[q] / f.depth_scale;
-    if (!(d > 0.f && d <= f.depth_trunc)) return -1.f;        // NaN fails both; +inf fails the second
-    return d;
-}
-
-// world-space point of pixel (i, j) at depth d: pc = (((i + 0.5) - cx) / fx * d, ((j + 0.5) - cy) / fy * d, d), P = R pc + t
-__device__ __forceinline__ void tsdf_back_project(const TsdfFrame &f, int i, int j, float d, float P[3]) {
-    const float xc = ((((float)i + 0.5f) - f.cx) / f.fx) * d;
-    const float yc = ((((float)j + 0.5f) - f.cy) / f.fy) * d;
-#pragma unroll
-    for (int r = 0; r < 3; r++) P[r] = ((f.m[4 * r] * xc + f.m[4 * r + 1] * yc) + f.m[4 * r + 2] * d) + f.m[4 * r + 3];
-}
 
 // fp32 bits -> int32 that orders like the value (-0 below +0)
 __device__ __forceinline__ int32_t tsdf_ordered(float v) {
@@ -88,33 +55,16 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_bounds_kernel(const float *
     }
 }
 
-// block range [lo, hi] along one axis of the interval [p - trunc, p + trunc]; false when it misses the box (or p is NaN)
-__device__ __forceinline__ bool tsdf_block_range(float p, float trunc, float origin, float block_len, int32_t nb, int &lo, int &hi) {
-    const float a = floorf(((p - trunc) - origin) / block_len), b = floorf(((p + trunc) - origin) / block_len);
-    if (!(b >= 0.f && a <= (float)(nb - 1))) return false;
-    lo = (int)fmaxf(a, 0.f);
-    hi = (int)fminf(b, (float)(nb - 1));
-    return true;
-}
-
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_touch_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ mask,
                                                                   TsdfFrame f, TsdfBox b, int32_t stride, int32_t ns_w,
                                                                   int64_t n_samples, uint8_t *__restrict__ active) {
     const int64_t s = (int64_t)blockIdx.x * TSDF_THREADS + threadIdx.x;
     if (s >= n_samples) return;
-    const int j = (int)(s / ns_w) * stride, i = (int)(s % ns_w) * stride;
-    const float d = tsdf_depth(depth, mask, f, i, j);
-    if (!(d > 0.f)) return;
-    float P[3];
-    tsdf_back_project(f, i, j, d, P);
-    const float bl = 8.0f * b.voxel_length;
-    int x0, x1, y0, y1, z0, z1;
-    if (!tsdf_block_range(P[0], b.sdf_trunc, b.ox, bl, b.nbx, x0, x1) || !tsdf_block_range(P[1], b.sdf_trunc, b.oy, bl, b.nby, y0, y1) ||
-        !tsdf_block_range(P[2], b.sdf_trunc, b.oz, bl, b.nbz, z0, z1))
-        return;
-    for (int x = x0; x <= x1; x++)
-        for (int y = y0; y <= y1; y++)
-            for (int z = z0; z <= z1; z++) active[((int64_t)x * b.nby + y) * b.nbz + z] = 1;
+    int lo[3], hi[3];
+    if (!tsdf_touch_range(depth, mask, f, b, stride, ns_w, s, lo, hi)) return;
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int y = lo[1]; y <= hi[1]; y++)
+            for (int z = lo[2]; z <= hi[2]; z++) active[((int64_t)x * b.nby + y) * b.nbz + z] = 1;
 }
 
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ rgb,
@@ -142,28 +92,9 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(const floa
     for (int xi = 0; xi < TSDF_BLOCK; xi++) {
         const int i = bx * TSDF_BLOCK + xi;
         const float px = b.ox + ((float)i + 0.5f) * b.voxel_length;
-        float pc[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++) pc[q] = ((f.m[4 * q] * px + f.m[4 * q + 1] * py) + f.m[4 * q + 2] * pz) + f.m[4 * q + 3];
-        if (!(pc[2] > 0.f)) continue;
-        const float u = floorf((f.fx * pc[0]) / pc[2] + f.cx), v = floorf((f.fy * pc[1]) / pc[2] + f.cy);
-        if (!(u >= 0.f && u < (float)f.W && v >= 0.f && v < (float)f.H)) continue;
-        const int pi = (int)u, pj = (int)v;
-        const float d = tsdf_depth(depth, mask, f, pi, pj);
-        if (!(d > 0.f)) continue;
-        const float a = (((float)pi + 0.5f) - f.cx) / f.fx, c = (((float)pj + 0.5f) - f.cy) / f.fy;
-        const float m = sqrtf((1.0f + a * a) + c * c);
-        const float sdf = (d - pc[2]) * m;
-        if (!(sdf > -b.sdf_trunc)) continue;
-        const float q = sdf / b.sdf_trunc;
-        const float t = q < 1.0f ? q : 1.0f;
         const int64_t p = ((int64_t)i * ny + j) * nz + k;
-        const float w = weight[p], w1 = w + 1.0f;
-        tsdf[p] = (tsdf[p] * w + t) / w1;
-        const uint8_t *px8 = rgb + 3 * ((int64_t)pj * f.W + pi);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) color[ch * plane + p] = (color[ch * plane + p] * w + (float)px8[ch]) / w1;
-        weight[p] = w1;
+        tsdf_update_voxel(depth, rgb, mask, f, b.sdf_trunc, px, py, pz, tsdf + p, weight + p, color + p, color + plane + p,
+                          color + 2 * plane + p);
     }
 }
 
@@ -204,25 +135,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_vertex_colors_kernel(const 
     }
 }
 
-static bool tsdf_frame(TsdfFrame *f, const float *depth, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
-                       const float *m_host, float depth_scale, float depth_trunc) {
-    if (!depth || !m_host || H < 1 || W < 1 || H > TSDF_MAX_SIDE || W > TSDF_MAX_SIDE) return false;
-    if (!(fx != 0.f) || !(fy != 0.f) || !(depth_scale > 0.f) || !(depth_trunc > 0.f)) return false;
-    f->H = H, f->W = W, f->fx = fx, f->fy = fy, f->cx = cx, f->cy = cy;
-    for (int q = 0; q < 12; q++) f->m[q] = m_host[q];
-    f->depth_scale = depth_scale, f->depth_trunc = depth_trunc;
-    return true;
-}
-
-static bool tsdf_box(TsdfBox *b, float ox, float oy, float oz, float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby,
-                     int32_t nbz) {
-    if (!(voxel_length > 0.f) || !(sdf_trunc > 0.f) || nbx < 1 || nby < 1 || nbz < 1) return false;
-    if ((int64_t)nbx * nby * nbz * 512 >= ((int64_t)1 << 31)) return false;
-    b->ox = ox, b->oy = oy, b->oz = oz, b->voxel_length = voxel_length, b->sdf_trunc = sdf_trunc;
-    b->nbx = nbx, b->nby = nby, b->nbz = nbz;
-    return true;
-}
-
 extern "C" int32_t mh_tsdf_group_blocks(void) { return TSDF_GROUP; }
 
 extern "C" int mh_tsdf_bounds(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
@@ -246,6 +158,24 @@ extern "C" int mh_tsdf_touch(const float *depth, const uint8_t *mask, int32_t H,
     TsdfBox b;
     if (!tsdf_frame(&f, depth, H, W, fx, fy, cx, cy, c2w_host, depth_scale, depth_trunc) || stride < 1 || !active ||
         !tsdf_box(&b, ox, oy, oz, voxel_length, sdf_trunc, nbx, nby, nbz))
+        return MH_ERR_ARG;
+    const int32_t ns_w = (W + stride - 1) / stride, ns_h = (H + stride - 1) / stride;
+    const int64_t n = (int64_t)ns_w * ns_h;
+    hipLaunchKernelGGL(tsdf_touch_kernel, dim3((unsigned)((n + TSDF_THREADS - 1) / TSDF_THREADS)), dim3(TSDF_THREADS), 0,
+                       mh_stream(stream), depth, mask, f, b, stride, ns_w, n, active);
+    MH_CHECK_LAUNCH();
+    return MH_OK;
+}
+
+// the touch pass over the sparse store's logical box (more voxels than mh_tsdf_touch takes): the same kernel, one byte per block
+extern "C" int mh_tsdf_sparse_mark(const float *depth, const uint8_t *mask, int32_t H, int32_t W, float fx, float fy, float cx,
+                                   float cy, const float *c2w_host, float depth_scale, float depth_trunc, int32_t stride, float ox,
+                                   float oy, float oz, float voxel_length, float sdf_trunc, int32_t nbx, int32_t nby, int32_t nbz,
+                                   uint8_t *active, void *stream) {
+    TsdfFrame f;
+    TsdfBox b;
+    if (!tsdf_frame(&f, depth, H, W, fx, fy, cx, cy, c2w_host, depth_scale, depth_trunc) || stride < 1 || !active ||
+        !tsdf_sparse_box(&b, ox, oy, oz, voxel_length, sdf_trunc, nbx, nby, nbz))
         return MH_ERR_ARG;
     const int32_t ns_w = (W + stride - 1) / stride, ns_h = (H + stride - 1) / stride;
     const int64_t n = (int64_t)ns_w * ns_h;

@@ -6,8 +6,12 @@ voxels by the HIP kernels of csrc/tsdf.hip (mh_tsdf_touch + mh_tsdf_integrate pe
 frames), the surface comes from the masked marching cubes of csrc/mesh.hip (cells with an unobserved corner give nothing) and
 the vertex colours from mh_tsdf_vertex_colors.  Conventions: include/morpheus_hip.h (TSDF fusion).
 
-Storage is dense inside the box: 20 bytes per voxel and one byte per 8^3 block.  A box that does not fit is refused before
-anything is allocated (volume_bytes / memory_cap_bytes); a pooled block-sparse store is not part of this module.
+Two stores share the kernels' per-voxel arithmetic.  TSDFVolume is dense inside the box: 20 bytes per voxel and one byte per
+8^3 block; a box that does not fit (2^31 voxels or more, or more bytes than the cap) is refused before anything is allocated
+(volume_bytes / memory_cap_bytes).  SparseTSDFVolume (csrc/tsdf_sparse.hip) holds only the blocks a frame reached, in a pool of
+capacity_blocks slots behind an index volume of 4 bytes per block (sparse_bytes): the same block rule, the same bytes per
+voxel, a logical box of up to 32768 voxels a side.  run_tsdf_fusion(store="sparse") sizes the pool from the frames.  The
+default stays dense: the sparse store is asked for, never fallen back to.
 """
 from __future__ import annotations
 
@@ -26,6 +30,9 @@ BLOCK = 8
 BYTES_PER_VOXEL = 20                 # tsdf, weight and three colour planes, fp32
 PIXEL_CENTERS = ("integer", "half")
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+STORES = ("dense", "sparse")
+SPARSE_MAX_SIDE_BLOCKS = 4096        # blocks per side of the sparse store's logical box (mh_tsdf_sparse_max_side_blocks)
+BYTES_PER_SLOT = BLOCK ** 3 * BYTES_PER_VOXEL                       # 10 240: one block's five fp32 planes
 
 
 def volume_bytes(dims: Sequence[int]) -> int:
@@ -57,7 +64,43 @@ def check_box(origin, dims, voxel_length: float, cap_bytes: float) -> None:
         raise MorpheusHipError(
             f"TSDF box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
             f"{float(voxel_length):g} is {nx} x {ny} x {nz} = {n} voxels: {why}.  Pass a tighter box with bounds=(min, max), or a "
-            f"larger voxel_length (storage falls with its cube); max_gb= raises the cap.")
+            f"larger voxel_length (storage falls with its cube); max_gb= raises the cap.  run_tsdf_fusion(store=\"sparse\") and "
+            f"SparseTSDFVolume hold only the blocks that the frames reach.")
+
+
+def sparse_bytes(dims: Sequence[int], capacity_blocks: int) -> int:
+    """device bytes of a block-sparse volume over a logical box of dims voxels with a pool of capacity_blocks slots: 10 240 per
+    slot (five fp32 planes of 512 voxels) + 4 per slot (its block id) + 4 per block of the box (the index volume) + 8 (the
+    slot counter and the overflow flag)"""
+    blocks = (int(dims[0]) // BLOCK) * (int(dims[1]) // BLOCK) * (int(dims[2]) // BLOCK)
+    return int(capacity_blocks) * (BYTES_PER_SLOT + 4) + 4 * blocks + 8
+
+
+def _capacity(capacity_blocks) -> int:
+    if isinstance(capacity_blocks, bool) or not isinstance(capacity_blocks, (int, np.integer)) or not 1 <= capacity_blocks < 2 ** 31:
+        raise MorpheusHipError(f"capacity_blocks must be an integer in [1, 2^31), got {capacity_blocks!r}")
+    return int(capacity_blocks)
+
+
+def check_sparse_box(origin, dims, voxel_length: float, capacity_blocks: int, cap_bytes: float) -> None:
+    """Raises MorpheusHipError when the block-sparse store cannot hold the logical box: a side over 32768 voxels, 2^31 blocks or
+    more, or more bytes (sparse_bytes) than cap_bytes."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < BLOCK or any(d % BLOCK for d in (nx, ny, nz)):
+        raise MorpheusHipError(f"TSDF box: dims must be positive multiples of the block side {BLOCK}, got {(nx, ny, nz)}")
+    capacity = _capacity(capacity_blocks)
+    blocks = (nx // BLOCK) * (ny // BLOCK) * (nz // BLOCK)
+    need = sparse_bytes((nx, ny, nz), capacity)
+    side = max(nx, ny, nz) > SPARSE_MAX_SIDE_BLOCKS * BLOCK
+    if side or blocks >= 2 ** 31 or need > cap_bytes:
+        lo = [float(o) for o in origin]
+        hi = [o + d * float(voxel_length) for o, d in zip(lo, (nx, ny, nz))]
+        why = (f"a side over {SPARSE_MAX_SIDE_BLOCKS * BLOCK} voxels" if side else "more than 2^31 - 1 blocks" if blocks >= 2 ** 31 else
+               f"{need / 1e9:.2f} GB ({need} bytes: {BYTES_PER_SLOT + 4} per slot, 4 per block), over the cap of {cap_bytes / 1e9:.2f} GB")
+        raise MorpheusHipError(
+            f"sparse TSDF box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
+            f"{float(voxel_length):g} is {nx} x {ny} x {nz} voxels = {blocks} blocks with capacity_blocks = {capacity}: {why}.  Pass a "
+            f"tighter box with bounds=(min, max), a larger voxel_length or a smaller capacity_blocks; max_gb= raises the cap.")
 
 
 def box_from_bounds(lo, hi, voxel_length: float, margin: float):
@@ -141,6 +184,24 @@ def _host_ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _frame(device, depth, color, K, c2w, mask, stride, pixel_centers):
+    """what both stores' integrate() hand the kernels: (depth fp32, rgb uint8, mask uint8 or None, H, W, (fx, fy, cx, cy), c2w
+    [3,4], w2c [3,4])"""
+    intr = _intrinsics(K, pixel_centers)
+    if int(stride) < 1:
+        raise MorpheusHipError(f"stride must be >= 1, got {stride}")
+    d = _depth32(depth, device)
+    c = rgb8(color, device=device)
+    m = mask8(mask, device)
+    H, W = d.shape
+    if c.shape[:2] != (H, W) or (m is not None and m.shape != (H, W)):
+        raise MorpheusHipError(f"depth {tuple(d.shape)}, color {tuple(c.shape)} and mask "
+                               f"{None if m is None else tuple(m.shape)} must share H and W")
+    require_gpu(d, c, m)
+    c2w_h, w2c_h = _pose(c2w)
+    return d, c, m, H, W, intr, c2w_h, w2c_h
+
+
 class TSDFVolume:
     """A dense truncated signed distance volume on the device.  origin: world position of the box's corner; dims = (nx, ny,
     nz) voxels, multiples of 8.  Attributes: tsdf, weight [nx,ny,nz] fp32, color [3,nx,ny,nz] fp32 in [0, 255], active
@@ -169,18 +230,7 @@ class TSDFVolume:
                   stride: int = 4, pixel_centers: str = "half") -> None:
         """One frame: depth [H,W], color [H,W,3] (uint8 RGB8, or floating point in [0, 1]), K [3,3], c2w the OpenCV
         camera-to-world pose, mask [H,W] (pixels with mask <= 0 are not used).  Two launches, no host synchronisation."""
-        fx, fy, cx, cy = _intrinsics(K, pixel_centers)
-        if int(stride) < 1:
-            raise MorpheusHipError(f"stride must be >= 1, got {stride}")
-        d = _depth32(depth, self.device)
-        c = rgb8(color, device=self.device)
-        m = mask8(mask, self.device)
-        H, W = d.shape
-        if c.shape[:2] != (H, W) or (m is not None and m.shape != (H, W)):
-            raise MorpheusHipError(f"depth {tuple(d.shape)}, color {tuple(c.shape)} and mask "
-                                   f"{None if m is None else tuple(m.shape)} must share H and W")
-        require_gpu(d, c, m)
-        c2w_h, w2c_h = _pose(c2w)
+        d, c, m, H, W, (fx, fy, cx, cy), c2w_h, w2c_h = _frame(self.device, depth, color, K, c2w, mask, stride, pixel_centers)
         box = (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
         launch("mh_tsdf_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale), float(depth_trunc),
                int(stride), *box, ptr(self.active))
@@ -205,6 +255,166 @@ class TSDFVolume:
         origin = torch.from_numpy(self.origin).to(self.device)
         vertices = origin + (iv + 0.5) * self.voxel_length
         return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+
+
+class SparseTSDFVolume:
+    """A truncated signed distance volume that stores only the 8^3 blocks a frame reached (include/morpheus_hip.h, the pooled
+    block-sparse store).  origin, dims: the LOGICAL box, as TSDFVolume's but with up to 32768 voxels a side and no limit on the
+    voxel count; capacity_blocks: the slots of the pool, fixed at construction (10 240 bytes each).  The block rule and every
+    voxel's bytes are TSDFVolume's.  Attributes: slot [nbx,nby,nbz] int32 (-1: no storage), slot_block [capacity] int32, counters
+    [2] int32 (slots wanted, overflow flag), tsdf, weight [capacity,512] fp32, color [3,capacity,512] fp32.
+    When the frames reach more blocks than the pool has slots, the blocks beyond it stay without storage, nothing is written
+    outside the pool, and the first call that reads the device anyway (check, allocated_blocks, to_dense, extract_mesh) raises."""
+
+    def __init__(self, voxel_length: float, sdf_trunc: float, origin, dims, capacity_blocks: int, device="cuda",
+                 max_gb: Optional[float] = None):
+        if not (voxel_length > 0 and sdf_trunc > 0):
+            raise MorpheusHipError(f"voxel_length and sdf_trunc must be positive, got {voxel_length}, {sdf_trunc}")
+        self.capacity = _capacity(capacity_blocks)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise MorpheusHipError(f"SparseTSDFVolume runs on an MI355X only (device is {device}); there is no CPU path")
+        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
+        self.origin = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
+        self.dims = tuple(int(d) for d in dims)
+        check_sparse_box(self.origin, self.dims, voxel_length, self.capacity, memory_cap_bytes(device, max_gb))
+        self.device, self.max_gb = device, max_gb
+        self.blocks = tuple(d // BLOCK for d in self.dims)
+        n = BLOCK ** 3
+        self.slot = torch.full(self.blocks, -1, dtype=torch.int32, device=device)
+        self.slot_block = torch.zeros(self.capacity, dtype=torch.int32, device=device)
+        self.counters = torch.zeros(2, dtype=torch.int32, device=device)
+        self.tsdf = torch.zeros(self.capacity, n, dtype=torch.float32, device=device)
+        self.weight = torch.zeros(self.capacity, n, dtype=torch.float32, device=device)
+        self.color = torch.zeros(3, self.capacity, n, dtype=torch.float32, device=device)
+        self.frames = 0
+
+    def _box(self):
+        return (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
+
+    def integrate(self, depth, color, K, c2w, mask=None, *, depth_scale: float = 1.0, depth_trunc: float = 10.0,
+                  stride: int = 4, pixel_centers: str = "half") -> None:
+        """One frame, as TSDFVolume.integrate.  Two launches, no host synchronisation."""
+        d, c, m, H, W, (fx, fy, cx, cy), c2w_h, w2c_h = _frame(self.device, depth, color, K, c2w, mask, stride, pixel_centers)
+        launch("mh_tsdf_sparse_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+               float(depth_trunc), int(stride), *self._box(), self.capacity, ptr(self.slot), ptr(self.slot_block), ptr(self.counters))
+        launch("mh_tsdf_sparse_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(w2c_h), float(depth_scale),
+               float(depth_trunc), *self._box(), self.capacity, ptr(self.slot_block), ptr(self.counters), ptr(self.tsdf),
+               ptr(self.weight), ptr(self.color))
+        self.frames += 1
+
+    def _checked(self, wanted: int, overflow: int) -> int:
+        if overflow or wanted > self.capacity:
+            raise MorpheusHipError(
+                f"SparseTSDFVolume: the pool of capacity_blocks = {self.capacity} slots is full: the frames so far reached {wanted} "
+                f"blocks, and those beyond the pool were left without storage, so the volume is incomplete.  Build it again with "
+                f"capacity_blocks >= {wanted}; run_tsdf_fusion(store=\"sparse\") without capacity_blocks sizes the pool from the "
+                f"frames (the union of the blocks their touch passes reach).")
+        return wanted
+
+    def check(self) -> int:
+        """-> the number of allocated blocks; raises when the pool overflowed.  One host read."""
+        wanted, overflow = self.counters.tolist()
+        return self._checked(wanted, overflow)
+
+    def allocated_blocks(self) -> torch.Tensor:
+        """-> int64 [n]: the linear ids (bx*nby + by)*nbz + bz of the blocks with storage, ascending.  One host read."""
+        return self.slot_block[:self.check()].sort().values.long()
+
+    def to_dense(self) -> "TSDFVolume":
+        """-> a TSDFVolume over the same box with the same bytes (active = the allocated blocks); refused with the dense store's
+        own error when the box does not fit it."""
+        vol = TSDFVolume(self.voxel_length, self.sdf_trunc, self.origin, self.dims, device=self.device, max_gb=self.max_gb)
+        self.check()
+        launch("mh_tsdf_sparse_to_dense", *self.blocks, self.capacity, ptr(self.slot_block), ptr(self.counters), ptr(self.tsdf),
+               ptr(self.weight), ptr(self.color), ptr(vol.tsdf), ptr(vol.weight), ptr(vol.color), ptr(vol.active))
+        vol.frames = self.frames
+        return vol
+
+    @classmethod
+    def from_dense(cls, dense: "TSDFVolume", keep=None, capacity_blocks: Optional[int] = None, block_order=None,
+                   max_gb: Optional[float] = None) -> "SparseTSDFVolume":
+        """The blocks of `dense` where keep [nbx,nby,nbz] != 0 (default: dense.active) as a sparse volume over the same box.
+        capacity_blocks: default the number of kept blocks (one host read), at least 1.  block_order: a permutation of the
+        nbx*nby*nbz block ids, the order in which blocks are handed their slots (no result depends on it)."""
+        keep = dense.active if keep is None else _tensor(keep, dense.device)
+        if tuple(keep.shape) != dense.blocks:
+            raise MorpheusHipError(f"from_dense: keep must be {dense.blocks}, one entry per block, got {tuple(keep.shape)}")
+        keep = (keep != 0).to(torch.uint8).contiguous()
+        if capacity_blocks is None:
+            capacity_blocks = max(int(keep.sum(dtype=torch.int64)), 1)
+        order = None
+        if block_order is not None:
+            order = _tensor(block_order, dense.device).to(torch.int32).contiguous()
+            if order.dim() != 1 or order.numel() != keep.numel():
+                raise MorpheusHipError(f"from_dense: block_order must list all {keep.numel()} block ids, got {tuple(order.shape)}")
+        vol = cls(dense.voxel_length, dense.sdf_trunc, dense.origin, dense.dims, capacity_blocks, device=dense.device, max_gb=max_gb)
+        require_gpu(dense.tsdf, dense.weight, dense.color, keep, order)
+        launch("mh_tsdf_sparse_from_dense", ptr(dense.tsdf), ptr(dense.weight), ptr(dense.color), ptr(keep), ptr(order), *vol.blocks,
+               vol.capacity, ptr(vol.slot), ptr(vol.slot_block), ptr(vol.counters), ptr(vol.tsdf), ptr(vol.weight), ptr(vol.color))
+        vol.frames = dense.frames
+        return vol
+
+    def vertex_colors(self, index_vertices: torch.Tensor) -> torch.Tensor:
+        """colours in [0, 1] of marching-cubes vertices given in the logical box's index space"""
+        require_gpu(index_vertices)
+        V = index_vertices.shape[0]
+        out = torch.empty(V, 3, dtype=torch.float32, device=self.device)
+        launch("mh_tsdf_sparse_vertex_colors", ptr(index_vertices), V, ptr(self.color), ptr(self.slot), *self.blocks, self.capacity,
+               ptr(out))
+        return out
+
+    def marching_cubes(self, isovalue: float = 0.0):
+        """-> (vertices fp32 [V,3] in the logical box's index space, triangles int64 [T,3]): the masked marching cubes over the
+        allocated blocks, in ascending block id whatever the slot order.  One host read (sizes, slot counter, overflow flag)."""
+        lib = _lib.load()
+        dev = self.device
+        live = self.counters[0].clamp(max=self.capacity)
+        ids = torch.where(torch.arange(self.capacity, device=dev) < live, self.slot_block, INT32_MAX)
+        sorted_blocks = ids.sort().values.to(torch.int32).contiguous()
+        ws = torch.empty(lib.mh_mc_sparse_workspace_bytes(self.capacity), dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        args = (ptr(self.tsdf), ptr(self.weight), ptr(self.slot), ptr(sorted_blocks), ptr(self.counters), *self.blocks, self.capacity,
+                float(isovalue), ptr(ws))
+        launch("mh_mc_count_sparse", *args, ptr(counts))
+        V, T, wanted, overflow = torch.cat([counts, self.counters.long()]).tolist()
+        self._checked(wanted, overflow)
+        if V >= 2 ** 31 or T >= 2 ** 31:
+            raise MorpheusHipError(f"SparseTSDFVolume: {V} vertices / {T} triangles do not fit int32 indices")
+        vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
+        if V or T:
+            launch("mh_mc_emit_sparse", *args, ptr(vertices), ptr(triangles))
+        return vertices, triangles.long()
+
+    def extract_mesh(self) -> dict:
+        """As TSDFVolume.extract_mesh: dict(vertices world space, triangles, colors); the same vertex and triangle sets as the
+        dense volume's (ordered by block).  One host synchronisation."""
+        iv, tri = self.marching_cubes(0.0)
+        colors = self.vertex_colors(iv)
+        origin = torch.from_numpy(self.origin).to(self.device)
+        vertices = origin + (iv + 0.5) * self.voxel_length
+        return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+
+
+def count_touched_blocks(K, c2w_list, depth_list, mask_list, origin, dims, voxel_length, sdf_trunc, *, depth_scale=1.0,
+                         depth_trunc=10.0, stride=4, pixel_centers="integer", device="cuda") -> int:
+    """-> the number of blocks of the logical box that the touch passes of all frames reach: what a SparseTSDFVolume fed the same
+    frames allocates.  One launch per frame into one byte per block, and ONE host read."""
+    fx, fy, cx, cy = _intrinsics(K, pixel_centers)
+    device = torch.device(device)
+    blocks = tuple(int(d) // BLOCK for d in dims)
+    o = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
+    active = torch.zeros(blocks, dtype=torch.uint8, device=device)
+    for f, (c2w, depth) in enumerate(zip(c2w_list, depth_list)):
+        d = _depth32(depth, device)
+        m = mask8(None if mask_list is None else mask_list[f], device)
+        require_gpu(d, m)
+        c2w_h, _ = _pose(c2w)
+        launch("mh_tsdf_sparse_mark", ptr(d), ptr(m), d.shape[0], d.shape[1], fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+               float(depth_trunc), int(stride), float(o[0]), float(o[1]), float(o[2]), float(voxel_length), float(sdf_trunc), *blocks,
+               ptr(active))
+    return int(active.sum(dtype=torch.int64))
 
 
 def frame_bounds(K, c2w_list, depth_list, mask_list=None, *, depth_scale=1.0, depth_trunc=10.0, stride=4,
@@ -243,7 +453,8 @@ def _empty_mesh(device):
 def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, skip=None, save_path=None, depth_scale=1.0,
                     depth_trunc=10.0, sdf_trunc=0.04, voxel_length=0.02, gray_scale=False, *, bounds=None,
                     pixel_centers: str = "integer", stride: int = 4, max_gb: Optional[float] = None, device="cuda",
-                    intensity_scale: float = 1.0, alpha: float = 0.0, return_volume: bool = False):
+                    intensity_scale: float = 1.0, alpha: float = 0.0, return_volume: bool = False, store: str = "dense",
+                    capacity_blocks: Optional[int] = None):
     """run_tsdf_fusion (tools/vis.py:315-361) on the device -> dict(vertices, triangles, colors), what meshrender, mesheval and
     mesh.write_ply take; written as a PLY to save_path when that is given.
     K [3,3]; c2w_list: OpenCV camera-to-world poses; depth_list [H,W]; rgb_list [H,W,3] in [0, 1] (or uint8); mask_list [H,W] or
@@ -252,6 +463,9 @@ def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, ski
     "half" as the rest of this library does.  bounds = (min [3], max [3]) fixes the box (grown by sdf_trunc and to whole
     blocks); without it the box is sized from the frames' own back-projected pixels (one more launch per frame and one host
     read).  A box over max_gb (default: min(0.4 of the device, 0.85 of what is free)) is refused before anything is allocated.
+    store: "dense" (TSDFVolume, the default) or "sparse" (SparseTSDFVolume: only the blocks the frames reach are stored, so a
+    box the dense store refuses can be fused); never chosen automatically.  capacity_blocks (sparse only): the slots of the
+    pool; without it the pool is sized exactly, by one touch pass over all frames and one more host read.
     No host synchronisation inside the frame loop."""
     n = len(c2w_list)
     if len(depth_list) != n or len(rgb_list) != n or (mask_list is not None and len(mask_list) != n):
@@ -260,6 +474,12 @@ def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, ski
     if not (voxel_length > 0 and sdf_trunc > 0 and depth_scale > 0 and depth_trunc > 0) or int(stride) < 1:
         raise MorpheusHipError("run_tsdf_fusion: voxel_length, sdf_trunc, depth_scale and depth_trunc must be positive, stride >= 1")
     _intrinsics(K, pixel_centers)
+    if store not in STORES:
+        raise MorpheusHipError(f"run_tsdf_fusion: store must be one of {STORES}, got {store!r}")
+    if capacity_blocks is not None:
+        if store != "sparse":
+            raise MorpheusHipError("run_tsdf_fusion: capacity_blocks sizes the pool of store=\"sparse\"; the dense store has none")
+        _capacity(capacity_blocks)
     H, W = int(H), int(W)
     for f in range(n):
         if tuple(depth_list[f].shape) != (H, W):
@@ -277,7 +497,15 @@ def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, ski
             return (mesh, None) if return_volume else mesh
         bounds = found
     origin, dims = box_from_bounds(bounds[0], bounds[1], voxel_length, sdf_trunc)
-    vol = TSDFVolume(voxel_length, sdf_trunc, origin, dims, device=device, max_gb=max_gb)
+    if store == "sparse":
+        if capacity_blocks is None:
+            check_sparse_box(origin, dims, voxel_length, 1, memory_cap_bytes(device, max_gb))
+            capacity_blocks = max(1, count_touched_blocks(K, c2w_list, depth_list, mask_list, origin, dims, voxel_length, sdf_trunc,
+                                                          depth_scale=depth_scale, depth_trunc=depth_trunc, stride=stride,
+                                                          pixel_centers=pixel_centers, device=device))
+        vol = SparseTSDFVolume(voxel_length, sdf_trunc, origin, dims, capacity_blocks, device=device, max_gb=max_gb)
+    else:
+        vol = TSDFVolume(voxel_length, sdf_trunc, origin, dims, device=device, max_gb=max_gb)
     for f in range(n):
         c = rgb8(rgb_list[f], gray_scale, intensity_scale, alpha, device=device)
         vol.integrate(depth_list[f], c, K, c2w_list[f], None if mask_list is None else mask_list[f], depth_scale=depth_scale,
@@ -291,7 +519,8 @@ def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, ski
 def back_proj_frame(K, H, W, c2w, depth, rgb, save_path=None, mask=None, depth_scale=1.0, depth_trunc=10.0, sdf_trunc=0.04,
                     voxel_length=0.02, gray_scale=False, intensity_scale=1.0, alpha=0.0, **kwargs):
     """back_proj_frame (tools/vis.py:251-312): run_tsdf_fusion of one frame, with its colour options (gray_scale, else
-    intensity_scale < 1, else alpha > 0).  The point-cloud form (save_as_pcd) is not provided."""
+    intensity_scale < 1, else alpha > 0).  store= and capacity_blocks= go through.  The point-cloud form (save_as_pcd) is not
+    provided."""
     if kwargs.pop("save_as_pcd", False):
         raise MorpheusHipError("back_proj_frame: save_as_pcd (Open3D's extract_point_cloud) is not provided")
     return run_tsdf_fusion(K, H, W, [c2w], [depth], [rgb], None if mask is None else [mask], save_path=save_path,

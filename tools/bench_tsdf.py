@@ -1,6 +1,7 @@
 """Time the TSDF fusion (morpheus_amd.tsdf, csrc/tsdf.hip) and the masked marching cubes (csrc/mesh.hip).
 
     python tools/bench_tsdf.py [--dims 256,512] [--frames 200] [--views 20] [--reps 20] [--out profiles/r10_tsdf_fusion.txt]
+    python tools/bench_tsdf.py --store sparse [--grow 1,2] ...      the pooled block-sparse store (csrc/tsdf_sparse.hip)
 
 Scene: synthetic (no dataset is assumed): an icosphere of radius 0.3 standing on a quad, --views cameras on a circle of radius
 1.2, depth and colour at 640 x 480 from this library's own rasteriser; the views are cycled to --frames frames.  The box is the
@@ -22,6 +23,21 @@ scene (a sphere and a ground plane in a cube) the active share should be well un
 launch floor of a few microseconds of device time plus the host's ~10 us a call: 400 launches in ~10 ms, host-bound.  The masked
 pair with all weights positive should be within the unmasked pair's own run-to-run spread, plus one streaming pass over the
 weights (the cell marks: 4 B read + 1 B written a voxel, ~0.2 ms at 512^3).
+--store sparse: the same scene into SparseTSDFVolume.  The logical box is the cube above grown --grow times a side (the content
+stays where it is: the origin moves out by whole blocks), the pool is sized exactly (tsdf.count_touched_blocks).  Rows: the
+per-launch pair (mh_tsdf_sparse_touch / mh_tsdf_sparse_integrate, timed as above; after the first pass every block has its slot,
+as the dense activity bytes are all set), pool bytes (tsdf.sparse_bytes) against the dense bytes of the same box
+(tsdf.volume_bytes), run_tsdf_fusion(store="sparse") and extract_mesh wall clock.
+Expectation for the sparse store, written before its first run: integrate walks allocated blocks x 512 voxels x 20 B (read and
+written: x 40 B), the bytes of the dense launch's active blocks, in full 256-byte lines, and skips the dense launch's pass over
+the activity bytes of the whole grid; so per frame it should cost no more than the dense launch on the same box, and it should
+stay flat when the logical box grows 8 x at fixed content (--grow 2), where only the index volume grows (4 B a block, touched
+by the touch pass alone).  At grow 1 the allocated blocks are the dense active ones; at grow 2 the ground plane reaches beyond
+the cube, so "fixed content" holds for the sphere only and the allocated count is reported beside the time.  Both launches
+should sit near the launch floor on this scene, as the dense ones.  The sparse touch adds one atomic per NEW block, none in
+the steady state that the passes time.  extract_mesh over the sparse store stages a 10^3 halo per block through the index
+volume (2 x the block's own points); it should cost less than the dense masked pair whenever well under half of the blocks are
+allocated, since the dense pair visits every point of the box.
 Result: see the file named by --out and DESIGN 7d.
 """
 from __future__ import annotations
@@ -92,6 +108,55 @@ def wall_once(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def bench_sparse(a, emit, dev, K, poses, depths, rgbs, order, dims, grow):
+    """the rows of --store sparse for one cube size and one logical box"""
+    vl = 2 * HALF / dims
+    trunc = 2 * vl
+    shift = (grow - 1) * (dims // 8) // 2                          # blocks: the cube sits in the middle of the logical box
+    origin = tuple(-HALF - shift * 8 * vl for _ in range(3))
+    ldims = (dims * grow,) * 3
+    fx, fy, cx, cy = tsdf._intrinsics(K, "half")
+    host = [tsdf._pose(p) for p in poses]
+    views = sorted(set(order))
+    need = tsdf.count_touched_blocks(K, [poses[f] for f in views], [depths[f] for f in views], None, origin, ldims, vl, trunc,
+                                     pixel_centers="half", stride=4, device=dev)
+    vol = tsdf.SparseTSDFVolume(vl, trunc, origin, ldims, max(need, 1), device=dev)
+    box = vol._box()
+
+    def touch_pass():
+        for f in order:
+            tsdf.launch("mh_tsdf_sparse_touch", tsdf.ptr(depths[f]), None, H, W, fx, fy, cx, cy, tsdf._host_ptr(host[f][0]), 1.0, 10.0,
+                        4, *box, vol.capacity, tsdf.ptr(vol.slot), tsdf.ptr(vol.slot_block), tsdf.ptr(vol.counters))
+
+    def integrate_pass():
+        for f in order:
+            tsdf.launch("mh_tsdf_sparse_integrate", tsdf.ptr(depths[f]), tsdf.ptr(rgbs[f]), None, H, W, fx, fy, cx, cy,
+                        tsdf._host_ptr(host[f][1]), 1.0, 10.0, *box, vol.capacity, tsdf.ptr(vol.slot_block), tsdf.ptr(vol.counters),
+                        tsdf.ptr(vol.tsdf), tsdf.ptr(vol.weight), tsdf.ptr(vol.color))
+
+    touch = event_pass_ms(touch_pass, a.reps, a.frames)
+    integ = event_pass_ms(integrate_pass, a.reps, a.frames)
+    allocated = vol.check()
+    nbytes = allocated * 512 * 40 + H * W * 7
+    pool, dense = tsdf.sparse_bytes(ldims, vol.capacity), tsdf.volume_bytes(ldims)
+    emit(dict(row="sparse_launch", dims=dims, logical_dims=ldims[0], voxel_length=round(vl, 6), allocated_blocks=allocated,
+              allocated_share=round(allocated / (ldims[0] // 8) ** 3, 5), touch_ms=touch, integrate_ms=integ, integrate_bytes=int(nbytes),
+              integrate_GB_per_s=round(nbytes / (integ["median"] * 1e-3) / 1e9, 1), pool_bytes=pool, dense_bytes=dense,
+              pool_over_dense=round(pool / dense, 5)))
+    del vol
+    lo, hi = np.array(origin) + trunc, np.array(origin) + ldims[0] * vl - trunc - 0.5 * vl
+    fuse = []
+    for _ in range(3 + max(3, a.reps // 4)):
+        ms, (m, vol) = wall_once(lambda: tsdf.run_tsdf_fusion(
+            K, H, W, [poses[f] for f in order], [depths[f] for f in order], [rgbs[f] for f in order], bounds=(lo, hi),
+            voxel_length=vl, sdf_trunc=trunc, pixel_centers="half", device=dev, return_volume=True, store="sparse"))
+        fuse.append(ms)
+    extract = [wall_once(vol.extract_mesh)[0] for _ in range(3 + a.reps)][3:]
+    emit(dict(row="sparse_fusion", dims=dims, logical_dims=vol.dims[0], frames=a.frames, run_tsdf_fusion_ms=_stats(fuse[3:], 3),
+              extract_mesh_ms=_stats(extract, 3), V=int(m["vertices"].shape[0]), T=int(m["triangles"].shape[0]),
+              allocated_blocks=vol.check()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="256,512")
@@ -99,6 +164,8 @@ def main():
     ap.add_argument("--views", type=int, default=20)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--store", default="dense", choices=tsdf.STORES)
+    ap.add_argument("--grow", default="1,2", help="--store sparse: logical box sides, in multiples of the cube's")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     lines = [f"# tools/bench_tsdf.py: {a.frames} frames ({a.views} views cycled) of {W} x {H}; per-launch: a HIP event pair around "
@@ -126,6 +193,10 @@ def main():
     for dims in [int(x) for x in a.dims.split(",")]:
         vl = 2 * HALF / dims
         trunc = 2 * vl
+        if a.store == "sparse":
+            for grow in [int(x) for x in a.grow.split(",")]:
+                bench_sparse(a, emit, dev, K, poses, depths, rgbs, order, dims, grow)
+            continue
         box = dict(voxel_length=vl, sdf_trunc=trunc, origin=(-HALF, -HALF, -HALF), dims=(dims,) * 3, device=dev)
         vol = tsdf.TSDFVolume(**box)
         lib_args = (float(vol.origin[0]), float(vol.origin[1]), float(vol.origin[2]), vol.voxel_length, vol.sdf_trunc) + vol.blocks
