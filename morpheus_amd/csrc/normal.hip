@@ -76,8 +76,9 @@ __global__ __launch_bounds__(256) void fd_normal_kernel(const float *__restrict_
     const float inv_eps = 1.0f / eps;
 #pragma unroll
     for (int k = 0; k < 3; k++) r[k] = (0.5f * (sdf6[m * 6 + 2 * k] - sdf6[m * 6 + 2 * k + 1])) * inv_eps;
-    const float ss = fmaxf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2], 1e-20f);
-    const float len = sqrtf(ss);
+    // clamp(min) as torch does it: a NaN stays a NaN (fmaxf would drop it and hand the other two components a length of 1e-10)
+    const float ss0 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    const float len = sqrtf(ss0 < 1e-20f ? 1e-20f : ss0);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         raw[m * 3 + k] = r[k];
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void fd_normal_bwd_kernel(const float *__restr
     if (g_normal) {
         const float ss0 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
         const bool clamped = !(ss0 >= 1e-20f);                          // clamp(min): no gradient to ss when ss < min
-        const float len = sqrtf(fmaxf(ss0, 1e-20f));
+        const float len = sqrtf(ss0 < 1e-20f ? 1e-20f : ss0);
         float gn[3], dot = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
@@ -235,7 +236,7 @@ __device__ __forceinline__ SdfLossTerm sdf_loss_term(float z, float target, floa
     const float a = expf(-5.0f * p) - 1.0f, b = p - bnd;
     const float mx = fmaxf(a, b);
     const float dmx = (a > b) ? (-5.0f * expf(-5.0f * p)) : ((a < b) ? 1.0f : 0.5f * (1.0f - 5.0f * expf(-5.0f * p)));
-    const bool pos = mx > 0.0f;
+    const bool pos = mx >= 0.0f;                                        // clamp(min = 0) passes its gradient AT 0 too (p == 0 in free space)
     o.fs = front ? (pos ? mx : 0.0f) / n : 0.0f;
     o.dfs = (front && pos) ? dmx / n : 0.0f;
     const float d = p - bnd;
