@@ -365,13 +365,11 @@ __global__ __launch_bounds__(256) void bin_colscan_kernel(int32_t *__restrict__ 
 // single block: exclusive scans over the NBRK+1 brick totals -> brick_start[NBRK+2], and over the
 // per-brick work-item counts ceil(cnt/chunk) -> work_start[NBRK+1] (stored behind brick_start)
 // points per work item.  Every item flushes its brick's touched vertices -- ~9000 global float atomics whatever its size, a
-// fifth of the staged backward at cfg3 (-DBRK_EXP_NOFLUSH: 1.16 -> 0.94 ms) -- so large calls take larger items (cfg3: 1.16 ->
+// fifth of the staged backward at cfg3 (with the flush taken out: 1.16 -> 0.94 ms, profiles/r05_ab_hashgrid.txt) -- so large calls take larger items (cfg3: 1.16 ->
 // 1.08 ms, the binned forward 0.36 -> 0.34); the small calls of a training step lose balance with them (real-view step 0.78 ->
 // 0.92 ms at 2048, 1.15 at 4096).  The binning writes its choice behind the work-item table; the kernels read it there.
 #define BRK_CHUNK_SMALL 1024
-#ifndef BRK_CHUNK_LARGE
-#define BRK_CHUNK_LARGE 2048
-#endif
+constexpr int BRK_CHUNK_LARGE = 2048;
 #define BRK_CHUNK_WORD (2 * NBRK + 5)
 __global__ __launch_bounds__(1024) void bin_rowscan_kernel(const int32_t *__restrict__ brick_cnt,
                                                            int32_t *__restrict__ brick_start, int chunk) {
@@ -467,8 +465,7 @@ __device__ __forceinline__ void fx_scales(uint32_t maxbits, float &to_fx, float 
 
 // Workgroup = BRK_THREADS = 1024 lanes: 64 points x 16 levels in flight per iteration, 16 waves sharing one accumulator.
 //
-// Round-5 timing experiments on the d/dx form (2 tables at cfg3, same box; the wrong-result variants live in
-// tools/micro/hashgrid_brk_exp.patch, applied to a copy by tools/build_grid_variants.sh exp:NAME -- never in this file):
+// Round-5 timing experiments on the d/dx form (2 tables at cfg3, same box; the wrong-result variants were never in this file):
 //   as shipped in round 4 1.38 ms | VALU stream cut by 40 % (DPP sums, branch-free rows, contracted d/dx) 1.32 | LDS atomics
 //   removed 1.21 | the eight table-row gathers of d/dx sent to ONE row 0.86 | both 0.76.
 // Neither the instruction stream nor the LDS atomic pipe nor load latency (operands requested an iteration ahead: no gain) was
@@ -480,21 +477,11 @@ __device__ __forceinline__ void fx_scales(uint32_t maxbits, float &to_fx, float 
 // CU (4 waves per SIMD, 128 registers), which pays for requesting the next point's operands an iteration ahead.
 // (DESIGN.md section 3 "The hash grid" has the whole table; profiles/r05_ab_hashgrid.txt the final kernels' run of it.)
 #define BRK_THREADS 1024
-#ifndef BRK_PIPE
-#define BRK_PIPE 2             // A/B: 0 = every operand requested in the iteration that uses it, 1 = the index one iteration ahead, 2 = index two ahead, x / grad one
-#endif
-#ifndef BRK_STAGE
-#define BRK_STAGE 1            // A/B: 0 = the d/dx forms gather their table rows from global memory (two workgroups per CU)
-#endif
-#ifndef BRK_STAGE_UNROLL
-#define BRK_STAGE_UNROLL 8     // staging gathers in flight per lane
-#endif
-#ifndef BRK_STAGE_MIN_POINTS
-#define BRK_STAGE_MIN_POINTS (1 << 20)
-#endif
-#ifndef BRK_STAGE_MIN
-#define BRK_STAGE_MIN 96       // a work item with fewer points gathers its rows directly (staging = 4558 gathers, ~36 points' worth, at half the occupancy)
-#endif
+constexpr int BRK_PIPE = 2;             // 0 = every operand requested in the iteration that uses it, 2 = the index two iterations ahead, x / grad one
+constexpr int BRK_STAGE = 1;            // 0 = the d/dx forms always gather their table rows from global memory (two workgroups per CU)
+constexpr int BRK_STAGE_UNROLL = 8;     // staging gathers in flight per lane
+constexpr int BRK_STAGE_MIN_POINTS = 1 << 20;      // initial value of mh_grid_stage_min_points
+constexpr int BRK_STAGE_MIN = 96;       // a work item with fewer points gathers its rows directly (staging = 4558 gathers, ~36 points' worth, at half the occupancy)
 
 // j / d for 0 <= j < 4608, 1 <= d <= 16 (a level's vertex block fits BRK_NODES_MAX: <= 16 vertices per axis): one multiply and a
 // shift, m = ceil(2^16 / d) -- checked exhaustively over that range
@@ -710,8 +697,8 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     int p_cur = 0, p_nxt = 0;
     float xv[3] = {0.f, 0.f, 0.f};
     float2 gr = make_float2(0.f, 0.f);
-    if (PIPE >= 1) p_cur = perm[min(start + sub, last)];
     if (PIPE == 2) {
+        p_cur = perm[min(start + sub, last)];
         p_nxt = perm[min(start + sub + PPI, last)];
 #pragma unroll
         for (int d = 0; d < 3; d++) xv[d] = x[(int64_t)p_cur * 3 + d];
@@ -731,7 +718,6 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
             for (int d = 0; d < 3; d++) xn[d] = x[(int64_t)p_nxt * 3 + d];
             grn = grad[(int64_t)p_nxt * L + l];
         } else {
-            if (PIPE == 1) p_nxt = perm[min(i + PPI, last)];
 #pragma unroll
             for (int d = 0; d < 3; d++) xv[d] = x[p * 3 + d];
             gr = grad[p * L + l];
@@ -800,8 +786,6 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
         if (PIPE == 2) {
             p_cur = p_nxt, p_nxt = p_nn;
             xv[0] = xn[0], xv[1] = xn[1], xv[2] = xn[2], gr = grn;
-        } else if (PIPE == 1) {
-            p_cur = p_nxt;
         }
     }
     __syncthreads();

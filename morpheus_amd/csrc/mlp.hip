@@ -614,9 +614,6 @@ __device__ __forceinline__ const float *acc_add_lds(f32x16 (&a)[N], const float 
 }
 
 // ---- the same two primitives with exact fp32 products on the bf16 matrix pipe (mlp_b3.hip's arithmetic) -------------------
-#ifndef FUSED_FILL
-#define FUSED_FILL 0        // measured round 5: 4 fillers per MFMA made the fused backward SLOWER (1.78 -> 1.84-1.93 ms: 6 more spilled registers in the sdf launch)
-#endif
 // weights: [plane hi|mid|lo][out tile][k16 step][lane][8 bf16] (packing.py: bwd3 blocks of the field packer); `bin` holds what
 // the fp32 chain carries per 2-wide k-step, so k16 step s takes bin[8s .. 8s+7]
 // S_RUN < KS / 8: the caller knows that bin[8 S_RUN ..] is all zeros (the short last layers: dP2 = [d geo | d sdf | zeros], dQ2 = three
@@ -653,15 +650,8 @@ __device__ __forceinline__ void mfma_layer_z_b3(const f32x4 *__restrict__ w, con
 #pragma unroll
         for (int t = 0; t < MT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bh.h, acc[t], 0, 0, 0);
     }
-    // round 5: step s + 1's slicing (44 VALU) rides in the shadow of step s's 6 MT MFMAs instead of running between them
-    // (tools/micro/mfma_valu_gap.hip: 5-6 single-issue instructions per MFMA gap are free inside a wave; this kernel is one wave per SIMD)
-#if FUSED_FILL > 0
-#pragma unroll
-    for (int g_ = 0; g_ < S_RUN * 6 * MT; g_++) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, FUSED_FILL, 0);
-    }
-#endif
+    // no scheduling groups here or in dw_mma_b3: asking for step s + 1's slicing (44 VALU) in the shadow of step s's MFMAs, 4 VALU per
+    // MFMA, made the fused backward slower (round 5: 1.78 -> 1.84-1.93 ms, 6 more spilled registers in the sdf launch)
 }
 
 // ONE k16 step `s` of a layer of S steps, accumulators = that step's products alone (every other step's B operand is zero)
@@ -720,13 +710,6 @@ __device__ __forceinline__ void dw_mma_b3(const RowFrag &a, const RowSl *__restr
 #pragma unroll
         for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[n].h[s].h, acc[n], 0, 0, 0);
     }
-#if FUSED_FILL > 0
-#pragma unroll
-    for (int g_ = 0; g_ < 12 * NI; g_++) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, FUSED_FILL, 0);
-    }
-#endif
 }
 // arithmetic selector of the fused kernels (B3 is their template parameter): LAYER(KS, MT, w, bin, acc); SLICE(N, B, Bs) after the
 // parked rows landed; DW(NI, A, B, Bs, acc, bsum)
@@ -1544,30 +1527,18 @@ struct WgRaw {
 };
 __device__ __forceinline__ void wg_raw_load(WgRaw &f, const float *__restrict__ a, const float *__restrict__ b) {
     const f32x4 *a4 = reinterpret_cast<const f32x4 *>(a), *b4 = reinterpret_cast<const f32x4 *>(b);
-#ifdef WG_NT_LOADS   // A/B, measured: weight gradients 4.2 -> 6.6 ms.  Every parked row is read once by one wave, but a lane takes
-                     // its 64 bytes of a row as four consecutive dwordx4 loads, i.e. an instruction touches 32 bytes of each of 32
-                     // lines and the other three find the line in the cache -- which a non-temporal load does not leave there.
-                     // (A streaming read gains 10 % from nt, tools/micro/hbm_read.hip; using it here needs lane-linear loads,
-                     // i.e. the A operand through LDS as well.)
-#pragma unroll
-    for (int j = 0; j < 4; j++) f.a[j] = __builtin_nontemporal_load(a4 + j);
-#pragma unroll
-    for (int j = 0; j < 4; j++) f.b[j] = __builtin_nontemporal_load(b4 + j);
-#else
+    // plain loads, not non-temporal ones (measured: weight gradients 4.2 -> 6.6 ms): a lane takes its 64 bytes of a row as four
+    // consecutive dwordx4 loads, and the last three find the line in the cache only if the first one left it there
 #pragma unroll
     for (int j = 0; j < 4; j++) f.a[j] = a4[j];
 #pragma unroll
     for (int j = 0; j < 4; j++) f.b[j] = b4[j];
-#endif
 }
 // measured on cfg3 (warp group, same box): 4 sets / one workgroup per CU 5.28 ms, 5 sets 5.25, 3 sets / TWO workgroups per CU
 // (240 registers, 2 x 48 KB of LDS: the second workgroup's MFMAs fill the first one's slicing and barrier time) 4.95
-#ifndef WG_REG_SETS
-#define WG_REG_SETS 3
-#endif
-#ifndef WG_REG_WAVES
-#define WG_REG_WAVES 2        // waves per SIMD the register budget is sized for = workgroups per CU
-#endif
+constexpr int WG_REG_SETS = 3;
+constexpr int WG_REG_WAVES = 2;      // waves per SIMD the register budget is sized for = workgroups per CU
+constexpr int WG_FILL = 4;           // slicing instructions asked for behind each MFMA of WG_STEP_FAST (0, 3, 4, 5 measured alike: profiles/r05_ab_fill_counts.txt)
 template <int IT>
 __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ acts, const float *__restrict__ dpre,
                                                    int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off, int dpre_off,
@@ -1647,9 +1618,6 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
     // Round 5 (tools/micro/mfma_valu_gap.hip): up to 5-6 single-issue instructions ride free in the 32-cycle shadow of a bf16 MFMA
     // *of the same wave*; the step used to run its 48 MFMAs and then its ~200 slicing instructions back to back and left the
     // overlap to whatever the SIMD's other wave happened to be doing.
-#ifndef WG_FILL
-#define WG_FILL 4
-#endif
 #define WG_STEP_FAST(J)                                                                     \
     do {                                                                                    \
         __syncthreads();                                                                    \
@@ -1658,11 +1626,9 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
         __builtin_amdgcn_sched_barrier(0);                                                  \
         WG_MMA((J) & 1);                                                                    \
         WG_SPLIT(((J) + 1) % NS, ((J) + 1) & 1, true);                                      \
-        if (WG_FILL > 0) {                                                                  \
-            _Pragma("unroll") for (int g_ = 0; g_ < 12 * IT; g_++) {                        \
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-                __builtin_amdgcn_sched_group_barrier(0x002, WG_FILL, 0);                    \
-            }                                                                               \
+        _Pragma("unroll") for (int g_ = 0; g_ < 12 * IT; g_++) {                            \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                              \
+            __builtin_amdgcn_sched_group_barrier(0x002, WG_FILL, 0);                        \
         }                                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                  \
     } while (0)
@@ -1673,6 +1639,7 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
         WG_SPLIT(0, 0, true);
         // the set index has period NS, the slice / B-buffer parity period 2: one loop trip = lcm(NS, 2) steps
         constexpr int TRIP = (NS % 2 ? 2 * NS : NS);
+        static_assert(TRIP == 6, "the loops below spell out six steps per trip");
         int64_t k0 = 0;
         if (IT == 4) {           // (4 waves = 4 activation blocks: every wave publishes, `mt < IT` folds away)
             for (; k0 + TRIP < n_my; k0 += TRIP) {      // every step's tile AND its successor are real
@@ -1680,16 +1647,8 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
                 WG_STEP_FAST(1);
                 WG_STEP_FAST(2);
                 WG_STEP_FAST(3);
-                if (TRIP > 4) {
-                    WG_STEP_FAST(4);
-                    WG_STEP_FAST(5);
-                }
-                if (TRIP > 6) {
-                    WG_STEP_FAST(6);
-                    WG_STEP_FAST(7);
-                    WG_STEP_FAST(8);
-                    WG_STEP_FAST(9);
-                }
+                WG_STEP_FAST(4);
+                WG_STEP_FAST(5);
             }
         }
         for (; k0 < n_my; k0 += TRIP) {
@@ -1697,16 +1656,8 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
             WG_STEP(1);
             WG_STEP(2);
             WG_STEP(3);
-            if ((NS % 2 ? 2 * NS : NS) > 4) {
-                WG_STEP(4);
-                WG_STEP(5);
-            }
-            if ((NS % 2 ? 2 * NS : NS) > 6) {
-                WG_STEP(6);
-                WG_STEP(7);
-                WG_STEP(8);
-                WG_STEP(9);
-            }
+            WG_STEP(4);
+            WG_STEP(5);
         }
     }
 #undef WG_STEP
@@ -2099,9 +2050,7 @@ extern "C" int mh_field_fwd(const float *xc, const float *feat_s, const float *f
 }
 
 #define WG_PER_LAYER_TILES 16384      // from this many 32-point tiles on: one launch per layer, large-batch kernels
-#ifndef WG_MERGED_REGS_TILES
-#define WG_MERGED_REGS_TILES 256      // from this many tiles on (below the line above): the merged launch uses the slice-once body
-#endif
+constexpr int WG_MERGED_REGS_TILES = 256;      // from this many tiles on (below the line above): the merged launch uses the slice-once body
 static inline int wg_chunks(int out_pad, int64_t n_tiles, int n_layers) {
     // 4 waves per CU per launch = exactly one per SIMD (see wgrad_kernel) whatever the number of output tiles
     // large batches (the per-layer launches, from 16 384 tiles on): WG_REG_WAVES workgroups per CU (wgrad_regs_b3_kernel)

@@ -39,9 +39,7 @@
 #define B3_LDS_BYTES (B3_LH_F4 * 16 + 1024)            // one layer's slices + the layer's bias row (forward)
 
 extern __shared__ f32x4 lds_b3[];
-#ifndef B3_Q4_FILL
-#define B3_Q4_FILL 6
-#endif
+constexpr int B3_Q4_FILL = 6;      // epilogue instructions asked for behind each MFMA of the backward's fourth quarter
 // Parking stores a wave issues per epilogue EIGHTH (8 accumulator registers of one tile: one global_store_dword each) and per
 // epilogue HALF (two tiles = four eighths).  The vmcnt(KEEP) waits below are only right if at least KEEP such stores sit between
 // the LDS-DMA they wait for and the wait itself: KEEP is DERIVED from these counts, never chosen (round-5 advisor finding: a -D
@@ -277,9 +275,7 @@ __device__ __forceinline__ void b3_epilogue_half(f32x16 (&acc)[4], float *__rest
 // branch -- a branch ends the scheduling region the epilogue instructions are meant to share with the MFMAs.
 #define B3_SLOT_F4 B3_KH_F4                             // 3072 float4 = 48 KB; L0 (2560) and L5 (1536) fit one slot
 #define B3_BIASROW_F4 (2 * B3_SLOT_F4)                  // two bias rows of 32 float4 behind the slots (row = layer & 1)
-#ifndef B3_Q_FILL
-#define B3_Q_FILL 6
-#endif
+constexpr int B3_Q_FILL = 6;      // the forward prefers 6 (3.64-3.67 ms) to 4-5 (3.71-3.72) and 8 (3.78): profiles/r05_ab_fill_counts.txt
 
 // wave-uniform source offset / slot -> LDS-DMA of N_F4 float4.  The offset passes through an empty asm statement: the address
 // arithmetic is loop-invariant for most blocks, and hipcc otherwise hoists it out of the layer loop and spills it
@@ -411,13 +407,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #pragma unroll
     for (int k = 20; k < 24; k++) bin0[k] = 0.f;
     if (PARK) {
-#if defined(MH_PARK_PAD_ROWS) || defined(MH_PARK_H0_PAD)   // A/B (tools/gpu/r6_pad_ab.sh): the round-5 form, pad rows written (and, with MORPHEUS_WGRAD_LIVE=0, read)
+        // k-step ordered; the pad rows 40..63 are neither written nor read (wg_row; profiles/r06_ab_pad_rows.txt)
 #pragma unroll
-        for (int k = 0; k < 32; k++) tile[(2 * k + h) * TILE + pt] = k < 20 ? bin0[k] : 0.f;
-#else
-#pragma unroll
-        for (int k = 0; k < 20; k++) tile[(2 * k + h) * TILE + pt] = bin0[k];  // k-step ordered; the pad rows 40..63 are never read (wg_row)
-#endif
+        for (int k = 0; k < 20; k++) tile[(2 * k + h) * TILE + pt] = bin0[k];
     }
     uint2 *mk = PARK ? reinterpret_cast<uint2 *>(tile + WARP_HID_ROWS * TILE) : nullptr;
 
@@ -582,11 +574,6 @@ __device__ __forceinline__ void b3_epilogue_bwd_eighth(f32x16 (&acc)[4], uint2 m
 #pragma unroll
     for (int e2 = 0; e2 < 4; e2++)
         split2(acc[t][8 * s2 + 2 * e2], acc[t][8 * s2 + 2 * e2 + 1], bh[2 * t + s2].u[e2], bm[2 * t + s2].u[e2], bl[2 * t + s2].u[e2]);
-#ifdef B3_Q4_CHUNKS
-    Frag &fh = bh[2 * t + s2], &fm = bm[2 * t + s2], &fl = bl[2 * t + s2];
-    asm volatile("" : "+v"(fh.u[0]), "+v"(fh.u[1]), "+v"(fh.u[2]), "+v"(fh.u[3]), "+v"(fm.u[0]), "+v"(fm.u[1]), "+v"(fm.u[2]),
-                 "+v"(fm.u[3]), "+v"(fl.u[0]), "+v"(fl.u[1]), "+v"(fl.u[2]), "+v"(fl.u[3]));
-#endif
 }
 
 // PARK4 = false (round 6): dPre4 is not parked -- the layer-4 weight-gradient launch regenerates it (mlp.hip: wgrad_regen_b3_kernel)
@@ -629,14 +616,10 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
             if (nout == 3) d5[2] = g[p * nout + 2];
         }
         // dPre5's live rows only (0..nout-1 <= 3: registers 0..3 of the lower half; mh_mlp_wgrad reads no row behind them, wg_row)
-#ifdef MH_PARK_PAD_ROWS
-        store_acc_rows<1>(dt + 640 * TILE, d5, pt, h);
-#else
         if (h == 0) {
 #pragma unroll
             for (int r = 0; r < 4; r++) dt[(640 + r) * TILE + pt] = d5[r];
         }
-#endif
         Frag bh[8], bm[8], bl[8];
 #pragma unroll
         for (int s = 0; s < 2; s++)
@@ -664,14 +647,6 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
             b3_quarter<2, 0>(lds_b3, bh, bm, bl, acc, lane);
             b3_quarter<0, 4>(lds_b3, bh, bm, bl, acc, lane);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef B3_Q4_CHUNKS
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                b3_quarter_step<2>(lds_b3, bh, bm, bl, acc, lane, 4 + c);
-                b3_epilogue_bwd_eighth(acc, msk[l - 1], dt + (l - 1) * 128 * TILE, pt, h, bh, bm, bl, c >> 1, c & 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#else
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 b3_quarter_step<2>(lds_b3, bh, bm, bl, acc, lane, 4 + c);
@@ -684,7 +659,6 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
                 __builtin_amdgcn_sched_group_barrier(0x002, B3_Q4_FILL, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-#endif
             __syncthreads();
             wt += B3_LH_F4;
             if (l > 1)

@@ -180,12 +180,8 @@ union Frag {
     uint32_t u[4];
 };
 
-// parked tiles are written once and read much later by another kernel
-#ifdef MH_B3_PLAIN_STORES
-#define PARK_STORE(v, p) (*(p) = (v))
-#else
+// parked tiles are written once and read much later by another kernel: non-temporal stores
 #define PARK_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#endif
 
 // ReLU and the sign-mask bit as compiler-visible integer instructions (one v_max_i32; v_min_u32 + v_lshl_add_u32): the float
 // forms cost an extra canonicalising v_max each, inline-asm forms are invisible to the hazard recognizer (mlp_b3.hip:

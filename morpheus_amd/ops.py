@@ -747,9 +747,6 @@ def sample_positions_nograd(rays_o, rays_d, ray_idx, t_starts, t_ends):
 
 
 # ------------------------------------------------------------------------------------ fused MLPs
-# A/B switch (tools/gpu/r6_pad_ab.sh): 0 = the weight-gradient kernels read every row of the padded tiles (needs a library built with
-# -DMH_PARK_PAD_ROWS, whose forward / backward-data kernels write them)
-WGRAD_LIVE_ROWS = os.environ.get("MORPHEUS_WGRAD_LIVE", "1") != "0"
 # A/B and test switch: 0 = dPre4 of the warp nets is parked by backward-data and read by the weight gradients (the round-5 form)
 REGEN_DPRE4 = os.environ.get("MORPHEUS_REGEN_DPRE4", "1") != "0"
 
@@ -758,8 +755,6 @@ def _wgrad(lib, acts, dpre, acts_tile, dpre_tile, act_off, dpre_off, in_pad, out
            out_live=None):
     """in_live / out_live: rows of each layer's input / dPre tile that carry values (None: all; include/morpheus_hip.h)"""
     n_layers = len(act_off)
-    if not WGRAD_LIVE_ROWS:
-        in_live = out_live = None
     il_p = None if in_live is None else _i32arr(in_live)[1]
     ol_p = None if out_live is None else _i32arr(out_live)[1]
     dw_len = int(sum(i * o for i, o in zip(in_pad, out_pad)))

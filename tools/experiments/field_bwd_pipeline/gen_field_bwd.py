@@ -5,7 +5,7 @@ at C++ STATEMENT granularity.
 Why a generator.  The kernels run ONE wave per SIMD (160-192 accumulator registers), so nothing hides a vector instruction but the
 wave's own MFMAs: 5-6 single-issue instructions per v_mfma_f32_32x32x16_bf16 are free (tools/micro/mfma_valu_gap.hip), the rest is
 paid in full.  hipcc's scheduler does not produce that interleave for these kernels: sched_group_barrier pipelines are dropped in the
-register-tight regions (the schedule reverts to source order: round 5's FUSED_FILL experiment, round 6's first two forms of this
+register-tight regions (the schedule reverts to source order: round 5's fill experiment in mlp.hip's b3 primitives, round 6's first two forms of this
 kernel -- 80 and 357 spilled registers).  So the SOURCE ORDER is made the schedule: every MFMA is followed by the few statements
 that ride in its shadow and a full scheduling barrier (__builtin_amdgcn_sched_barrier(0)), and which statements go where is decided
 here, by a list scheduler over the tile's statement DAG:

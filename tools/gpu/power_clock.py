@@ -8,7 +8,7 @@ launched ALONE in a loop for --seconds (cfg3's call: 2 097 152 points, random we
 and, every 50 ms through the amdsmi library when it imports, the gpu_metrics record (average_socket_power, the per-XCD gfx clocks,
 gfx activity).  Beside them the bare streams of tools/micro/mfma_bf16_rate (built on the box): the matrix pipe with nothing else.
 Printed per kernel: ms per launch (HIP events over the loop), mean / p95 socket power, mean sclk, the board's power cap.
-The effective clock GRBM_GUI_ACTIVE / duration per kernel comes from a rocprofv3 --pmc pass over `--once` (tools/gpu/r6_power.sh).
+The effective clock GRBM_GUI_ACTIVE / duration per kernel comes from a rocprofv3 --pmc pass over `--once`.
 
     python tools/gpu/power_clock.py [--seconds 2.0] [--once] > profiles/r06_power_clock.txt
 """
