@@ -126,6 +126,10 @@ int mh_composite_bwd(const float *sigma, const float *t_starts, const float *t_e
 int mh_generate_rays(float fx, float fy, float cx, float cy, const float *c2w_host, int32_t H, int32_t W,
                      float *rays_o, float *rays_d, void *stream);
 /* AABB slab clip to [-bound,bound]^3, S bins of (t_far-t_near)/(S+1), comb shifted by jitter*dt.
+ * A ray is a MISS -- S zero-width samples at t = 0 here, no samples in the marcher below -- when the clipped segment is empty
+ * (t_far <= t_near, t_near >= 0), when any of its six slab quotients (+-bound - o[a]) / d[a] is NaN (a NaN origin or direction
+ * component; 0/0: a ray lying in a face plane), or when the clipped t_near / t_far is not finite (d = 0 inside the box).  The
+ * NaN is not dropped the way fmaxf / fminf alone would drop it.  Every finite ray that hits is clipped as before.
  * Outputs (length N*S, ray-major): ray_idx int32, t_starts, t_ends, xyz [N*S,3] = o + d*(ts+te)/2;
  * and ray_start/ray_cnt [N] int32. */
 int mh_sample_uniform(const float *rays_o, const float *rays_d, const float *jitter, int32_t N, int32_t S,
@@ -143,7 +147,8 @@ int mh_rays_sample_uniform(float fx, float fy, float cx, float cy, const float *
 
 /* Occupancy-grid marcher (nerfacc OccGridEstimator.sampling call shape, morpheus.py:628-638): fixed `step`,
  * one jitter per ray (NULL = none), binary grid [R,R,R] uint8 over the AABB [-bound,bound]^3.  Interval k of a ray:
- * ts = t_near + u*step + k*step, te = min(ts+step, t_far), kept iff the cell of its midpoint is occupied.
+ * ts = t_near + u*step + k*step, te = min(ts+step, t_far), kept iff the cell of its midpoint is occupied.  A miss (the rule
+ * stated at mh_sample_uniform) has no interval: ray_cnt = 0, and it never sets *overflow.
  * One wavefront per ray (64 steps per iteration, ballot/popcount compaction), single pass:
  * mh_march_slots writes ray_cnt [N] and the kept intervals of ray r to slot_ts/slot_te [r*cap .. r*cap+cnt), cap >=
  * mh_march_cap(step, bound) (steps on the AABB diagonal for unit-or-longer directions); *overflow (device int, zeroed by

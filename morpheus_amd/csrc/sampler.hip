@@ -5,7 +5,8 @@
 // Sampler: replaces the nerfacc OccGridEstimator.sampling call site (morpheus.py:628-638) with the
 // benchmark sampler of SURVEY 8(d); definition shared with oracle/field.py:uniform_samples:
 //   slab clip to [-bound,bound]^3 -> [t_near>=0, t_far];  dt = (t_far - t_near) / (S+1);
-//   ts_i = t_near + (i + u) * dt;  te_i = t_near + (i + 1 + u) * dt;   misses -> zero-width samples.
+//   ts_i = t_near + (i + u) * dt;  te_i = t_near + (i + 1 + u) * dt;   misses -> zero-width samples at t = 0.
+//   A miss: empty clip, a NaN slab quotient, or a non-finite clipped t_near / t_far (slab_clip below).
 // Arithmetic is un-contracted round-to-nearest mul/add/div (no FMA) so the packed
 // samples are bit-identical to the oracle's -- samples are *inputs* to every parity test.
 #include "common.h"
@@ -48,22 +49,37 @@ __global__ __launch_bounds__(256) void generate_rays_kernel(float fx, float fy, 
     }
 }
 
-// slab clip + the i-th stratified interval of one ray (shared by the two uniform-sampler kernels)
-__device__ __forceinline__ void uniform_interval(const float *o, const float *d, float bound, int S, int i, float u,
-                                                 float *ts, float *te) {
+// Slab clip of one ray to the AABB [-bound,bound]^3 -> [*t_near >= 0, *t_far]; a MISS gives t_near = t_far = 0.
+// A ray is a miss when the clipped segment is empty, when one of its six slab quotients is NaN (fmaxf / fminf would drop
+// the NaN and clip on the remaining axes; the oracle's minimum / maximum propagate it) or when the clipped t_far is not
+// finite (d = 0 inside the box: nothing bounds the walk).  For every finite ray that hits, the operations and their order
+// are the ones this file always had.  Shared by the two uniform-sampler kernels and the marcher.
+__device__ __forceinline__ void slab_clip(const float *o, const float *d, float bound, float *t_near, float *t_far) {
     float tmin = -INFINITY, tmax = INFINITY;
+    bool nan = false;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         const float ta = (-bound - o[a]) / d[a];
         const float tb = (bound - o[a]) / d[a];
+        nan = nan || ta != ta || tb != tb;
         tmin = fmaxf(tmin, fminf(ta, tb));
         tmax = fminf(tmax, fmaxf(ta, tb));
     }
     tmin = fmaxf(tmin, 0.0f);
-    if (!(tmax > tmin)) {
+    // tmax > tmin >= 0 leaves +inf as the only non-finite t_far; a non-finite t_near never passes tmax > tmin
+    if (nan || !(tmax > tmin) || !(tmax < INFINITY)) {
         tmin = 0.f;
         tmax = 0.f;
     }
+    *t_near = tmin;
+    *t_far = tmax;
+}
+
+// the i-th stratified interval of one ray (shared by the two uniform-sampler kernels)
+__device__ __forceinline__ void uniform_interval(const float *o, const float *d, float bound, int S, int i, float u,
+                                                 float *ts, float *te) {
+    float tmin, tmax;
+    slab_clip(o, d, bound, &tmin, &tmax);
     const float dt = (tmax - tmin) / (float)(S + 1);
     *ts = tmin + ((float)i + u) * dt;
     *te = tmin + (((float)i + 1.0f) + u) * dt;
@@ -148,7 +164,7 @@ __global__ __launch_bounds__(256) void rays_sample_uniform_kernel(float fx, floa
 // tree, so the interval placement is defined here (and mirrored by oracle/field.py:march_samples):
 //   [t_near, t_far] = slab clip to the AABB, t_near >= 0;   t0 = t_near + u * step;
 //   interval k: ts = t0 + k*step, te = min(ts + step, t_far), kept while ts < t_far and only if the grid cell
-//   containing the interval's midpoint is occupied.
+//   containing the interval's midpoint is occupied.  A miss (slab_clip: empty clip, NaN quotient, non-finite t_far) has no interval.
 // The packed layout is ragged: march into per-ray slot rows, scan the counts, pack (march_wave_kernel, march_pack_kernel).
 struct MarchRay {
     float o[3], d[3];
@@ -158,21 +174,13 @@ struct MarchRay {
 __device__ __forceinline__ MarchRay march_setup(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                 const float *__restrict__ jitter, int r, float step, float bound) {
     MarchRay m;
-    float tmin = -INFINITY, tmax = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         m.o[a] = rays_o[r * 3 + a];
         m.d[a] = rays_d[r * 3 + a];
-        const float ta = (-bound - m.o[a]) / m.d[a];
-        const float tb = (bound - m.o[a]) / m.d[a];
-        tmin = fmaxf(tmin, fminf(ta, tb));
-        tmax = fminf(tmax, fmaxf(ta, tb));
     }
-    tmin = fmaxf(tmin, 0.0f);
-    if (!(tmax > tmin)) {
-        tmin = 0.f;
-        tmax = 0.f;
-    }
+    float tmin, tmax;
+    slab_clip(m.o, m.d, bound, &tmin, &tmax);
     m.t0 = tmin + (jitter ? jitter[r] : 0.0f) * step;
     m.tfar = tmax;
     return m;

@@ -458,12 +458,18 @@ def march_rays(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.
 
 def march_count(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor) -> torch.Tensor:
     """Total number of samples the marcher would emit for these rays, as a 0-dim int32 DEVICE tensor (no host sync): lets a
-    caller size / pick a fixed-capacity buffer ahead of the step (trainstep.GraphedRealViewStep)."""
+    caller size / pick a fixed-capacity buffer ahead of the step (trainstep.GraphedRealViewStep).
+    One march at the slot-row length mh_march_cap gives and no retry: the overflow flag is not read, so for a batch with a ray
+    that overflows its slot row (directions much shorter than unit length -- march_rays marches such a batch again) the result
+    is a LOWER BOUND of march_rays' total, each overflowing ray counted at the slot-row length at most."""
     require_gpu(rays_o, rays_d, jitter, binary)
     lib = _lib.load()
     o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
     j = _ray_jitter(jitter, rays_o.shape[0])
+    assert binary.dtype == torch.uint8 and binary.is_contiguous() and binary.dim() == 3
     N, R, dev = o.shape[0], binary.shape[0], o.device
+    if N == 0:
+        return torch.zeros((), dtype=torch.int32, device=dev)
     cap = int(lib.mh_march_cap(float(step), float(bound)))
     cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
     slots = torch.empty(2, N, cap, device=dev)
@@ -476,7 +482,8 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     """The same marcher with a FIXED packed length and no device->host sync, so that a training step has constant shapes and
     can be captured in a HIP graph: -> (ray_idx int32 [capacity], t_starts, t_ends [capacity], ray_start [N], ray_cnt [N],
     n_valid int32 0-dim, overflow int32 0-dim).  The first n_valid entries are the packed samples (identical to march_rays');
-    the rest is padding (ray 0, t = 0) that no ray owns: ray_cnt is clamped so that start + cnt never passes `capacity`.
+    the rest is padding (ray 0, t = 0) that no ray owns: ray_cnt and ray_start are clamped so that start + cnt never passes
+    `capacity` (a ray behind the cut has start = capacity, cnt = 0: ray_start stays the exclusive scan of ray_cnt).
     overflow != 0: the batch had more samples than `capacity` (the tail rays were truncated) or a ray overflowed its slot
     row -- the caller re-captures with a larger capacity."""
     require_gpu(rays_o, rays_d, jitter, binary)
@@ -493,9 +500,9 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     _timed("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt), ptr(slots[0]),
            ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
     csum = torch.cumsum(cnt, 0, dtype=torch.int32)
-    start = (csum - cnt).contiguous()
+    start = (csum - cnt).clamp_(max=capacity)
     total = csum[N - 1]
-    cnt_c = torch.minimum(cnt, (capacity - start).clamp(min=0)).contiguous()
+    cnt_c = torch.minimum(cnt, capacity - start)
     n_valid = total.clamp(max=capacity)
     overflow = ((total > capacity) | (cnt_ovf[N] != 0)).to(torch.int32)
     ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
