@@ -19,6 +19,19 @@ __device__ __forceinline__ float wave_incl_scan(float v, int lane) {
     return v;
 }
 
+// Exclusive prefix from the inclusive one.  `incl - v` returns the prefix with an absolute error of ulp(incl) / 2, which the weight
+// takes as a relative error.  While the sample's own v = sigma*dt is below 1 that is at most 2^-24 x the transmittance-weighted
+// share of the sample (a prefix large enough to raise ulp(incl) has already taken the weight away), and the subtraction stays, so
+// that results for ordinary densities are bit for bit what they were.  For an opaque sample -- the first one of a ray carries most
+// of the ray's weight -- incl is rounded at ulp(v): 4e-6 of the weight at v = 100, 5e-4 at 1e4, and inf - inf = NaN at
+// sigma = +inf, where the definition gives w = T for the sample and 0 behind it.  There the exclusive value is the inclusive value
+// of the lane below, 0 at lane 0, which never contains the sample's own term.
+constexpr float COMPOSITE_OPAQUE_SD = 1.0f;
+__device__ __forceinline__ float wave_excl_from_incl(float incl, float v, int lane) {
+    const float below = __shfl_up(incl, 1);
+    return v >= COMPOSITE_OPAQUE_SD ? (lane ? below : 0.f) : incl - v;
+}
+
 __device__ __forceinline__ float wave_rev_incl_scan(float v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -57,7 +70,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float *__restr
             sd = sigma[i] * (s1 - s0);
         }
         const float incl = wave_incl_scan(sd, lane);
-        const float excl = carry + (incl - sd);
+        const float excl = carry + wave_excl_from_incl(incl, sd, lane);
         // alpha = 1 - exp(-sd) as -expm1(-sd): the subtraction cancels for the thin samples of a ray that only grazes the box
         // (sd ~ 1e-4 keeps 3 digits of 1 - exp); the same function, correct to an ulp of alpha itself
         const float w = on ? expf(-excl) * -expm1f(-sd) : 0.f;
@@ -119,7 +132,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         const int64_t i = start + k;
         const float sd = on ? sigma[i] * (te[i] - ts[i]) : 0.f;
         const float incl = wave_incl_scan(sd, lane);
-        if (on) d_sigma[i] = carry + (incl - sd);
+        const float excl = carry + wave_excl_from_incl(incl, sd, lane);
+        if (on) d_sigma[i] = excl;
         carry += __shfl(incl, 63);
     }
     // pass 2 (reverse): suffix sums of g*w
