@@ -20,10 +20,7 @@ import math
 import torch
 
 from morpheus_amd import synth
-
-U = 2.0 ** -24          # unit round-off of fp32
-F32 = torch.float32
-F64 = torch.float64
+from tests.f64_judge import F32, F64, U, judge_sum, judge_vs_f64      # noqa: F401  (judge_sum: the suites call it from here)
 
 
 def f32_scalar(v) -> float:
@@ -157,50 +154,18 @@ def sdf_losses(pred, ts, te, depth, mask, ri, trunc, dec=None, terms=False):
 
 
 # -------------------------------------------------------------------------------------------------------- the judgement
-def _flat64(t):
-    return torch.as_tensor(t).detach().double().reshape(-1).cpu()
-
-
 def judge(hip, chain, f64, scale, count, what):
     """The rule for everything with a division, sqrt, expf or lerp: errors are |x - f64| / scale (scale: same shape or scalar,
     the element's own magnitude as the caller defines it; where it is 0 the value must be exactly the yardstick's).  The fp32
     torch chain's own error is the measure: the worst HIP element within 3 x the chain's worst, and at most 3 x as many (+ 2)
     elements above the chain's 99.9th percentile.  Where the chain is exact the floor is `count` roundings (count * 2^-24).
-    -> the record the report keeps; raises AssertionError."""
-    h, c, r = _flat64(hip), _flat64(chain), _flat64(f64)
-    s = _flat64(scale).expand_as(r) if torch.as_tensor(scale).numel() > 1 else torch.full_like(r, float(scale))
-    assert h.shape == r.shape == c.shape == s.shape, (what, h.shape, c.shape, r.shape, s.shape)
-    assert bool(torch.isfinite(r).all()) and bool(torch.isfinite(c).all()), f"{what}: the yardstick itself is not finite"
-    assert bool(torch.isfinite(h).all()), f"{what}: non-finite HIP result where the fp32 chain is finite"
-    live = s > 0
-    assert bool((h[~live] == r[~live]).all()), f"{what}: elements of zero scale must be exact"
-    if not bool(live.any()):
-        return dict(worst_hip=0.0, worst_chain=0.0, ratio=0.0, n_above=0)
-    e_h, e_c = (h - r).abs()[live] / s[live], (c - r).abs()[live] / s[live]
+    -> the record the report keeps; raises AssertionError (f64_judge.judge_vs_f64)."""
     floor = count * U
-    worst_h, worst_c = float(e_h.max()), float(e_c.max())
-    thr = max(float(torch.quantile(e_c, 0.999)) if e_c.numel() > 1 else worst_c, floor)
-    n_h, n_c = int((e_h > thr).sum()), int((e_c > thr).sum())
-    rec = dict(worst_hip=worst_h, worst_chain=worst_c, ratio=worst_h / max(worst_c, floor), n_above=n_h)
-    assert worst_h <= max(3.0 * worst_c, floor), \
-        f"{what}: worst error vs float64 {worst_h:.3e} > 3 x the fp32 chain's own {worst_c:.3e} (floor {floor:.2e})"
-    assert n_h <= 3 * n_c + 2, f"{what}: {n_h} elements above {thr:.3e}; the fp32 chain has {n_c}"
-    return rec
-
-
-def judge_sum(hip, f64, abs_sum, count, what, extra=0.0):
-    """The rule for pure sums: |x - f64| <= count * 2^-24 * (the float64 sum of the ABSOLUTE terms) [+ extra], element by
-    element -- not relative to the result.  -> record (ratio = worst error / bound)."""
-    h, r, a = _flat64(hip), _flat64(f64), _flat64(abs_sum)
-    assert h.shape == r.shape == a.shape, (what, h.shape, r.shape, a.shape)
-    assert bool(torch.isfinite(h).all()), f"{what}: non-finite"
-    bound = count * U * a + extra
-    err = (h - r).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f"{what}: sums without terms must be exactly 0"
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    assert ratio <= 1.0, f"{what}: error {ratio:.3f} x the bound of {count} roundings of the absolute sum"
-    return dict(worst_hip=float(err.max()), worst_chain=None, ratio=ratio, n_above=int((err > bound).sum()))
+    f = judge_vs_f64(hip, chain, f64, scale, what, 3.0, floor, 2, percentile=True)
+    if f["n"] == 0:      # nothing live: with count == 0 the ratio below would be 0 / 0
+        return dict(worst_hip=0.0, worst_chain=0.0, ratio=0.0, n_above=0)
+    return dict(worst_hip=f["worst_hip"], worst_chain=f["worst_ref"], ratio=f["worst_hip"] / max(f["worst_ref"], floor),
+                n_above=f["n_hip"])
 
 
 # --------------------------------------------------------------------------------------------------------------- cases

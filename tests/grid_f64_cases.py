@@ -17,6 +17,7 @@ import torch
 from morpheus_amd import synth
 from oracle.hashgrid import effective_levels, level_resolutions, oracle_grid_encode
 from oracle.hashgrid_f64 import grid_table_grad_f64, grid_term_counts
+from tests.f64_judge import within
 
 BOUND = float(np.float32(1.01))       # the same number in fp32 and in double: u = (x + bound) / (2 bound) differs by round-off only
 FACTOR, FLOOR = 3.0, 2.0 ** -22
@@ -143,7 +144,7 @@ def level_metrics(t, t64, offs):
 
 
 def gate(hip, ora):
-    return hip <= max(FACTOR * ora, FLOOR)
+    return within(hip, ora, FACTOR, FLOOR)
 
 
 def check_levels(what, hip, ora, t64, cnt, offs, log=print):

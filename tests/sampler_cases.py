@@ -20,9 +20,9 @@ import torch
 
 from morpheus_amd import synth
 from oracle import field as of
+from tests.f64_judge import U
 
 F = np.float32
-U = 2.0 ** -24                                     # unit round-off of fp32
 BELOW_ONE = float(np.nextafter(F(1), F(0)))        # the largest float below 1: the largest jitter a [0,1) draw can give
 JITTERS = (None, 0.0, BELOW_ONE)                   # None = the NULL pointer of the C ABI (no jitter)
 SENTINEL = -12345.0                                # fills slot buffers: no sample has a negative t

@@ -15,67 +15,29 @@ error against float64 must stay within a fixed factor of the restatement's own w
 Case builders (`*_case`, `*_layout`) place the counts, tails, lanes and values at which the kernels branch;
 tests/test_step_oracle_host.py asserts on the CPU that they do, tests/test_gpu_step_f64.py runs them on the GPU.
 """
-import json
-import os
-
 import numpy as np
 import torch
 
-U = 2.0 ** -24          # unit round-off of fp32
+from tests.f64_judge import F32, F64, U, assert_figures, figures_vs_f64, report
+
 FLOOR_ULPS = 4          # where the restatement happens to be exact a kernel is held to this many roundings of the scale
-F32, F64 = torch.float32, torch.float64
 
 
 # -------------------------------------------------------------------------------------------------------- the judgement
-def _flat64(t):
-    return torch.as_tensor(t).detach().double().reshape(-1).cpu()
-
-
-def errors(x, f64, scale):
-    """|x - f64| / scale over the elements of non-zero scale (scale: the quantity's natural size, same shape as f64), and the
-    elements of zero scale, which must be exact.  -> (errors of the live elements, count of inexact zero-scale elements)"""
-    x, r, s = _flat64(x), _flat64(f64), _flat64(scale)
-    assert x.shape == r.shape == s.shape, (x.shape, r.shape, s.shape)
-    live = s > 0
-    return (x - r).abs()[live] / s[live], int((x[~live] != r[~live]).sum())
-
-
 def judge(hip, ref32, f64, scale, what, factor=2.0, slack=2):
     """The two conditions of tests/util.py:assert_close_vs_f64 at a natural scale instead of the element's own value: the kernel's
     worst error against float64 within `factor` x the fp32 restatement's own worst (or FLOOR_ULPS roundings of the scale, whichever
     is larger), and at most `factor` x as many elements (+ `slack`) above that floor as the restatement has.  Elements of zero
-    scale must equal the yardstick exactly.  Prints the figures, then asserts.  -> the record the report keeps."""
-    r = _flat64(f64)
-    assert bool(torch.isfinite(r).all()) and bool(torch.isfinite(_flat64(ref32)).all()), f"{what}: the yardstick is not finite"
-    assert bool(torch.isfinite(_flat64(hip)).all()), f"{what}: non-finite kernel result where the definition is finite"
-    e_h, bad_h = errors(hip, f64, scale)
-    e_c, bad_c = errors(ref32, f64, scale)
+    scale must equal the yardstick exactly, the restatement's too.  Prints the figures and appends them to the JSON-lines file
+    MORPHEUS_STEP_REPORT names, then asserts (f64_judge: figures_vs_f64, assert_figures).  -> the record the report keeps."""
     tol = FLOOR_ULPS * U
-    worst_h, worst_c = (float(e_h.max()), float(e_c.max())) if e_h.numel() else (0.0, 0.0)
-    n_h, n_c = int((e_h > tol).sum()), int((e_c > tol).sum())
-    rec = dict(what=what, worst_hip=worst_h, worst_ref=worst_c, ratio=(worst_h / worst_c if worst_c > 0 else None), n_hip=n_h,
-               n_ref=n_c, n=int(e_h.numel()), factor=factor)
-    print(f"[step-f64] {what}: kernel {worst_h:.3e}  fp32 restatement {worst_c:.3e}  above {tol:.1e}: {n_h} / {n_c}  of {e_h.numel()}")
-    report(rec)
-    assert bad_c == 0, f"{what}: the restatement is inexact where the scale is 0"
-    assert bad_h == 0, f"{what}: {bad_h} elements of zero scale are not exactly the definition's value"
-    assert worst_h <= max(factor * worst_c, tol), \
-        f"{what}: worst error vs float64 {worst_h:.3e} > {factor:g} x the fp32 restatement's own {worst_c:.3e} (floor {tol:.1e})"
-    assert n_h <= int(factor * n_c) + slack, f"{what}: {n_h} elements above {tol:.1e} vs float64; the restatement has {n_c}"
+    f = figures_vs_f64(hip, ref32, f64, scale, what, tol)
+    rec = dict(what=what, worst_hip=f["worst_hip"], worst_ref=f["worst_ref"], ratio=(f["worst_hip"] / f["worst_ref"] if f["worst_ref"] > 0 else None),
+               n_hip=f["n_hip"], n_ref=f["n_ref"], n=f["n"], factor=factor)
+    print(f"[step-f64] {what}: kernel {f['worst_hip']:.3e}  fp32 restatement {f['worst_ref']:.3e}  above {tol:.1e}: {f['n_hip']} / {f['n_ref']}  of {f['n']}")
+    report("MORPHEUS_STEP_REPORT", rec)
+    assert_figures(f, what, factor, tol, slack, ref_zero_scale_exact=True)
     return rec
-
-
-def report(rec):
-    """append the record to the JSON-lines file MORPHEUS_STEP_REPORT names (nothing is written without it)"""
-    path = os.environ.get("MORPHEUS_STEP_REPORT")
-    if not path:
-        return
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-    except OSError:
-        pass
 
 
 # ============================================================================================================ compositor

@@ -11,13 +11,11 @@ Rules, none of them fitted to a run:
     99.9th percentile (glue_f64_oracle.judge).
 Every test appends {kernel, case, worst_hip, worst_chain, ratio, n_above} to the JSON-lines file that the environment variable
 MORPHEUS_GLUE_REPORT names (nothing is written without it); profiles/r07_glue_f64_report.jsonl is the committed copy of one run."""
-import json
-import os
-
 import pytest
 import torch
 
 from tests import glue_f64_oracle as G
+from tests.f64_judge import report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -25,15 +23,7 @@ F32, F64 = torch.float32, torch.float64
 
 
 def _report(kernel, case, rec):
-    path = os.environ.get("MORPHEUS_GLUE_REPORT")
-    if not path:
-        return
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "a") as f:
-            f.write(json.dumps(dict(kernel=kernel, case=case, **rec)) + "\n")
-    except OSError:
-        pass
+    report("MORPHEUS_GLUE_REPORT", dict(kernel=kernel, case=case, **rec))
 
 
 def _dev(t, dtype=None):

@@ -701,6 +701,8 @@ def test_sdf_losses_kernel_vs_reference_formula():
         assert_close(pg.grad, po.grad, 1e-5, "d/d pred", floor=1e-2 * float(po.grad.abs().max()))
 
 
+# (its own writer, not tests/f64_judge.py:append_jsonl: the fixed path below is named by where the suite is run, not by the project, and
+# stays on the lines it was written on; anything new reports through f64_judge)
 def _report(record):
     """append a measurement record to gpurun_out/precision_report.jsonl (scratch on the GPU box; the judged copy is
     profiles/r03_precision_report.jsonl) -- the numbers DESIGN.md section 4 quotes"""

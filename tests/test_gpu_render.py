@@ -16,6 +16,7 @@ import torch
 
 from morpheus_amd import synth
 from oracle import field as of
+from tests.f64_judge import flat64
 from tests.util import assert_close, assert_close_counted, assert_close_vs_f64, grad_digest_check, load_golden, max_rel
 
 pytestmark = pytest.mark.gpu
@@ -1119,7 +1120,7 @@ def real_view_f64_errors(case, mlp_mode):
     rows = f64_gradient_errors(model, g, case)
 
     def err(x, ref):
-        x, ref = torch.as_tensor(x).double().reshape(-1).cpu(), torch.as_tensor(ref).double().reshape(-1)
+        x, ref = flat64(x), flat64(ref)
         return float((x - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
 
     values = [("loss", loss.detach())] + [(lk, outputs[lk].detach()) for lk in ("sdf_loss", "fs_loss", "loss_code", "loss_normal_perturb",

@@ -38,6 +38,7 @@ import pytest
 import torch
 
 from tests import step_f64_oracle as S
+from tests.f64_judge import flat64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -68,7 +69,7 @@ def _same_bits(a, b):
 def _pool(records, key, hip, ref32, f64, scale):
     h, c, r, s = records.setdefault(key, ([], [], [], []))
     for lst, t in ((h, hip), (c, ref32), (r, f64), (s, scale)):
-        lst.append(torch.as_tensor(t).detach().double().reshape(-1).cpu())
+        lst.append(flat64(t))
 
 
 def _judge_pool(records, prefix):

@@ -8,12 +8,13 @@ import torch
 
 from oracle import field as of
 from tests import step_f64_oracle as S
+from tests.f64_judge import scaled_errors
 
 F32, F64 = torch.float32, torch.float64
 
 
 def _measure(x32, x64, scale):
-    e, bad = S.errors(x32, x64, scale)
+    e, bad = scaled_errors(x32, x64, scale)
     assert bad == 0 and e.numel() > 0
     worst = float(e.max())
     assert np.isfinite(worst) and worst > 0.0, "the restatement's own error must be finite and non-zero"

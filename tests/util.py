@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from morpheus_amd import synth
+from tests.f64_judge import flat64, judge_vs_f64
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REL_FLOOR = 1e-3   # rel = |a-b| / max(|b|, REL_FLOOR)   (SURVEY 8d "state the floor")
@@ -15,8 +16,7 @@ def load_golden(name):
 
 
 def max_rel(a, b, floor=REL_FLOOR):
-    a = torch.as_tensor(a).detach().double().reshape(-1).cpu()
-    b = torch.as_tensor(b).detach().double().reshape(-1).cpu()
+    a, b = flat64(a), flat64(b)
     assert a.shape == b.shape, (a.shape, b.shape)
     return float(((a - b).abs() / b.abs().clamp(min=floor)).max())
 
@@ -35,8 +35,7 @@ def assert_close_counted(a, b, what="", tol=1e-4, floor=REL_FLOOR, max_tol=3e-4,
     values below ~1e-3 in magnitude (an SDF sample next to its zero crossing, the opacity / depth of a ray that only grazes
     the box) whose ABSOLUTE error is one or two fp32 ulps of the O(1) quantities that cancel to them (DESIGN.md section 4);
     the gate counts them instead of moving the floor."""
-    a = torch.as_tensor(a).detach().double().reshape(-1).cpu()
-    b = torch.as_tensor(b).detach().double().reshape(-1).cpu()
+    a, b = flat64(a), flat64(b)
     assert a.shape == b.shape, (a.shape, b.shape)
     rel = (a - b).abs() / b.abs().clamp(min=floor)
     n_bad = int((rel > tol).sum())
@@ -48,8 +47,7 @@ def assert_close_counted(a, b, what="", tol=1e-4, floor=REL_FLOOR, max_tol=3e-4,
 
 
 def rel_err(a, b, floor=REL_FLOOR):
-    a = torch.as_tensor(a).detach().double().reshape(-1).cpu()
-    b = torch.as_tensor(b).detach().double().reshape(-1).cpu()
+    a, b = flat64(a), flat64(b)
     assert a.shape == b.shape, (a.shape, b.shape)
     return (a - b).abs() / b.abs().clamp(min=floor)
 
@@ -63,14 +61,8 @@ def assert_close_vs_f64(hip, ref32, f64, what="", tol=1e-4, floor=REL_FLOOR, fac
         * its worst element within `factor` x the reference's own worst (or `tol`, whichever is larger), and
         * at most `factor` x as many elements above `tol` as the reference's own fp32 result has (+ `slack`).
     -> (worst_hip, n_hip, worst_ref, n_ref)."""
-    e_hip, e_ref = rel_err(hip, f64, floor), rel_err(ref32, f64, floor)
-    worst_hip, worst_ref = float(e_hip.max()), float(e_ref.max())
-    n_hip, n_ref = int((e_hip > tol).sum()), int((e_ref > tol).sum())
-    assert worst_hip <= max(factor * worst_ref, tol), \
-        f"{what}: max rel err vs float64 {worst_hip:.3e} > {factor:g} x the reference's own fp32 error {worst_ref:.3e} (floor {floor:g})"
-    assert n_hip <= int(factor * n_ref) + slack, \
-        f"{what}: {n_hip} elements above {tol:.0e} vs float64; the reference's own fp32 result has {n_ref} (floor {floor:g})"
-    return worst_hip, n_hip, worst_ref, n_ref
+    f = judge_vs_f64(hip, ref32, f64, flat64(f64).abs().clamp(min=floor), f"{what} (relative to max(|f64|, {floor:g}))", factor, tol, slack)
+    return f["worst_hip"], f["n_hip"], f["worst_ref"], f["n_ref"]
 
 
 def probe_points(n, stream=300, scale=1.15):
