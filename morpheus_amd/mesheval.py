@@ -6,10 +6,14 @@ points on the culled mesh and on the ground-truth mesh with trimesh, aligns the 
 scores accuracy / completion with a CPU KD-tree.  Here the depth map is morpheus_amd.meshrender's, and the HIP kernels of
 csrc/mesheval.hip do the rest: mh_nn_search is the exact brute-force nearest-neighbour search every score and every ICP
 iteration rests on; mh_cull_*, mh_mesh_area_weights / mh_sample_surface and mh_icp_* are the small kernels around it
-(conventions in include/morpheus_hip.h, restated in numpy by tests/mesheval_oracle.py).
+(conventions in include/morpheus_hip.h, restated in numpy by tests/mesheval_oracle.py).  The reference subdivides every mesh to
+0.01 edges before it culls (trimesh.remesh.subdivide_to_size); subdivide_to_size does that on the device (csrc/subdivide.hip,
+mh_subdiv_*, tests/subdivide_oracle.py), and cull_mesh / eval_mesh run it with subdivide=True -- the reference's behaviour; the
+default, False, culls the triangles as they are given.
 
-Known differences from the reference's scores: no trimesh subdivide_to_size before culling; the ICP parameters and
-stopping rule follow Open3D's documented defaults and were never compared with Open3D; sample_surface is seeded, where the
+Known differences from the reference's scores: with subdivide=True the subdivided mesh is trimesh's as a surface and
+as a set of triangles, not in vertex order or in which midpoints are shared (no consumer depends on either); the ICP parameters
+and stopping rule follow Open3D's documented defaults and were never compared with Open3D; sample_surface is seeded, where the
 reference draws from numpy's global generator.
 """
 from __future__ import annotations
@@ -25,6 +29,7 @@ import torch
 from . import _lib
 from ._lib import MorpheusHipError, launch, ptr, require_gpu
 from .meshrender import _mesh_arrays, _mesh_sequence, cv2gl, render_mesh
+from .tsdf import memory_cap_bytes
 
 
 def _points(name, a):
@@ -94,7 +99,7 @@ def _depth_map(name, d, H, W, device):
 
 def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[torch.Tensor] = None, *, c2w, K, H: int,
               W: int, depth_gt=None, eps: float = 0.005, remove_missing_depth: bool = True, rendered_depth=None,
-              return_masks: bool = False) -> dict:
+              return_masks: bool = False, subdivide: bool = False, max_edge: float = 0.01, max_iter: int = 10) -> dict:
     """cull_one_mesh / cull_from_one_pose (tools/culling.py:17-49, 86-131): keep the triangles that the camera of pose c2w
     (OpenGL, as the dataset stores it) observes -- a vertex in the frustum and no further than eps behind the rendered depth
     -- unless all three vertices fall on pixels without ground-truth depth.
@@ -102,8 +107,11 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
     vertices removed; with return_masks also frustum / observed / invalid (bool [V]) and keep (bool [T]).
     rendered_depth defaults to render_mesh's double-sided depth map from the same camera (near = 0.01 as the reference's
     pyrender camera; its zfar = 10 is not restated: the scene box is [-1, 1]^3).  depth_gt: [H,W] float32, needed when
-    remove_missing_depth.  The reference subdivides the mesh to 0.01 edges first; this works on the triangles it is given.
-    One host synchronisation (to size the outputs)."""
+    remove_missing_depth.  subdivide=True is the reference's behaviour: the mesh is first subdivided to max_edge (subdivide_to_size;
+    0.01 and 10 rounds there), so that what is kept or dropped is a piece no longer than that; the depth map is still rendered
+    from the mesh as given ("we don't need subdivided mesh to render depth"), the masks, the kept set and the interpolated
+    colours are those of the subdivided mesh, and return_masks refers to its arrays.  The default culls the triangles as they
+    are given.  One host synchronisation (to size the outputs), one more with subdivide."""
     tri = _mesh_arrays(vertices, triangles, colors)
     H, W = int(H), int(W)
     dev = vertices.device
@@ -117,6 +125,10 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
                                      near=0.01)["depth"]
     rendered_depth = _depth_map("rendered_depth", rendered_depth, H, W, dev)
     depth_gt = _depth_map("depth_gt", depth_gt, H, W, dev) if remove_missing_depth else None
+    if subdivide:
+        fine = _subdivide(vertices, tri, colors, max_edge, max_iter, None, False)
+        if fine is not None:
+            vertices, tri, colors, _ = fine
     w2c, w2c_p = _doubles(world_to_camera_f64(c2w))
     Kd, K_p = _doubles(Kh)
     V, T = vertices.shape[0], tri.shape[0]
@@ -134,6 +146,83 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
            "colors": None if colors is None else colors[used].contiguous()}
     if return_masks:
         out.update(frustum=frustum.bool(), observed=observed.bool(), invalid=invalid.bool(), keep=keep)
+    return out
+
+
+# ---- subdivision ---------------------------------------------------------------------------------------------------------
+
+def _subdivide(vertices, tri, colors, max_edge, max_iter, max_gb, want_index, hand_on_bytes=0):
+    """subdivide_to_size on checked arrays (tri int32) -> (vertices, tri int32, colors, index int32 or None), or None when no
+    triangle is split.  hand_on_bytes: what the caller allocates per output triangle on top (counted under the cap)."""
+    m = np.float32(max_edge)
+    if not (m > 0 and np.isfinite(m)):
+        raise MorpheusHipError(f"subdivide_to_size: max_edge must be finite and positive in float32, got {max_edge}")
+    max_iter = int(max_iter)
+    if not 0 <= max_iter <= 10:
+        raise MorpheusHipError(f"subdivide_to_size: max_iter must be in [0, 10], got {max_iter}")
+    V, T = vertices.shape[0], tri.shape[0]
+    if T == 0:
+        return None
+    dev = vertices.device
+    depth = torch.empty(T, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, T, dtype=torch.int64, device=dev)
+    launch("mh_subdiv_count", ptr(vertices), V, ptr(tri), T, float(m), max_iter, ptr(depth), ptr(counts[0]), ptr(counts[1]))
+    starts = torch.zeros(2, T + 1, dtype=torch.int64, device=dev)
+    starts[:, 1:] = torch.cumsum(counts, 1)                       # exclusive prefix sums: integer, exact in any order
+    n_new, n_tri, deepest = (int(x) for x in torch.stack([starts[0, T], starts[1, T], depth.max().long()]).cpu())   # the host waits here
+    if deepest > max_iter:
+        long = depth > max_iter
+        e = vertices[tri[long].long()].double()
+        longest = float(torch.stack([(e[:, 1] - e[:, 0]).norm(dim=1), (e[:, 2] - e[:, 1]).norm(dim=1),
+                                     (e[:, 0] - e[:, 2]).norm(dim=1)]).max())
+        raise MorpheusHipError(
+            f"subdivide_to_size: {int(long.sum())} of {T} triangles still have an edge above max_edge = {float(m):g} after max_iter = "
+            f"{max_iter} halvings (longest edge {longest:g}); pass a larger max_edge (trimesh raises here too)")
+    if n_new == 0 and n_tri == T:
+        return None
+    if V + n_new >= 2 ** 31 or n_tri >= 2 ** 31:
+        raise MorpheusHipError(f"subdivide_to_size: {V + n_new} vertices and {n_tri} triangles at max_edge = {float(m):g} do not fit "
+                               f"int32 indices; pass a larger max_edge")
+    need = (V + n_new) * 12 * (1 if colors is None else 2) + n_tri * (12 + (4 if want_index else 0) + hand_on_bytes)
+    cap = memory_cap_bytes(dev, max_gb)
+    if need > cap:
+        raise MorpheusHipError(
+            f"subdivide_to_size: {V} vertices / {T} triangles become {V + n_new} vertices / {n_tri} triangles at max_edge = "
+            f"{float(m):g}: {need / 1e9:.3f} GB, over the cap of {cap / 1e9:.3f} GB.  Pass a larger max_edge (the counts fall with "
+            f"its square); max_gb= raises the cap.")
+    out_v = torch.empty(V + n_new, 3, dtype=torch.float32, device=dev)
+    out_c = None if colors is None else torch.empty(V + n_new, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(n_tri, 3, dtype=torch.int32, device=dev)
+    index = torch.empty(n_tri, dtype=torch.int32, device=dev) if want_index else None
+    launch("mh_subdiv_emit", ptr(vertices), ptr(colors), V, ptr(tri), T, ptr(depth), ptr(starts[0]), ptr(starts[1]), n_new, n_tri,
+           ptr(out_v), ptr(out_c), ptr(out_t), ptr(index))
+    return out_v, out_t, out_c, index
+
+
+def subdivide_to_size(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[torch.Tensor] = None, *,
+                      max_edge: float = 0.01, max_iter: int = 10, max_gb: Optional[float] = None,
+                      return_index: bool = False) -> dict:
+    """trimesh.remesh.subdivide_to_size(vertices, triangles, max_edge, max_iter) as cull_one_mesh runs it (tools/culling.py:
+    93-96): every triangle with an edge longer than max_edge is split into four at its edge midpoints, and so are its children.
+    The children's edges are the parent's halved, so a triangle ends as 4^d pieces, d the smallest depth at which its longest
+    edge * 2^-d <= max_edge (float64, no square root; include/morpheus_hip.h).  -> dict(vertices [V',3], triangles int64 [T',3],
+    colors [V',3] or None -- interpolated like the positions), with return_index also index int64 [T'], the input triangle of
+    every output triangle.  The V input vertices come first, unchanged; new vertices are not shared between input triangles (on a
+    shared edge of equal depth they are the same bytes); trimesh's vertex order is not reproduced.  When no triangle needs
+    splitting the result is the input.  A triangle with an index outside [0, V) or with a NaN edge passes through.
+    One host synchronisation (the two totals and the largest depth).  Raises when a triangle is still too long after max_iter
+    halvings (an infinite coordinate included), when the result does not fit int32 indices, and -- before anything is allocated
+    -- when it would exceed max_gb (default: min(0.4 of the device, 0.85 of what is free))."""
+    tri = _mesh_arrays(vertices, triangles, colors)
+    res = _subdivide(vertices, tri, colors, max_edge, max_iter, max_gb, return_index, hand_on_bytes=24 + (8 if return_index else 0))
+    if res is None:
+        out = {"vertices": vertices, "triangles": triangles if triangles.dtype == torch.int64 else triangles.long(), "colors": colors}
+        if return_index:
+            out["index"] = torch.arange(tri.shape[0], dtype=torch.int64, device=vertices.device)
+        return out
+    out = {"vertices": res[0], "triangles": res[1].long(), "colors": res[2]}
+    if return_index:
+        out["index"] = res[3].long()
     return out
 
 
@@ -292,15 +381,18 @@ def mesh_metrics(rec, gt, align: bool = True, num_points: int = 50000, seed: int
 
 def eval_mesh(meshes_or_dir, gt_meshes, poses, K, H: int, W: int, depths_gt, save_file: Optional[str] = None, epoch: int = 0,
               mesh_epoch: Optional[int] = None, align: bool = True, num_points: int = 50000, seed: int = 0, eps: float = 0.005,
-              remove_missing_depth: bool = True, device="cuda") -> dict:
+              remove_missing_depth: bool = True, device="cuda", subdivide: bool = False, max_edge: float = 0.01) -> dict:
     """The loop of eval_mesh + eval_mesh_3d (tools/culling.py:223-235, 262-275): mesh i is culled from poses[i] against
     depths_gt[i] and scored against gt_meshes[i]; nothing is written in between.  meshes_or_dir as in render_all_meshes
     (`mesh_epoch` selects a directory's files); gt_meshes: mesh dicts or PLY paths by frame.  Appends the reference's line
-    "Ep_{epoch}:\\t Acc:{}\\t Comp:{}" to save_file.  -> {"acc": [...], "comp": [...], "comp ratio": [...], "frames": [...]}."""
+    "Ep_{epoch}:\\t Acc:{}\\t Comp:{}" to save_file.  subdivide, max_edge: handed to cull_mesh; subdivide=True is what the reference
+    does (every mesh subdivided to 0.01 edges before it is culled), the default culls the exported triangles as they are.
+    -> {"acc": [...], "comp": [...], "comp ratio": [...], "frames": [...]}."""
     out = {"acc": [], "comp": [], "comp ratio": [], "frames": []}
     for i, mesh in _mesh_sequence(meshes_or_dir, device, mesh_epoch):
         culled = cull_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), c2w=poses[i], K=K, H=H, W=W,
-                           depth_gt=depths_gt[i], eps=eps, remove_missing_depth=remove_missing_depth)
+                           depth_gt=depths_gt[i], eps=eps, remove_missing_depth=remove_missing_depth, subdivide=subdivide,
+                           max_edge=max_edge)
         m = mesh_metrics(culled, gt_meshes[i], align=align, num_points=num_points, seed=seed, device=device)
         for k in ("acc", "comp", "comp ratio"):
             out[k].append(m[k])
