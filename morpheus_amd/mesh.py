@@ -9,13 +9,30 @@ morpheus.py:431); morpheus_amd.meshrender renders it here and read_ply reads it 
 from __future__ import annotations
 
 import os
-from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import MorpheusHipError, launch, ptr, require_gpu
+from .geometry import host_array
+
+
+def _count_then_emit(count_name, emit_name, count_args, emit_args, wbytes, device, extra_counters=None, check=None):
+    """The two passes of every marching cubes -> (vertices float32 [V,3], triangles int64 [T,3]): count_name(*count_args, workspace,
+    counts) sizes the outputs, ONE host read fetches V and T (and extra_counters, an integer device tensor, with them),
+    check(V, T, *extra) may refuse them, emit_name(*emit_args, workspace, vertices, triangles) fills them unless both are empty."""
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=device)
+    counts = torch.empty(2, dtype=torch.int64, device=device)
+    launch(count_name, *count_args, ptr(ws), ptr(counts))
+    V, T, *extra = (counts if extra_counters is None else torch.cat([counts, extra_counters.long()])).tolist()
+    if check is not None:
+        check(V, T, *extra)
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=device)
+    triangles = torch.empty(T, 3, dtype=torch.int32, device=device)
+    if V or T:
+        launch(emit_name, *emit_args, ptr(ws), ptr(vertices), ptr(triangles))
+    return vertices, triangles.long()
 
 
 def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
@@ -25,22 +42,12 @@ def marching_cubes(volume: torch.Tensor, isovalue: float = 0.0):
     if volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous():
         raise MorpheusHipError(f"marching_cubes takes a contiguous float32 [nx,ny,nz] volume, got {volume.dtype} "
                                f"{tuple(volume.shape)}")
-    lib = _lib.load()
     nx, ny, nz = volume.shape
-    wbytes = lib.mh_mc_workspace_bytes(nx, ny, nz)
+    wbytes = _lib.load().mh_mc_workspace_bytes(nx, ny, nz)
     if wbytes < 0:
         raise MorpheusHipError(f"marching_cubes: shape {tuple(volume.shape)} unsupported (each side >= 2, < 2^31 points)")
-    dev = volume.device
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-    counts = torch.empty(2, dtype=torch.int64, device=dev)
-    iso = float(isovalue)
-    launch("mh_mc_count", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(counts))
-    V, T = counts.tolist()
-    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
-    if V or T:
-        launch("mh_mc_emit", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles))
-    return vertices, triangles.long()
+    args = (ptr(volume), nx, ny, nz, float(isovalue))
+    return _count_then_emit("mh_mc_count", "mh_mc_emit", args, args, wbytes, volume.device)
 
 
 def marching_cubes_masked(volume: torch.Tensor, weight: torch.Tensor, isovalue: float = 0.0):
@@ -52,22 +59,13 @@ def marching_cubes_masked(volume: torch.Tensor, weight: torch.Tensor, isovalue: 
         if a.dim() != 3 or a.dtype != torch.float32 or not a.is_contiguous() or a.shape != volume.shape:
             raise MorpheusHipError(f"marching_cubes_masked takes contiguous float32 [nx,ny,nz] volume and weight of one shape, got "
                                    f"{name} {a.dtype} {tuple(a.shape)}")
-    lib = _lib.load()
     nx, ny, nz = volume.shape
-    wbytes = lib.mh_mc_masked_workspace_bytes(nx, ny, nz)
+    wbytes = _lib.load().mh_mc_masked_workspace_bytes(nx, ny, nz)
     if wbytes < 0:
         raise MorpheusHipError(f"marching_cubes_masked: shape {tuple(volume.shape)} unsupported (each side >= 2, < 2^31 points)")
-    dev = volume.device
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-    counts = torch.empty(2, dtype=torch.int64, device=dev)
-    iso = float(isovalue)
-    launch("mh_mc_count_masked", ptr(volume), ptr(weight), nx, ny, nz, iso, ptr(ws), ptr(counts))
-    V, T = counts.tolist()
-    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
-    if V or T:
-        launch("mh_mc_emit_masked", ptr(volume), nx, ny, nz, iso, ptr(ws), ptr(vertices), ptr(triangles))
-    return vertices, triangles.long()
+    args = (nx, ny, nz, float(isovalue))
+    return _count_then_emit("mh_mc_count_masked", "mh_mc_emit_masked", (ptr(volume), ptr(weight)) + args, (ptr(volume),) + args,
+                            wbytes, volume.device)
 
 
 @torch.no_grad()
@@ -105,12 +103,12 @@ def extract_mesh(model, resolution: int = 128, S: int = 128, t=None, cano: bool 
 def write_ply(path: str, vertices, triangles, colors=None) -> None:
     """Binary little-endian PLY: float x y z [uchar red green blue alpha], faces as `list uchar int vertex_indices`.
     Colours in [0, 1] are stored as round(clip(c, 0, 1) * 255) with alpha 255."""
-    v = np.ascontiguousarray(_host(vertices), dtype="<f4").reshape(-1, 3)
-    f = np.ascontiguousarray(_host(triangles), dtype="<i4").reshape(-1, 3)
+    v = host_array(vertices, "<f4").reshape(-1, 3)
+    f = host_array(triangles, "<i4").reshape(-1, 3)
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
             "property float x", "property float y", "property float z"]
     if colors is not None:
-        c = np.rint(np.clip(_host(colors).astype(np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+        c = np.rint(np.clip(host_array(colors, np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
         head += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
         vrec = np.empty(v.shape[0], dtype=[("xyz", "<f4", 3), ("rgba", "u1", 4)])
         vrec["xyz"] = v
@@ -187,7 +185,10 @@ def export_mesh(model, mesh_savepath: str, resolution: int = 128, S: int = 128, 
     return mesh
 
 
-def _host(a) -> Optional[np.ndarray]:
-    if isinstance(a, torch.Tensor):
-        return a.detach().cpu().numpy()
-    return np.asarray(a)
+def load_mesh(mesh_or_path, device):
+    """the path of a PLY (read_ply's layout) -> dict(vertices, triangles, colors or None) on `device`; a mesh dict is handed back"""
+    if not isinstance(mesh_or_path, (str, os.PathLike)):
+        return mesh_or_path
+    v, t, c = read_ply(os.fspath(mesh_or_path))
+    return {"vertices": torch.from_numpy(v).to(device), "triangles": torch.from_numpy(t).to(device),
+            "colors": None if c is None else torch.from_numpy(c).to(device)}

@@ -18,7 +18,6 @@ reference draws from numpy's global generator.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 from typing import Optional
@@ -28,20 +27,10 @@ import torch
 
 from . import _lib
 from ._lib import MorpheusHipError, launch, ptr, require_gpu
-from .meshrender import _mesh_arrays, _mesh_sequence, cv2gl, render_mesh
-from .tsdf import memory_cap_bytes
-
-
-def _points(name, a):
-    require_gpu(a)
-    if a.dim() != 2 or a.shape[1] != 3 or a.dtype != torch.float32 or not a.is_contiguous():
-        raise MorpheusHipError(f"{name}: contiguous float32 [N,3], got {a.dtype} {tuple(a.shape)}")
-    return a
-
-
-def _doubles(a: np.ndarray):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a, a.ctypes.data_as(ctypes.c_void_p)
+from .geometry import (host_array, host_ptr, memory_cap_bytes, mesh_arrays, require_points, transform_points,  # noqa: F401
+                       world_to_camera)                            # transform_points: also mesheval's public name
+from .mesh import load_mesh
+from .meshrender import mesh_sequence, render_mesh
 
 
 # ---- nearest neighbour ---------------------------------------------------------------------------------------------------
@@ -51,8 +40,8 @@ def nearest(query: torch.Tensor, ref: torch.Tensor, max_dist: Optional[float] = 
     fp32 operators), the lowest index among equals; candidates with a NaN or infinite d2, or with d2 > float32(max_dist)^2,
     are ignored; idx = -1 and d2 = +inf where none is left.  Exact brute force.  `segments` (how many runs the reference set
     is cut into; 0: chosen from the sizes) never changes the result.  No host synchronisation."""
-    _points("query", query)
-    _points("ref", ref)
+    require_points("query", query)
+    require_points("ref", ref)
     if segments > 4096:
         raise MorpheusHipError(f"nearest: at most 4096 segments, got {segments}")
     max_d2 = math.inf
@@ -76,21 +65,14 @@ def nearest(query: torch.Tensor, ref: torch.Tensor, max_dist: Optional[float] = 
 def world_to_camera_f64(c2w) -> np.ndarray:
     """OpenGL camera-to-world [4,4] or [3,4] host pose -> float64 [3,4] world -> OpenCV camera (columns 1 and 2 negated, then
     numpy.linalg.inv, as cull_from_one_pose does)."""
-    if isinstance(c2w, torch.Tensor):
-        c2w = c2w.detach().cpu().numpy()
-    c = np.asarray(c2w, dtype=np.float64)
-    if c.shape not in ((4, 4), (3, 4)):
-        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
-    m = np.eye(4, dtype=np.float64)
-    m[:3] = c[:3]
-    return np.ascontiguousarray(np.linalg.inv(cv2gl(m))[:3])
+    return world_to_camera(c2w, "opengl", np.float64)
 
 
 def _depth_map(name, d, H, W, device):
     if d is None:
         return None
     if not isinstance(d, torch.Tensor):
-        d = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float32)).to(device)
+        d = torch.from_numpy(host_array(d, np.float32)).to(device)
     require_gpu(d)
     if tuple(d.shape) != (H, W) or d.dtype != torch.float32 or not d.is_contiguous():
         raise MorpheusHipError(f"{name}: contiguous float32 [{H},{W}], got {d.dtype} {tuple(d.shape)}")
@@ -112,10 +94,10 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
     from the mesh as given ("we don't need subdivided mesh to render depth"), the masks, the kept set and the interpolated
     colours are those of the subdivided mesh, and return_masks refers to its arrays.  The default culls the triangles as they
     are given.  One host synchronisation (to size the outputs), one more with subdivide."""
-    tri = _mesh_arrays(vertices, triangles, colors)
+    tri = mesh_arrays(vertices, triangles, colors)
     H, W = int(H), int(W)
     dev = vertices.device
-    Kh = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
+    Kh = host_array(K)
     if Kh.shape != (3, 3):
         raise MorpheusHipError(f"K must be [3,3], got {Kh.shape}")
     if remove_missing_depth and depth_gt is None:
@@ -129,13 +111,12 @@ def cull_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optional[
         fine = _subdivide(vertices, tri, colors, max_edge, max_iter, None, False)
         if fine is not None:
             vertices, tri, colors, _ = fine
-    w2c, w2c_p = _doubles(world_to_camera_f64(c2w))
-    Kd, K_p = _doubles(Kh)
+    w2c, Kd = world_to_camera_f64(c2w), host_array(Kh, np.float64)
     V, T = vertices.shape[0], tri.shape[0]
     frustum, observed, invalid = (torch.zeros(V, dtype=torch.uint8, device=dev) for _ in range(3))
     keep = torch.zeros(T, dtype=torch.uint8, device=dev)
-    launch("mh_cull_vertices", ptr(vertices), V, w2c_p, K_p, H, W, ptr(rendered_depth), ptr(depth_gt), float(eps), ptr(frustum),
-           ptr(observed), ptr(invalid))
+    launch("mh_cull_vertices", ptr(vertices), V, host_ptr(w2c), host_ptr(Kd), H, W, ptr(rendered_depth), ptr(depth_gt), float(eps),
+           ptr(frustum), ptr(observed), ptr(invalid))
     launch("mh_cull_triangles", ptr(tri), T, V, ptr(observed), ptr(invalid), ptr(keep))
     keep = keep.bool()
     kept = tri[keep].long()                                        # the host waits here
@@ -213,7 +194,7 @@ def subdivide_to_size(vertices: torch.Tensor, triangles: torch.Tensor, colors: O
     One host synchronisation (the two totals and the largest depth).  Raises when a triangle is still too long after max_iter
     halvings (an infinite coordinate included), when the result does not fit int32 indices, and -- before anything is allocated
     -- when it would exceed max_gb (default: min(0.4 of the device, 0.85 of what is free))."""
-    tri = _mesh_arrays(vertices, triangles, colors)
+    tri = mesh_arrays(vertices, triangles, colors)
     res = _subdivide(vertices, tri, colors, max_edge, max_iter, max_gb, return_index, hand_on_bytes=24 + (8 if return_index else 0))
     if res is None:
         out = {"vertices": vertices, "triangles": triangles if triangles.dtype == torch.int64 else triangles.long(), "colors": colors}
@@ -231,7 +212,7 @@ def subdivide_to_size(vertices: torch.Tensor, triangles: torch.Tensor, colors: O
 def area_weights(vertices: torch.Tensor, triangles: torch.Tensor):
     """-> (areas float32 [T], cum int64 [T]): the triangles' areas and the inclusive prefix sum of their fixed-point values
     (grid q = G * 2^-40, G the power of two strictly above the largest area): integer, so exact in any order."""
-    tri = _mesh_arrays(vertices, triangles)
+    tri = mesh_arrays(vertices, triangles)
     V, T = vertices.shape[0], tri.shape[0]
     areas = torch.empty(T, dtype=torch.float32, device=vertices.device)
     qarea = torch.empty(T + 1, dtype=torch.int64, device=vertices.device)
@@ -245,7 +226,7 @@ def sample_surface(vertices: torch.Tensor, triangles: torch.Tensor, count: int, 
     -> (points float32 [count,3], face int32 [count]).  uniforms [count,3] float32 in [0, 1) (column 0 picks the face, 1 and 2
     the barycentrics) default to a torch.Generator seeded with `seed` on the device.  One host synchronisation (an empty mesh
     or one of zero total area raises)."""
-    tri = _mesh_arrays(vertices, triangles)
+    tri = mesh_arrays(vertices, triangles)
     count = int(count)
     dev = vertices.device
     V, T = vertices.shape[0], tri.shape[0]
@@ -255,7 +236,7 @@ def sample_surface(vertices: torch.Tensor, triangles: torch.Tensor, count: int, 
         g = torch.Generator(device=dev)
         g.manual_seed(int(seed))
         uniforms = torch.rand(count, 3, generator=g, dtype=torch.float32, device=dev)
-    _points("uniforms", uniforms)
+    require_points("uniforms", uniforms)
     if uniforms.shape[0] != count:
         raise MorpheusHipError(f"uniforms: [{count},3], got {tuple(uniforms.shape)}")
     _, cum = area_weights(vertices, tri)
@@ -269,20 +250,11 @@ def sample_surface(vertices: torch.Tensor, triangles: torch.Tensor, count: int, 
 
 # ---- rigid alignment -----------------------------------------------------------------------------------------------------
 
-def transform_points(points: torch.Tensor, T) -> torch.Tensor:
-    """T [4,4] or [3,4] host float64 applied to fp32 points: computed in float64, rounded once."""
-    _points("points", points)
-    Th, T_p = _doubles(np.asarray(T, dtype=np.float64)[:3])
-    out = torch.empty_like(points)
-    launch("mh_icp_transform", ptr(points), points.shape[0], T_p, ptr(out))
-    return out
-
-
 def icp_sums(moved: torch.Tensor, target: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor) -> torch.Tensor:
     """-> float64 [17] on the device: n, sum d2, sum p, sum q, sum p q^T over the correspondences with idx >= 0, in a fixed
     order (the same bytes run to run)."""
-    _points("moved", moved)
-    _points("target", target)
+    require_points("moved", moved)
+    require_points("target", target)
     require_gpu(idx, d2)
     N = moved.shape[0]
     if idx.shape != (N,) or idx.dtype != torch.int32 or d2.shape != (N,) or d2.dtype != torch.float32:
@@ -314,8 +286,8 @@ def icp_align(source: torch.Tensor, target: torch.Tensor, threshold: float = 0.1
     -> dict(transformation float64 [4,4] numpy, fitness, inlier_rmse, iterations).  The parameters and the stopping rule
     (both |delta fitness| and |delta rmse| below their thresholds, or max_iteration) are what Open3D's registration_icp is
     understood to use; agreement with Open3D is unverified.  One host synchronisation per iteration."""
-    _points("source", source)
-    _points("target", target)
+    require_points("source", source)
+    require_points("target", target)
     Ns = source.shape[0]
     T = np.eye(4)
 
@@ -345,15 +317,6 @@ def icp_align(source: torch.Tensor, target: torch.Tensor, threshold: float = 0.1
 
 # ---- the scores ----------------------------------------------------------------------------------------------------------
 
-def _load_mesh(m, device):
-    if isinstance(m, (str, os.PathLike)):
-        from .mesh import read_ply
-        v, t, c = read_ply(os.fspath(m))
-        return {"vertices": torch.from_numpy(v).to(device), "triangles": torch.from_numpy(t).to(device),
-                "colors": None if c is None else torch.from_numpy(c).to(device)}
-    return m
-
-
 def mesh_metrics(rec, gt, align: bool = True, num_points: int = 50000, seed: int = 0, dist_th: float = 0.05,
                  device="cuda", uniforms_rec=None, uniforms_gt=None) -> dict:
     """calc_3d_metric (tools/culling.py:189-221) -> {'acc': mean distance rec -> gt in cm, 'comp': mean distance gt -> rec in
@@ -361,7 +324,7 @@ def mesh_metrics(rec, gt, align: bool = True, num_points: int = 50000, seed: int
     paths of PLYs in read_ply's layout; a gt with triangles None is a point cloud and is used as it is.  align: icp_align
     between the two vertex sets first, applied to rec.  Both surfaces are sampled with num_points points (seeds `seed` and
     `seed + 1`, or the injected uniforms).  Distances are sqrt(d2) in float64, the means in float64."""
-    rec, gt = _load_mesh(rec, device), _load_mesh(gt, device)
+    rec, gt = load_mesh(rec, device), load_mesh(gt, device)
     rv = rec["vertices"]
     if align:
         rv = transform_points(rv, icp_align(rv, gt["vertices"])["transformation"])
@@ -370,7 +333,7 @@ def mesh_metrics(rec, gt, align: bool = True, num_points: int = 50000, seed: int
 
     rec_pts = sample_surface(rv, rec["triangles"], count(uniforms_rec), seed=seed, uniforms=uniforms_rec)[0]
     if gt.get("triangles") is None:
-        gt_pts = _points("gt vertices", gt["vertices"])
+        gt_pts = require_points("gt vertices", gt["vertices"])
     else:
         gt_pts = sample_surface(gt["vertices"], gt["triangles"], count(uniforms_gt), seed=seed + 1, uniforms=uniforms_gt)[0]
     d_acc = nearest(rec_pts, gt_pts)[1].double().sqrt()
@@ -389,7 +352,7 @@ def eval_mesh(meshes_or_dir, gt_meshes, poses, K, H: int, W: int, depths_gt, sav
     does (every mesh subdivided to 0.01 edges before it is culled), the default culls the exported triangles as they are.
     -> {"acc": [...], "comp": [...], "comp ratio": [...], "frames": [...]}."""
     out = {"acc": [], "comp": [], "comp ratio": [], "frames": []}
-    for i, mesh in _mesh_sequence(meshes_or_dir, device, mesh_epoch):
+    for i, mesh in mesh_sequence(meshes_or_dir, device, mesh_epoch):
         culled = cull_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), c2w=poses[i], K=K, H=H, W=W,
                            depth_gt=depths_gt[i], eps=eps, remove_missing_depth=remove_missing_depth, subdivide=subdivide,
                            max_edge=max_edge)

@@ -8,7 +8,6 @@ renders it.  A render call does not wait for the device: every output's size fol
 """
 from __future__ import annotations
 
-import ctypes
 import glob
 import os
 import re
@@ -18,30 +17,19 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MorpheusHipError, launch, ptr, require_gpu
+from ._lib import MorpheusHipError, launch, ptr
+from .geometry import (cv2gl, host_array, host_ptr, intrinsics, mesh_arrays, transform_points,  # noqa: F401  (cv2gl: re-exported)
+                       world_to_camera)
+from .mesh import load_mesh
 
 MODES = {"color": 0, "normal": 1, "shaded": 2}
 MAX_SIDE = 16384
 
 
-def _mesh_arrays(vertices, triangles, colors=None, normals=None):
-    require_gpu(vertices, triangles, colors, normals)
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or not vertices.is_contiguous():
-        raise MorpheusHipError(f"vertices: contiguous float32 [V,3], got {vertices.dtype} {tuple(vertices.shape)}")
-    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype not in (torch.int32, torch.int64) \
-            or not triangles.is_contiguous():
-        raise MorpheusHipError(f"triangles: contiguous int32 / int64 [T,3], got {triangles.dtype} {tuple(triangles.shape)}")
-    for name, a in (("colors", colors), ("normals", normals)):
-        if a is not None and (a.shape != vertices.shape or a.dtype != torch.float32 or not a.is_contiguous()):
-            raise MorpheusHipError(f"{name}: contiguous float32 [V,3] like vertices, got {a.dtype} {tuple(a.shape)}")
-    # the C ABI takes the int32 indices mh_mc_emit writes; extract_mesh hands out int64 (a device-side cast, no wait)
-    return triangles if triangles.dtype == torch.int32 else triangles.to(torch.int32)
-
-
 def vertex_normal_sums(vertices: torch.Tensor, triangles: torch.Tensor):
     """-> (normals float32 [V,3], acc int64 [3V + 1]): the area-weighted vertex normals and the fixed-point sums they come
     from (acc[:3V] = sums [V][3] on the grid q, acc[3V] = the bits of the mesh's largest |cross component|)."""
-    tri = _mesh_arrays(vertices, triangles)
+    tri = mesh_arrays(vertices, triangles)
     V, T = vertices.shape[0], tri.shape[0]
     acc = torch.empty(3 * V + 1, dtype=torch.int64, device=vertices.device)
     normals = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
@@ -55,33 +43,9 @@ def vertex_normals(vertices: torch.Tensor, triangles: torch.Tensor) -> torch.Ten
     return vertex_normal_sums(vertices, triangles)[0]
 
 
-def cv2gl(c2w) -> np.ndarray:
-    """OpenGL <-> OpenCV camera-to-world (tools/vis.py:cv2gl): columns 1 and 2 negated.  Its own inverse."""
-    c2w = np.array(c2w, dtype=np.float64)
-    c2w[:3, 1:3] *= -1
-    return c2w
-
-
-def world_to_camera(c2w, convention: str = "opengl") -> np.ndarray:
-    """c2w [4,4] or [3,4] host pose -> row-major float32 [3,4] world -> OpenCV camera, inverted in float64."""
-    if convention not in ("opengl", "opencv"):
-        raise MorpheusHipError(f"convention must be 'opengl' or 'opencv', got {convention!r}")
-    if isinstance(c2w, torch.Tensor):
-        c2w = c2w.detach().cpu().numpy()
-    m = np.eye(4, dtype=np.float64)
-    c = np.asarray(c2w, dtype=np.float64)
-    if c.shape not in ((4, 4), (3, 4)):
-        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
-    m[:3] = c[:3]
-    if convention == "opengl":
-        m = cv2gl(m)
-    return np.ascontiguousarray(np.linalg.inv(m)[:3].astype(np.float32))
-
-
 def _intrinsics(K, fx, fy, cx, cy):
     if K is not None:
-        K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
-        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        return intrinsics(K)
     if None in (fx, fy, cx, cy):
         raise MorpheusHipError("render_mesh needs K or fx, fy, cx, cy")
     return float(fx), float(fy), float(cx), float(cy)
@@ -98,7 +62,7 @@ def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optiona
     computed when a mode needs them and none are given.  depth and tri_id do not depend on mode, run or triangle order."""
     if mode not in MODES:
         raise MorpheusHipError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    tri = _mesh_arrays(vertices, triangles, colors, normals)
+    tri = mesh_arrays(vertices, triangles, colors, normals)
     H, W = int(H), int(W)
     V, T = vertices.shape[0], tri.shape[0]
     lib = _lib.load()
@@ -107,7 +71,7 @@ def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optiona
         raise MorpheusHipError(f"render_mesh: H, W must be in [1, {MAX_SIDE}] and T below 2^31, got {H} x {W}, T = {T}")
     fx, fy, cx, cy = _intrinsics(K, fx, fy, cx, cy)
     w2c = world_to_camera(c2w, convention)
-    w2c_p = w2c.ctypes.data_as(ctypes.c_void_p)
+    w2c_p = host_ptr(w2c)
     if normals is None and MODES[mode] != 0:
         normals = vertex_normals(vertices, tri)
     dev = vertices.device
@@ -126,16 +90,15 @@ def render_mesh(vertices: torch.Tensor, triangles: torch.Tensor, colors: Optiona
 
 def concat_meshes(geom_list, need_colors: bool = False) -> dict:
     """Several mesh dicts -> one (vertices, triangles, colors) on the device: each mesh's optional 4 x 4 `transform` (host,
-    float64) is applied to its vertices through mesheval.transform_points, the triangle indices are offset.  colors: None when
+    float64) is applied to its vertices through geometry.transform_points, the triangle indices are offset.  colors: None when
     no mesh has any; a mesh without colours beside coloured ones gets the rasteriser's 0.7 grey."""
-    from .mesheval import transform_points
     if not geom_list:
         raise MorpheusHipError("render_mesh_from_view: geom_list is empty")
     any_colors = need_colors and any(g.get("colors") is not None for g in geom_list)
     verts, tris, cols, base = [], [], [], 0
     for g in geom_list:
         v, t = g["vertices"], g["triangles"]
-        _mesh_arrays(v, t, g.get("colors"))
+        mesh_arrays(v, t, g.get("colors"))
         if g.get("transform") is not None and v.shape[0]:
             v = transform_points(v, g["transform"])
         verts.append(v)
@@ -169,11 +132,10 @@ def render_mesh_from_view(geom_list, c2w, K, H: int, W: int, mode: str = "gray",
 _PLY_NAME = re.compile(r"mesh_(\d+)_(\d+)\.ply$")
 
 
-def _mesh_sequence(meshes_or_dir, device, epoch=None):
+def mesh_sequence(meshes_or_dir, device, epoch=None):
     """-> iterator of (frame id, mesh dict on the device).  A directory holds mesh_{epoch:04d}_{frame:04d}.ply, every epoch's
     files side by side (morpheus.py:1489): `epoch` selects one; without it the directory must hold a single epoch."""
     if isinstance(meshes_or_dir, (str, os.PathLike)):
-        from .mesh import read_ply
         named = []
         for path in glob.glob(os.path.join(os.fspath(meshes_or_dir), "*.ply")):
             m = _PLY_NAME.match(os.path.basename(path))
@@ -189,9 +151,7 @@ def _mesh_sequence(meshes_or_dir, device, epoch=None):
             raise MorpheusHipError(f"no mesh_EPOCH_FRAME.ply under {meshes_or_dir}" +
                                    ("" if epoch is None else f" for epoch {int(epoch)} (found epochs {epochs})"))
         for _, frame, path in sorted(named):
-            v, t, c = read_ply(path)
-            yield frame, {"vertices": torch.from_numpy(v).to(device), "triangles": torch.from_numpy(t).to(device),
-                          "colors": None if c is None else torch.from_numpy(c).to(device)}
+            yield frame, load_mesh(path, device)
     else:
         if epoch is not None:
             raise MorpheusHipError("epoch selects files of a mesh directory; it has no meaning for an iterable of meshes")
@@ -221,11 +181,11 @@ def render_all_meshes(meshes_or_dir, poses, K, H: int, W: int, save_images_dir: 
         except ImportError as e:                                   # images were asked for and cannot be written
             raise MorpheusHipError("render_all_meshes: save_images_dir needs PIL to write PNGs") from e
         os.makedirs(save_images_dir, exist_ok=True)
-    K = np.array(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
+    K = host_array(K, np.float64)                                  # only the focal lengths are read
     fx, fy = K[0, 0] * scale, K[1, 1] * scale
     h, w = int(H * scale), int(W * scale)
     results, depths = [], {}
-    for i, mesh in _mesh_sequence(meshes_or_dir, device, epoch):
+    for i, mesh in mesh_sequence(meshes_or_dir, device, epoch):
         out = render_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), mesh.get("normals"), c2w=poses[i], H=h, W=w,
                           fx=fx, fy=fy, cx=w / 2.0, cy=h / 2.0, convention=convention, mode=mode, near=near,
                           background=background, ambient=ambient)

@@ -15,7 +15,6 @@ default stays dense: the sparse store is asked for, never fallen back to.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Optional, Sequence
 
@@ -24,7 +23,8 @@ import torch
 
 from . import _lib
 from ._lib import MorpheusHipError, launch, ptr, require_gpu
-from .chunking import DEFAULT_FRACTION, available_bytes
+from .geometry import gpu_device, host_ptr, intrinsics, memory_cap_bytes, pose_pair   # memory_cap_bytes: also tsdf's public name
+from .mesh import _count_then_emit, marching_cubes_masked, write_ply
 
 BLOCK = 8
 BYTES_PER_VOXEL = 20                 # tsdf, weight and three colour planes, fp32
@@ -41,29 +41,30 @@ def volume_bytes(dims: Sequence[int]) -> int:
     return n * BYTES_PER_VOXEL + n // BLOCK ** 3
 
 
-def memory_cap_bytes(device=None, max_gb: Optional[float] = None) -> float:
-    """max_gb in GB when given; else the rule of chunking.py for parked bytes: min(0.4 of the device, 0.85 of what is free)"""
-    if max_gb is not None:
-        return float(max_gb) * 1e9
-    idx = torch.cuda.current_device() if device is None or getattr(device, "index", None) is None else device.index
-    total = float(torch.cuda.get_device_properties(idx).total_memory)
-    return min(DEFAULT_FRACTION * total, 0.85 * available_bytes(device))
+def _block_dims(dims):
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < BLOCK or any(d % BLOCK for d in (nx, ny, nz)):
+        raise MorpheusHipError(f"TSDF box: dims must be positive multiples of the block side {BLOCK}, got {(nx, ny, nz)}")
+    return nx, ny, nz
+
+
+def _extent(origin, dims, voxel_length) -> str:
+    """the box as the refusals of check_box and check_sparse_box name it"""
+    lo = [float(o) for o in origin]
+    hi = [o + d * float(voxel_length) for o, d in zip(lo, dims)]
+    return (f"box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
+            f"{float(voxel_length):g} is {dims[0]} x {dims[1]} x {dims[2]}")
 
 
 def check_box(origin, dims, voxel_length: float, cap_bytes: float) -> None:
     """Raises MorpheusHipError when the dense box cannot be held: more than 2^31 - 1 voxels (the kernels' index range) or more
     bytes than cap_bytes."""
-    nx, ny, nz = (int(d) for d in dims)
-    if min(nx, ny, nz) < BLOCK or any(d % BLOCK for d in (nx, ny, nz)):
-        raise MorpheusHipError(f"TSDF box: dims must be positive multiples of the block side {BLOCK}, got {(nx, ny, nz)}")
+    nx, ny, nz = _block_dims(dims)
     n, need = nx * ny * nz, volume_bytes((nx, ny, nz))
     if n >= 2 ** 31 or need > cap_bytes:
-        lo = [float(o) for o in origin]
-        hi = [o + d * float(voxel_length) for o, d in zip(lo, (nx, ny, nz))]
         why = "more than 2^31 - 1 voxels" if n >= 2 ** 31 else f"{need / 1e9:.2f} GB of dense storage, over the cap of {cap_bytes / 1e9:.2f} GB"
         raise MorpheusHipError(
-            f"TSDF box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
-            f"{float(voxel_length):g} is {nx} x {ny} x {nz} = {n} voxels: {why}.  Pass a tighter box with bounds=(min, max), or a "
+            f"TSDF {_extent(origin, (nx, ny, nz), voxel_length)} = {n} voxels: {why}.  Pass a tighter box with bounds=(min, max), or a "
             f"larger voxel_length (storage falls with its cube); max_gb= raises the cap.  run_tsdf_fusion(store=\"sparse\") and "
             f"SparseTSDFVolume hold only the blocks that the frames reach.")
 
@@ -85,21 +86,16 @@ def _capacity(capacity_blocks) -> int:
 def check_sparse_box(origin, dims, voxel_length: float, capacity_blocks: int, cap_bytes: float) -> None:
     """Raises MorpheusHipError when the block-sparse store cannot hold the logical box: a side over 32768 voxels, 2^31 blocks or
     more, or more bytes (sparse_bytes) than cap_bytes."""
-    nx, ny, nz = (int(d) for d in dims)
-    if min(nx, ny, nz) < BLOCK or any(d % BLOCK for d in (nx, ny, nz)):
-        raise MorpheusHipError(f"TSDF box: dims must be positive multiples of the block side {BLOCK}, got {(nx, ny, nz)}")
+    nx, ny, nz = _block_dims(dims)
     capacity = _capacity(capacity_blocks)
     blocks = (nx // BLOCK) * (ny // BLOCK) * (nz // BLOCK)
     need = sparse_bytes((nx, ny, nz), capacity)
     side = max(nx, ny, nz) > SPARSE_MAX_SIDE_BLOCKS * BLOCK
     if side or blocks >= 2 ** 31 or need > cap_bytes:
-        lo = [float(o) for o in origin]
-        hi = [o + d * float(voxel_length) for o, d in zip(lo, (nx, ny, nz))]
         why = (f"a side over {SPARSE_MAX_SIDE_BLOCKS * BLOCK} voxels" if side else "more than 2^31 - 1 blocks" if blocks >= 2 ** 31 else
                f"{need / 1e9:.2f} GB ({need} bytes: {BYTES_PER_SLOT + 4} per slot, 4 per block), over the cap of {cap_bytes / 1e9:.2f} GB")
         raise MorpheusHipError(
-            f"sparse TSDF box [{lo[0]:.3f}, {hi[0]:.3f}] x [{lo[1]:.3f}, {hi[1]:.3f}] x [{lo[2]:.3f}, {hi[2]:.3f}] at voxel_length "
-            f"{float(voxel_length):g} is {nx} x {ny} x {nz} voxels = {blocks} blocks with capacity_blocks = {capacity}: {why}.  Pass a "
+            f"sparse TSDF {_extent(origin, (nx, ny, nz), voxel_length)} voxels = {blocks} blocks with capacity_blocks = {capacity}: {why}.  Pass a "
             f"tighter box with bounds=(min, max), a larger voxel_length or a smaller capacity_blocks; max_gb= raises the cap.")
 
 
@@ -156,21 +152,13 @@ def mask8(mask, device=None) -> Optional[torch.Tensor]:
 def _intrinsics(K, pixel_centers: str):
     if pixel_centers not in PIXEL_CENTERS:
         raise MorpheusHipError(f"pixel_centers must be one of {PIXEL_CENTERS}, got {pixel_centers!r}")
-    K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
-    fx, fy, cx, cy = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+    fx, fy, cx, cy = intrinsics(K)
     if pixel_centers == "integer":                                 # Open3D's convention: the same kernels, shifted principal point
         cx, cy = cx + 0.5, cy + 0.5
     return fx, fy, cx, cy
 
 
-def _pose(c2w):
-    """OpenCV camera-to-world [4,4] or [3,4] -> (c2w, w2c) float32 [3,4] host arrays; the inverse is taken in float64"""
-    c = c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w)
-    if c.shape not in ((4, 4), (3, 4)):
-        raise MorpheusHipError(f"c2w must be [4,4] or [3,4], got {c.shape}")
-    m = np.eye(4, dtype=np.float64)
-    m[:3] = c[:3]
-    return np.ascontiguousarray(m[:3].astype(np.float32)), np.ascontiguousarray(np.linalg.inv(m)[:3].astype(np.float32))
+_pose = pose_pair                    # OpenCV camera-to-world -> (c2w, w2c) float32 [3,4]; the name itself, not a call per frame
 
 
 def _depth32(depth, device) -> torch.Tensor:
@@ -178,10 +166,6 @@ def _depth32(depth, device) -> torch.Tensor:
     if t.dim() != 2:
         raise MorpheusHipError(f"depth must be [H,W], got {tuple(t.shape)}")
     return t.to(torch.float32).contiguous()
-
-
-def _host_ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _frame(device, depth, color, K, c2w, mask, stride, pixel_centers):
@@ -202,39 +186,61 @@ def _frame(device, depth, color, K, c2w, mask, stride, pixel_centers):
     return d, c, m, H, W, intr, c2w_h, w2c_h
 
 
-class TSDFVolume:
+_NO_POOL = object()                  # _Volume's capacity_blocks for the dense store
+
+
+class _Volume:
+    """What the two stores share: the constructor's checks, the box as the kernels take it (_box), and extract_mesh around the
+    store's own index-space surface (_index_mesh) and vertex_colors.  A store checks its own box and allocates."""
+
+    def __init__(self, voxel_length: float, sdf_trunc: float, origin, dims, device, capacity_blocks=_NO_POOL):
+        if not (voxel_length > 0 and sdf_trunc > 0):
+            raise MorpheusHipError(f"voxel_length and sdf_trunc must be positive, got {voxel_length}, {sdf_trunc}")
+        if capacity_blocks is not _NO_POOL:                        # refused after the lengths and before the device
+            self.capacity = _capacity(capacity_blocks)
+        self.device = gpu_device(type(self).__name__, device)
+        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
+        self.origin = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
+        self.dims = tuple(int(d) for d in dims)
+        self.blocks = tuple(d // BLOCK for d in self.dims)
+        self.frames = 0
+
+    def _box(self):
+        return (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
+
+    def extract_mesh(self) -> dict:
+        """-> dict(vertices [V,3] fp32 world space, triangles [T,3] int64, colors [V,3] fp32 in [0, 1]): the zero set over the
+        cells whose eight corners were all observed; the two stores give the same vertex and triangle sets (the sparse one
+        ordered by block).  One host synchronisation (to size the outputs)."""
+        iv, tri = self._index_mesh()
+        colors = self.vertex_colors(iv)
+        vertices = torch.from_numpy(self.origin).to(self.device) + (iv + 0.5) * self.voxel_length   # voxel samples sit at centres
+        return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+
+
+class TSDFVolume(_Volume):
     """A dense truncated signed distance volume on the device.  origin: world position of the box's corner; dims = (nx, ny,
     nz) voxels, multiples of 8.  Attributes: tsdf, weight [nx,ny,nz] fp32, color [3,nx,ny,nz] fp32 in [0, 255], active
     [nx/8,ny/8,nz/8] uint8."""
 
     def __init__(self, voxel_length: float, sdf_trunc: float, origin, dims, device="cuda", max_gb: Optional[float] = None):
-        if not (voxel_length > 0 and sdf_trunc > 0):
-            raise MorpheusHipError(f"voxel_length and sdf_trunc must be positive, got {voxel_length}, {sdf_trunc}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise MorpheusHipError(f"TSDFVolume runs on an MI355X only (device is {device}); there is no CPU path")
-        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
-        self.origin = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
-        self.dims = tuple(int(d) for d in dims)
-        check_box(self.origin, self.dims, voxel_length, memory_cap_bytes(device, max_gb))
-        self.device = device
+        super().__init__(voxel_length, sdf_trunc, origin, dims, device)
+        check_box(self.origin, self.dims, voxel_length, memory_cap_bytes(self.device, max_gb))
         nx, ny, nz = self.dims
-        self.blocks = (nx // BLOCK, ny // BLOCK, nz // BLOCK)
-        self.tsdf = torch.zeros(nx, ny, nz, dtype=torch.float32, device=device)
-        self.weight = torch.zeros(nx, ny, nz, dtype=torch.float32, device=device)
-        self.color = torch.zeros(3, nx, ny, nz, dtype=torch.float32, device=device)
-        self.active = torch.zeros(self.blocks, dtype=torch.uint8, device=device)
-        self.frames = 0
+        self.tsdf = torch.zeros(nx, ny, nz, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(nx, ny, nz, dtype=torch.float32, device=self.device)
+        self.color = torch.zeros(3, nx, ny, nz, dtype=torch.float32, device=self.device)
+        self.active = torch.zeros(self.blocks, dtype=torch.uint8, device=self.device)
 
     def integrate(self, depth, color, K, c2w, mask=None, *, depth_scale: float = 1.0, depth_trunc: float = 10.0,
                   stride: int = 4, pixel_centers: str = "half") -> None:
         """One frame: depth [H,W], color [H,W,3] (uint8 RGB8, or floating point in [0, 1]), K [3,3], c2w the OpenCV
         camera-to-world pose, mask [H,W] (pixels with mask <= 0 are not used).  Two launches, no host synchronisation."""
         d, c, m, H, W, (fx, fy, cx, cy), c2w_h, w2c_h = _frame(self.device, depth, color, K, c2w, mask, stride, pixel_centers)
-        box = (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
-        launch("mh_tsdf_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale), float(depth_trunc),
+        box = self._box()
+        launch("mh_tsdf_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, host_ptr(c2w_h), float(depth_scale), float(depth_trunc),
                int(stride), *box, ptr(self.active))
-        launch("mh_tsdf_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(w2c_h), float(depth_scale),
+        launch("mh_tsdf_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, host_ptr(w2c_h), float(depth_scale),
                float(depth_trunc), *box, ptr(self.active), ptr(self.tsdf), ptr(self.weight), ptr(self.color))
         self.frames += 1
 
@@ -246,18 +252,11 @@ class TSDFVolume:
         launch("mh_tsdf_vertex_colors", ptr(index_vertices), V, ptr(self.color), *self.dims, ptr(out))
         return out
 
-    def extract_mesh(self) -> dict:
-        """-> dict(vertices [V,3] fp32 world space, triangles [T,3] int64, colors [V,3] fp32 in [0, 1]): the zero set over the
-        cells whose eight corners were all observed.  One host synchronisation (to size the outputs)."""
-        from .mesh import marching_cubes_masked
-        iv, tri = marching_cubes_masked(self.tsdf, self.weight, 0.0)
-        colors = self.vertex_colors(iv)
-        origin = torch.from_numpy(self.origin).to(self.device)
-        vertices = origin + (iv + 0.5) * self.voxel_length
-        return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+    def _index_mesh(self):
+        return marching_cubes_masked(self.tsdf, self.weight, 0.0)
 
 
-class SparseTSDFVolume:
+class SparseTSDFVolume(_Volume):
     """A truncated signed distance volume that stores only the 8^3 blocks a frame reached (include/morpheus_hip.h, the pooled
     block-sparse store).  origin, dims: the LOGICAL box, as TSDFVolume's but with up to 32768 voxels a side and no limit on the
     voxel count; capacity_blocks: the slots of the pool, fixed at construction (10 240 bytes each).  The block rule and every
@@ -268,37 +267,24 @@ class SparseTSDFVolume:
 
     def __init__(self, voxel_length: float, sdf_trunc: float, origin, dims, capacity_blocks: int, device="cuda",
                  max_gb: Optional[float] = None):
-        if not (voxel_length > 0 and sdf_trunc > 0):
-            raise MorpheusHipError(f"voxel_length and sdf_trunc must be positive, got {voxel_length}, {sdf_trunc}")
-        self.capacity = _capacity(capacity_blocks)
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise MorpheusHipError(f"SparseTSDFVolume runs on an MI355X only (device is {device}); there is no CPU path")
-        self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
-        self.origin = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
-        self.dims = tuple(int(d) for d in dims)
-        check_sparse_box(self.origin, self.dims, voxel_length, self.capacity, memory_cap_bytes(device, max_gb))
-        self.device, self.max_gb = device, max_gb
-        self.blocks = tuple(d // BLOCK for d in self.dims)
-        n = BLOCK ** 3
+        super().__init__(voxel_length, sdf_trunc, origin, dims, device, capacity_blocks)
+        check_sparse_box(self.origin, self.dims, voxel_length, self.capacity, memory_cap_bytes(self.device, max_gb))
+        self.max_gb = max_gb
+        n, device = BLOCK ** 3, self.device
         self.slot = torch.full(self.blocks, -1, dtype=torch.int32, device=device)
         self.slot_block = torch.zeros(self.capacity, dtype=torch.int32, device=device)
         self.counters = torch.zeros(2, dtype=torch.int32, device=device)
         self.tsdf = torch.zeros(self.capacity, n, dtype=torch.float32, device=device)
         self.weight = torch.zeros(self.capacity, n, dtype=torch.float32, device=device)
         self.color = torch.zeros(3, self.capacity, n, dtype=torch.float32, device=device)
-        self.frames = 0
-
-    def _box(self):
-        return (float(self.origin[0]), float(self.origin[1]), float(self.origin[2]), self.voxel_length, self.sdf_trunc) + self.blocks
 
     def integrate(self, depth, color, K, c2w, mask=None, *, depth_scale: float = 1.0, depth_trunc: float = 10.0,
                   stride: int = 4, pixel_centers: str = "half") -> None:
         """One frame, as TSDFVolume.integrate.  Two launches, no host synchronisation."""
         d, c, m, H, W, (fx, fy, cx, cy), c2w_h, w2c_h = _frame(self.device, depth, color, K, c2w, mask, stride, pixel_centers)
-        launch("mh_tsdf_sparse_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+        launch("mh_tsdf_sparse_touch", ptr(d), ptr(m), H, W, fx, fy, cx, cy, host_ptr(c2w_h), float(depth_scale),
                float(depth_trunc), int(stride), *self._box(), self.capacity, ptr(self.slot), ptr(self.slot_block), ptr(self.counters))
-        launch("mh_tsdf_sparse_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, _host_ptr(w2c_h), float(depth_scale),
+        launch("mh_tsdf_sparse_integrate", ptr(d), ptr(c), ptr(m), H, W, fx, fy, cx, cy, host_ptr(w2c_h), float(depth_scale),
                float(depth_trunc), *self._box(), self.capacity, ptr(self.slot_block), ptr(self.counters), ptr(self.tsdf),
                ptr(self.weight), ptr(self.color))
         self.frames += 1
@@ -314,8 +300,7 @@ class SparseTSDFVolume:
 
     def check(self) -> int:
         """-> the number of allocated blocks; raises when the pool overflowed.  One host read."""
-        wanted, overflow = self.counters.tolist()
-        return self._checked(wanted, overflow)
+        return self._checked(*self.counters.tolist())
 
     def allocated_blocks(self) -> torch.Tensor:
         """-> int64 [n]: the linear ids (bx*nby + by)*nbz + bz of the blocks with storage, ascending.  One host read."""
@@ -367,34 +352,31 @@ class SparseTSDFVolume:
     def marching_cubes(self, isovalue: float = 0.0):
         """-> (vertices fp32 [V,3] in the logical box's index space, triangles int64 [T,3]): the masked marching cubes over the
         allocated blocks, in ascending block id whatever the slot order.  One host read (sizes, slot counter, overflow flag)."""
-        lib = _lib.load()
-        dev = self.device
+        wbytes = _lib.load().mh_mc_sparse_workspace_bytes(self.capacity)
         live = self.counters[0].clamp(max=self.capacity)
-        ids = torch.where(torch.arange(self.capacity, device=dev) < live, self.slot_block, INT32_MAX)
+        ids = torch.where(torch.arange(self.capacity, device=self.device) < live, self.slot_block, INT32_MAX)
         sorted_blocks = ids.sort().values.to(torch.int32).contiguous()
-        ws = torch.empty(lib.mh_mc_sparse_workspace_bytes(self.capacity), dtype=torch.uint8, device=dev)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)
         args = (ptr(self.tsdf), ptr(self.weight), ptr(self.slot), ptr(sorted_blocks), ptr(self.counters), *self.blocks, self.capacity,
-                float(isovalue), ptr(ws))
-        launch("mh_mc_count_sparse", *args, ptr(counts))
-        V, T, wanted, overflow = torch.cat([counts, self.counters.long()]).tolist()
-        self._checked(wanted, overflow)
-        if V >= 2 ** 31 or T >= 2 ** 31:
-            raise MorpheusHipError(f"SparseTSDFVolume: {V} vertices / {T} triangles do not fit int32 indices")
-        vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
-        triangles = torch.empty(T, 3, dtype=torch.int32, device=dev)
-        if V or T:
-            launch("mh_mc_emit_sparse", *args, ptr(vertices), ptr(triangles))
-        return vertices, triangles.long()
+                float(isovalue))
 
-    def extract_mesh(self) -> dict:
-        """As TSDFVolume.extract_mesh: dict(vertices world space, triangles, colors); the same vertex and triangle sets as the
-        dense volume's (ordered by block).  One host synchronisation."""
-        iv, tri = self.marching_cubes(0.0)
-        colors = self.vertex_colors(iv)
-        origin = torch.from_numpy(self.origin).to(self.device)
-        vertices = origin + (iv + 0.5) * self.voxel_length
-        return {"vertices": vertices.contiguous(), "triangles": tri, "colors": colors}
+        def check(V, T, wanted, overflow):                         # the pool's overflow first: it explains any count
+            self._checked(wanted, overflow)
+            if V >= 2 ** 31 or T >= 2 ** 31:
+                raise MorpheusHipError(f"SparseTSDFVolume: {V} vertices / {T} triangles do not fit int32 indices")
+
+        return _count_then_emit("mh_mc_count_sparse", "mh_mc_emit_sparse", args, args, wbytes, self.device, self.counters, check)
+
+    def _index_mesh(self):
+        return self.marching_cubes(0.0)
+
+
+def _frames(c2w_list, depth_list, mask_list, device):
+    """per frame -> (depth fp32 [H,W], mask uint8 [H,W] or None, H, W, c2w [3,4] host float32), checked to be on the device"""
+    for f, (c2w, depth) in enumerate(zip(c2w_list, depth_list)):
+        d = _depth32(depth, device)
+        m = mask8(None if mask_list is None else mask_list[f], device)
+        require_gpu(d, m)
+        yield d, m, d.shape[0], d.shape[1], _pose(c2w)[0]
 
 
 def count_touched_blocks(K, c2w_list, depth_list, mask_list, origin, dims, voxel_length, sdf_trunc, *, depth_scale=1.0,
@@ -406,12 +388,8 @@ def count_touched_blocks(K, c2w_list, depth_list, mask_list, origin, dims, voxel
     blocks = tuple(int(d) // BLOCK for d in dims)
     o = np.asarray(origin, np.float64).reshape(3).astype(np.float32)
     active = torch.zeros(blocks, dtype=torch.uint8, device=device)
-    for f, (c2w, depth) in enumerate(zip(c2w_list, depth_list)):
-        d = _depth32(depth, device)
-        m = mask8(None if mask_list is None else mask_list[f], device)
-        require_gpu(d, m)
-        c2w_h, _ = _pose(c2w)
-        launch("mh_tsdf_sparse_mark", ptr(d), ptr(m), d.shape[0], d.shape[1], fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+    for d, m, H, W, c2w_h in _frames(c2w_list, depth_list, mask_list, device):
+        launch("mh_tsdf_sparse_mark", ptr(d), ptr(m), H, W, fx, fy, cx, cy, host_ptr(c2w_h), float(depth_scale),
                float(depth_trunc), int(stride), float(o[0]), float(o[1]), float(o[2]), float(voxel_length), float(sdf_trunc), *blocks,
                ptr(active))
     return int(active.sum(dtype=torch.int64))
@@ -424,12 +402,8 @@ def frame_bounds(K, c2w_list, depth_list, mask_list=None, *, depth_scale=1.0, de
     fx, fy, cx, cy = _intrinsics(K, pixel_centers)
     device = torch.device(device)
     acc = torch.tensor([INT32_MAX] * 3 + [INT32_MIN] * 3, dtype=torch.int32, device=device)
-    for f, (c2w, depth) in enumerate(zip(c2w_list, depth_list)):
-        d = _depth32(depth, device)
-        m = mask8(None if mask_list is None else mask_list[f], device)
-        require_gpu(d, m)
-        c2w_h, _ = _pose(c2w)
-        launch("mh_tsdf_bounds", ptr(d), ptr(m), d.shape[0], d.shape[1], fx, fy, cx, cy, _host_ptr(c2w_h), float(depth_scale),
+    for d, m, H, W, c2w_h in _frames(c2w_list, depth_list, mask_list, device):
+        launch("mh_tsdf_bounds", ptr(d), ptr(m), H, W, fx, fy, cx, cy, host_ptr(c2w_h), float(depth_scale),
                float(depth_trunc), int(stride), ptr(acc))
     return decode_bounds(acc.cpu().numpy())
 
@@ -484,9 +458,7 @@ def run_tsdf_fusion(K, H, W, c2w_list, depth_list, rgb_list, mask_list=None, ski
     for f in range(n):
         if tuple(depth_list[f].shape) != (H, W):
             raise MorpheusHipError(f"run_tsdf_fusion: depth {f} is {tuple(depth_list[f].shape)}, expected {(H, W)}")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise MorpheusHipError(f"run_tsdf_fusion runs on an MI355X only (device is {device}); there is no CPU path")
+    device = gpu_device("run_tsdf_fusion", device)
     if bounds is None:
         found = frame_bounds(K, c2w_list, depth_list, mask_list, depth_scale=depth_scale, depth_trunc=depth_trunc, stride=stride,
                              pixel_centers=pixel_centers, device=device) if n else None
@@ -529,7 +501,6 @@ def back_proj_frame(K, H, W, c2w, depth, rgb, save_path=None, mask=None, depth_s
 
 
 def _save(path, mesh) -> None:
-    from .mesh import write_ply
     d = os.path.dirname(os.fspath(path))
     if d:
         os.makedirs(d, exist_ok=True)

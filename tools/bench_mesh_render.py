@@ -15,7 +15,6 @@ and the sweep of the split (small_area) over depth_ms.  Kernel-level times: run 
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -28,7 +27,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from morpheus_amd import _lib, harness, mesh, meshrender  # noqa: E402
+from morpheus_amd import _lib, geometry, harness, mesh, meshrender  # noqa: E402
 from morpheus_amd._lib import check, ptr, stream  # noqa: E402
 
 SWEEP = (16, 64, 256, 1024, 4096, 1 << 30)
@@ -90,7 +89,7 @@ def main():
     lib = _lib.load()
     model = harness.build_model("b", dev)
     w2c = meshrender.world_to_camera(look_at((0.4, -2.4, 0.7)))
-    w2c_p = w2c.ctypes.data_as(ctypes.c_void_p)
+    w2c_p = geometry.host_ptr(w2c)
     lines = [f"# tools/bench_mesh_render.py: model b, {a.view} x {a.view} view x scale; every column 3 warm-up + {a.reps} timed "
              f"repetitions, ms per call as median [min .. max]; extract_ms: wall around one call; the others: HIP events around "
              f"{BATCH} calls / {BATCH}", f"# device name reported by torch: {torch.cuda.get_device_name(0)}"]
