@@ -378,6 +378,11 @@ int mh_field_bwd_fused_b3(const float *xc, const float *sdf, const float *albedo
                           const float *g_albedo, const void *w3T, const float *beta, int32_t n_bands, int32_t with_color,
                           const float *acts, float *dgeo_scratch, float *workspace, float *raw, int32_t accumulate, float *g_xc,
                           float *g_feat_s, float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream);
+/* Tuning knob (process-wide) of mh_field_bwd_fused_b3: a with-colour call of at least this many points runs the pair form of its
+ * two launches (512-thread workgroups, two waves per SIMD that share a tile's chain and weight-gradient work); smaller calls and
+ * the sdf-only pass run the one-wave kernels.  Every output is bit-identical either way.  set < 0: query only.  Returns the
+ * value in force (default 0: every with-colour call). */
+int64_t mh_field_bwd_pair_min_points(int64_t set);
 /* ---- optimiser step over the flat parameter bucket (the step after the path) ---- */
 /* Replaces torch.optim.Adam(model.get_params_all(lr), betas=(0.9,0.99), eps=1e-15).step() of morpheus.py:154-155,
  * :1401-1424 (no weight decay, no amsgrad).  params/grads/exp_avg/exp_avg_sq: [n] fp32 device buffers, 16-byte aligned.

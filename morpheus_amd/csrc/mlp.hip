@@ -31,6 +31,7 @@
 //    loop is paid in full and the design effort goes into having few of them.
 #include "mlp_dev.h"
 #include <stdlib.h>
+#include <atomic>
 
 
 __shared__ f32x4 lds_w[4096];  // 64 KB: one layer's A fragments  [mt][q][lane] float4
@@ -518,7 +519,9 @@ __global__ __launch_bounds__(FIELD_THREADS, 1) void field_fwd_kernel(const float
 // operand; row stride 36 floats keeps ds_read_b128 conflict-free and 16-byte aligned) and accumulates dW_l.
 // One wave per SIMD (up to 512 registers), persistent 4-wave blocks, transposed weight packs resident in LDS; the two
 // nets are two launches (color first: it hands d(geo) to the sdf launch through a 4 KB-per-tile scratch) so that either
-// accumulator set fits.  Per-WORKGROUP partial sums (the four waves add up through LDS) go to the workspace in wgrad_kernel's [chunk][out x in] format and
+// accumulator set fits.  (These one-wave kernels run the sdf-only pass and the fp32 arithmetic; the with-colour pass of the bf16x3
+// arithmetic runs the PAIR form further down -- two waves per SIMD, each with half of a tile's work -- and is bit for bit these.)
+// Per-WORKGROUP partial sums (the four waves add up through LDS) go to the workspace in wgrad_kernel's [chunk][out x in] format and
 // wgrad_reduce_kernel finishes as before.
 // =====================================================================================
 #define FUSED_THREADS 256
@@ -1256,6 +1259,673 @@ __global__ __launch_bounds__(FUSED_THREADS, 1) void field_fused_sdf_kernel(
             ws[part.db[1] + pchunk * 64 + 32 * mt + i] = b1[mt];
             ws[part.db[0] + pchunk * 64 + 32 * mt + i] = b0[mt];
         }
+    }
+}
+
+// =====================================================================================
+// canonical field, fused backward, PAIR form (bf16x3 arithmetic, the two with-colour launches): two waves per SIMD.
+//
+// The one-wave kernels above keep a net's whole weight-gradient set in one wave (192 / 160 registers), so one wave per SIMD
+// runs loads, chain MFMAs, wait, slicing and weight-gradient MFMAs strictly one after the other with nothing to fill the
+// gaps.  Here a 512-thread workgroup holds 4 PAIRS: waves w and w + 4 (half k = 0 / 1) walk the tiles wave w walks above
+// (tile = 4 b + w, stride 4 gridDim), both on the SAME tile, and share the work so that either needs at most 256 registers:
+//   * chain: wave k computes out tile k of each layer (sdf layer 0, three input-gradient tiles: wave 0 the encoding / topo
+//     tiles 0 and 1, wave 1 the hash tile 2), masks it and drops its 32 dPre rows into the pair's fp32 scratch; after the
+//     workgroup barrier both read all 64 rows back, column-wise as the next layer's B operand and row-wise as the weight
+//     gradient's A operand (the scratch of the one-wave form, now shared by two waves);
+//   * weight gradients: wave k owns dW[all out tiles][in tile k] (sdf layer 0: wave 0 in tile 2, wave 1 in tiles 0 and 1 --
+//     72 MFMAs per wave and layer either way), so it loads and slices ONLY its own 32 (64) parked rows: 6 accumulator tiles
+//     = 96 registers per wave in either launch.  A bias sum (and d beta) lives in one wave of the pair.
+// Every accumulator sees the MFMA sequence of the one-wave form over the same tiles and the pairs add up in the same fixed
+// order, so every output is bit for bit the one-wave form's.
+// Scratch: two buffers per pair used in turn (an even number of exchanges per tile: 4 colour, 2 sdf), so ONE barrier per
+// exchange: a buffer written in exchange n was last read in exchange n - 2, and barrier n - 1 lies between.
+// Barriers: every wave of a workgroup makes pair_walk().trips trips -- the walk of the workgroup's first pair, the longest --
+// and meets the same barriers on each; a pair past its last tile re-runs the call's last tile with `live` off for every lane
+// (all-zero gradients: nothing stored, every sum gets + 0).  No barrier sits under a condition.
+// =====================================================================================
+#define PAIR_THREADS 512
+#define PAIR_RED_FLOATS (6 * 1024 + 8 * 64)   // one wave's share of the end-of-kernel sum: 6 accumulator tiles + up to 8 rows
+
+#define PAIR_LANE_ANEW                                            \
+    int lane_anew = threadIdx.x & 63;                             \
+    asm volatile("" : "+v"(lane_anew));                           \
+    const int lane = lane_anew, pt = lane & 31, h = lane >> 5, i = lane & 31
+
+struct PairWalk {
+    int64_t chunk, n_chunks, trips;
+};
+__device__ __forceinline__ PairWalk pair_walk(int pair, int64_t n_tiles) {
+    PairWalk w;
+    w.n_chunks = 4 * (int64_t)gridDim.x;
+    const int64_t first = 4 * (int64_t)blockIdx.x;        // the chunk of the workgroup's pair 0: no pair of it walks more tiles
+    w.chunk = first + pair;
+    w.trips = first < n_tiles ? (n_tiles - first + w.n_chunks - 1) / w.n_chunks : 0;
+    return w;
+}
+
+template <int N_F4>
+__device__ __forceinline__ void stage_pair(const float *__restrict__ g) {
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(g);
+    for (int i = threadIdx.x; i < N_F4; i += PAIR_THREADS) lds_fused[i] = src[i];
+}
+
+// scr_put for ONE out tile `t` (the wave's own)
+__device__ __forceinline__ void scr_put_tile(float *__restrict__ scr, const float (&v)[16], int t, int pt, int h) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) scr[(32 * t + acc_row(r, h)) * SCR_STRIDE + pt] = v[r];
+}
+
+// mfma_layer_z_b3 for NT consecutive out tiles from `t0` of the layer's MT: per accumulator the same products in the same order
+template <int KS, int MT, int NT, int S_RUN = KS / 8>
+__device__ __forceinline__ void mfma_tiles_z_b3(const f32x4 *__restrict__ w, int t0, const float (&bin)[KS], f32x16 (&acc)[NT], int lane) {
+    static_assert(KS % 8 == 0 && S_RUN >= 1 && S_RUN <= KS / 8 && NT <= MT, "k16 steps");
+    constexpr int S = KS / 8, PL = MT * S * 64;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    w += t0 * S * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < S_RUN; s++) {
+        Frag bh, bm, bl;
+#pragma unroll
+        for (int e2 = 0; e2 < 4; e2++) split2(bin[8 * s + 2 * e2], bin[8 * s + 2 * e2 + 1], bh.u[e2], bm.u[e2], bl.u[e2]);
+        Frag ah[NT], am[NT], al[NT];
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            ah[t].f = w[0 * PL + (t * S + s) * 64];
+            am[t].f = w[1 * PL + (t * S + s) * 64];
+            al[t].f = w[2 * PL + (t * S + s) * 64];
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t].h, bh.h, s == 0 ? zero : acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t].h, bm.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bl.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t].h, bh.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bm.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bh.h, acc[t], 0, 0, 0);
+        // keep step s + 1's operand reads behind step s: hoisted, the steps' fragments (12 NT registers each) pile up beside the
+        // accumulators and spill; the partner wave covers the LDS latency instead
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the same with the layer's 64 dPre rows taken from the pair's scratch (column form: lane = point), eight values per k16 step right
+// before the step's slicing -- 8 live registers instead of 32 beside the accumulators
+template <int MT, int NT>
+__device__ __forceinline__ void mfma_tiles_scr_b3(const f32x4 *__restrict__ w, int t0, const float *__restrict__ scr, int pt, int h,
+                                                  f32x16 (&acc)[NT], int lane) {
+    constexpr int S = 4, PL = MT * S * 64;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    w += t0 * S * 64 + lane;
+    scr += 4 * h * SCR_STRIDE + pt;
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+        float bin[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) bin[e] = scr[(32 * (s >> 1) + acc_row(8 * (s & 1) + e, 0)) * SCR_STRIDE];
+        Frag bh, bm, bl;
+#pragma unroll
+        for (int e2 = 0; e2 < 4; e2++) split2(bin[2 * e2], bin[2 * e2 + 1], bh.u[e2], bm.u[e2], bl.u[e2]);
+        Frag ah[NT], am[NT], al[NT];
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            ah[t].f = w[0 * PL + (t * S + s) * 64];
+            am[t].f = w[1 * PL + (t * S + s) * 64];
+            al[t].f = w[2 * PL + (t * S + s) * 64];
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t].h, bh.h, s == 0 ? zero : acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t].h, bm.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bl.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[t].h, bh.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bm.h, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bh.h, acc[t], 0, 0, 0);
+        // keep step s + 1's operand reads behind step s: hoisted, the steps' fragments (12 NT registers each) pile up beside the
+        // accumulators and spill; the partner wave covers the LDS latency instead
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the two halves of dw_mma_b3: both waves of a pair multiply, ONE of them keeps the bias row sums
+__device__ __forceinline__ void dw_bias(const RowFrag &a, float &bsum) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) bsum += (a.v[j][0] + a.v[j][1]) + (a.v[j][2] + a.v[j][3]);
+}
+template <int NI>
+__device__ __forceinline__ void dw_mfma_b3(const RowFrag &a, const RowSl *__restrict__ b, f32x16 (&acc)[NI]) {
+    RowSl as;
+    row_slices(a, as);
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.l[s].h, b[n].h[s].h, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[n].m[s].h, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[n].l[s].h, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[n].h[s].h, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[n].m[s].h, acc[n], 0, 0, 0);
+#pragma unroll
+        for (int n = 0; n < NI; n++) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[n].h[s].h, acc[n], 0, 0, 0);
+    }
+}
+// dw_mfma_b3<2> on two accumulators that are not neighbours in an array
+__device__ __forceinline__ void dw_mfma_b3_2(const RowFrag &a, const RowSl *__restrict__ b, f32x16 &acc0, f32x16 &acc1) {
+    RowSl as;
+    row_slices(a, as);
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.l[s].h, b[0].h[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.l[s].h, b[1].h[s].h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[0].m[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[1].m[s].h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[0].l[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[1].l[s].h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[0].h[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.m[s].h, b[1].h[s].h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[0].m[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[1].m[s].h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[0].h[s].h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as.h[s].h, b[1].h[s].h, acc1, 0, 0, 0);
+    }
+}
+// dw_store for the in tiles n0 .. n0 + NI - 1 of a layer
+template <int NI>
+__device__ __forceinline__ void dw_store_at(float *__restrict__ dw, const f32x16 (&acc)[NI], int mt, int in_pad, int n0, int i, int h) {
+#pragma unroll
+    for (int n = 0; n < NI; n++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) dw[(int64_t)(32 * mt + acc_row(r, h)) * in_pad + 32 * (n0 + n) + i] = acc[n][r];
+}
+
+// ---- color_net, pair form: the phases of field_fused_color_kernel<true>, each wave its half --------------------------
+__global__ __launch_bounds__(PAIR_THREADS, 1) void field_pair_color_kernel(
+    const float *__restrict__ albedo, const float *__restrict__ g_albedo, const float *__restrict__ wpackT,
+    const float *__restrict__ acts, float *__restrict__ dgeo_scr, float *__restrict__ g_feat_c, float *__restrict__ ws,
+    FusedPart part, uint32_t *__restrict__ gmax, int64_t M, int64_t n_tiles) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: uniform branches on k)
+    const int pair = wave & 3, k = wave >> 2;              // waves w and w + 4 are the halves k = 0, 1 of pair w
+    const int pt = lane & 31, h = lane >> 5, i = lane & 31;
+    constexpr int W_F4 = FUSED_TC2(1) + FUSED_TC1(1) + FUSED_TC0(1);
+    stage_pair<W_F4>(wpackT);
+    float *scrX = reinterpret_cast<float *>(lds_fused + W_F4) + pair * (2 * SCR_FLOATS), *scrY = scrX + SCR_FLOATS;
+    __syncthreads();
+    // dW [out tile][in tile k] of c2 (1 out tile), c1, c0 (2) and of the geo rows of the sdf net's last layer: 6 tiles
+    f32x16 w2[1], w1[2][1], w0[2][1], wg[1];
+    acc_zero<1>(w2);
+    acc_zero<1>(wg);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) {
+        acc_zero<1>(w1[mt]);
+        acc_zero<1>(w0[mt]);
+    }
+    float b2 = 0.f, bg = 0.f;          // bias sums of c2 and of the geo rows: wave 0 of the pair
+    float b1 = 0.f, b0 = 0.f;          // of out tile k of c1, c0
+    uint32_t max_c = 0;
+    const PairWalk walk = pair_walk(pair, n_tiles);
+    RowFrag B[1];
+    for (int64_t trip = 0; trip < walk.trips; trip++) {
+        const int64_t want = walk.chunk + trip * walk.n_chunks;
+        const bool active = want < n_tiles;               // (wave-uniform) past the pair's last tile: the barriers only
+        const int64_t tile_id = active ? want : n_tiles - 1;
+        const int64_t p = tile_id * TILE + pt;
+        const bool live = active && p < M;
+        const float *atile = acts + tile_id * (int64_t)(FIELD_ACT_ROWS * TILE);
+        const uint32_t *masks = reinterpret_cast<const uint32_t *>(atile + FIELD_HID_ROWS * TILE);
+        const f32x4 *wt = lds_fused;
+        RowFrag A;
+        RowSl Bs[1];
+        f32x16 acc[1];
+        float own[16];
+        // dQ2 = g_albedo * a * (1 - a): both waves hold all of it
+        float d2[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) d2[r] = 0.f;
+        if (g_albedo && live && h == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float a = albedo[p * 3 + c];
+                d2[c] = g_albedo[p * 3 + c] * a * (1.0f - a);
+            }
+        }
+        // the ReLU mask bits of the wave's own out tile k: bit r <-> accumulator register r
+        const uint32_t mw3 = masks[3 * 64 + lane] >> (16 * k), mw2 = masks[2 * 64 + lane] >> (16 * k);
+        // ---- layer c2: input C2 = rows 352..415
+        row_load_async(B[0], atile, 352 + 32 * k + i, h);
+        if (k == 0) scr_put<1>(scrX, d2, pt, h);
+        mfma_tiles_z_b3<16, 2, 1, 1>(wt, k, d2, acc, lane);       // (rows 8.. of dQ2 are zeros: k16 step 0 only)
+        wt += FUSED_TC2(1);
+#pragma unroll
+        for (int r = 0; r < 16; r++) own[r] = mask_bit(mw3, r, acc[0][r]);             // mask C2 -> dQ1, tile k
+        __syncthreads();                                  // exchange 1 of 4: dQ2 in X
+        scr_get(A, scrX, i, h);
+        fused_wait<1>(B);
+        row_slices(B[0], Bs[0]);
+        if (k == 0) dw_bias(A, b2);
+        dw_mfma_b3<1>(A, Bs, w2);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- layer c1: input C1 = rows 288..351
+        row_load_async(B[0], atile, 288 + 32 * k + i, h);
+        scr_put_tile(scrY, own, k, pt, h);
+        __syncthreads();                                  // exchange 2 of 4: dQ1 in Y
+        mfma_tiles_scr_b3<2, 1>(wt, k, scrY, pt, h, acc, lane);
+        wt += FUSED_TC1(1);
+#pragma unroll
+        for (int r = 0; r < 16; r++) own[r] = mask_bit(mw2, r, acc[0][r]);             // mask C1 -> dQ0, tile k
+        fused_wait<1>(B);
+        row_slices(B[0], Bs[0]);
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++) {
+            scr_get(A, scrY, 32 * mt + i, h);
+            if (k == mt) dw_bias(A, b1);
+            dw_mfma_b3<1>(A, Bs, w1[mt]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- layer c0: input [hash_c | geo] = rows 224..287
+        row_load_async(B[0], atile, 224 + 32 * k + i, h);
+        scr_put_tile(scrX, own, k, pt, h);
+        __syncthreads();                                  // exchange 3 of 4: dQ0 in X
+        mfma_tiles_scr_b3<2, 1>(wt, k, scrX, pt, h, acc, lane);   // wave 0: d(hash_c), wave 1: d(geo)
+        if (k == 0) {
+            if (live && g_feat_c) {
+                f32x4 *o = reinterpret_cast<f32x4 *>(g_feat_c + p * 32 + 16 * h);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    f32x4 v;
+#pragma unroll
+                    for (int c = 0; c < 4; c++) v[c] = acc[0][4 * q + c];
+                    o[q] = v;
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) max_c = max(max_c, __float_as_uint(fabsf(acc[0][r])));
+            }
+        } else if (active) {   // d(geo), accumulator order, for the sdf launch: [tile][lane][16]
+            f32x4 *o = reinterpret_cast<f32x4 *>(dgeo_scr + (tile_id * 64 + lane) * 16);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                f32x4 v;
+#pragma unroll
+                for (int c = 0; c < 4; c++) v[c] = acc[0][4 * q + c];
+                o[q] = v;
+            }
+        }
+        fused_wait<1>(B);
+        row_slices(B[0], Bs[0]);
+        RowFrag Bg[1];                                    // the sdf net's parked S2 rows (160..223): land under the c0 weight gradient
+        row_load_async(Bg[0], atile, 160 + 32 * k + i, h);
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++) {
+            scr_get(A, scrX, 32 * mt + i, h);
+            if (k == mt) dw_bias(A, b0);
+            dw_mfma_b3<1>(A, Bs, w0[mt]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- dW_s2, geo rows: A = d(geo) rows (wave 1 holds them) through the scratch, B = S2 rows
+        if (k == 1) {
+            float dg[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) dg[r] = acc[0][r];
+            scr_put<1>(scrY, dg, pt, h);
+        }
+        __syncthreads();                                  // exchange 4 of 4: d(geo) in Y
+        fused_wait<1>(Bg);
+        row_slices(Bg[0], Bs[0]);
+        scr_get(A, scrY, i, h);
+        if (k == 0) dw_bias(A, bg);
+        dw_mfma_b3<1>(A, Bs, wg);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (gmax) {            // (only the waves k == 0 have seen d(hash_c))
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) max_c = max(max_c, (uint32_t)__shfl_xor((int)max_c, o));
+        if (lane == 0 && max_c) atomicMax(gmax + 1, max_c);
+    }
+    bg += __shfl_xor(bg, 32);
+    b2 += __shfl_xor(b2, 32);
+    b1 += __shfl_xor(b1, 32);
+    b0 += __shfl_xor(b0, 32);
+    // the workgroup's partial = the sum of its four pairs', pairs 1, 2, 3 added to pair 0 in that order, half k to half k
+    float *red = reinterpret_cast<float *>(lds_fused) + k * PAIR_RED_FLOATS;
+    for (int src = 1; src < 4; src++) {
+        __syncthreads();
+        if (pair == src) {
+            float *q = acc_to_lds<1>(w2, red, lane);
+            q = acc_to_lds<1>(w1[0], q, lane);
+            q = acc_to_lds<1>(w1[1], q, lane);
+            q = acc_to_lds<1>(w0[0], q, lane);
+            q = acc_to_lds<1>(w0[1], q, lane);
+            q = acc_to_lds<1>(wg, q, lane);
+            q[0 * 64 + lane] = b2;
+            q[1 * 64 + lane] = b1;
+            q[2 * 64 + lane] = b0;
+            q[3 * 64 + lane] = bg;
+        }
+        __syncthreads();
+        if (pair == 0) {
+            const float *q = acc_add_lds<1>(w2, red, lane);
+            q = acc_add_lds<1>(w1[0], q, lane);
+            q = acc_add_lds<1>(w1[1], q, lane);
+            q = acc_add_lds<1>(w0[0], q, lane);
+            q = acc_add_lds<1>(w0[1], q, lane);
+            q = acc_add_lds<1>(wg, q, lane);
+            b2 += q[0 * 64 + lane];
+            b1 += q[1 * 64 + lane];
+            b0 += q[2 * 64 + lane];
+            bg += q[3 * 64 + lane];
+        }
+    }
+    if (pair != 0) return;
+    // partial sums of this workgroup, in tile k of every layer (c0, c1, c2 = part.dw[0..2])
+    const int64_t pchunk = blockIdx.x;
+    dw_store_at<1>(ws + part.dw[2] + pchunk * 32 * 64, w2, 0, 64, k, i, h);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) {
+        dw_store_at<1>(ws + part.dw[1] + pchunk * 64 * 64, w1[mt], mt, 64, k, i, h);
+        dw_store_at<1>(ws + part.dw[0] + pchunk * 64 * 64, w0[mt], mt, 64, k, i, h);
+    }
+    dw_store_at<1>(ws + part.dw_s2 + pchunk * 64 * 64, wg, 0, 64, k, i, h);      // out tile 0 (the geo rows) of the sdf net's last layer
+    if (h == 0) {
+        if (k == 0) {
+            ws[part.db[2] + pchunk * 32 + i] = b2;
+            ws[part.db_s2 + pchunk * 64 + i] = bg;
+        }
+        ws[part.db[1] + pchunk * 64 + 32 * k + i] = b1;
+        ws[part.db[0] + pchunk * 64 + 32 * k + i] = b0;
+    }
+}
+
+// ---- sdf_net (+ Laplace density), pair form: the phases of field_fused_sdf_kernel<true, true>, each wave its half -----
+__global__ __launch_bounds__(PAIR_THREADS, 1) void field_pair_sdf_kernel(
+    const float *__restrict__ xc, const float *__restrict__ sdf, const float *__restrict__ g_sdf,
+    const float *__restrict__ g_sigma, const float *__restrict__ wpackT, const float *__restrict__ beta_p, int n_bands,
+    const float *__restrict__ acts, const float *__restrict__ dgeo_scr, float *__restrict__ g_xc,
+    float *__restrict__ g_feat_s, float *__restrict__ g_topo, float *__restrict__ ws,
+    FusedPart part, uint32_t *__restrict__ gmax, int64_t M, int64_t n_tiles) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: uniform branches on k)
+    const int pair = wave & 3, k = wave >> 2;
+    constexpr int W_F4 = FUSED_TS2(1) + FUSED_TS1(1) + FUSED_TS0(1);
+    stage_pair<W_F4>(wpackT + 4 * (FUSED_TC2(1) + FUSED_TC1(1) + FUSED_TC0(1)));
+    float *scrX = reinterpret_cast<float *>(lds_fused + W_F4) + pair * (2 * SCR_FLOATS), *scrY = scrX + SCR_FLOATS;
+    __syncthreads();
+    // dW [out tile][in tile(s)]: s1 in tile k; s0 wave 0: in tile 2 (wa), wave 1: in tiles 0 (wa) and 1 (wb) -- 6 tiles at most.
+    // Wave 0 has no second s0 tile: there wb holds the two input-gradient tiles of the layer-0 chain while they are needed (they
+    // start from zero in every tile), so that both waves fit the same 96 registers.  The sdf row of s2 is `wsdf` as in the one-wave
+    // form, here for the in tile k alone; the geo rows' are the colour launch's
+    f32x16 w1[2][1], wa[2][1], wb[2];
+    acc_zero<2>(wb);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) {
+        acc_zero<1>(w1[mt]);
+        acc_zero<1>(wa[mt]);
+    }
+    float wsdf = 0.f;
+    float bsdf = 0.f, gb_acc = 0.f;    // every wave sums them, wave 0 of the pair hands them on
+    float b1 = 0.f, b0 = 0.f;          // of out tile k of s1, s0
+    uint32_t max_s = 0;
+    const float beta = *beta_p;
+    // the Laplace derivative's three quotients of beta, once and in scalar registers (per lane they are four more registers that live
+    // through every phase of every tile)
+    const float half_ib2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(0.5f / (beta * beta))));
+    const float one_ib2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (beta * beta))));
+    const float one_ib = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / beta)));
+    const PairWalk walk = pair_walk(pair, n_tiles);
+    RowFrag B[2];
+    for (int64_t trip = 0; trip < walk.trips; trip++) {
+        const int64_t want = walk.chunk + trip * walk.n_chunks;
+        const bool active = want < n_tiles;               // (wave-uniform) past the pair's last tile: the barriers only
+        const int64_t tile_id = active ? want : n_tiles - 1;
+        // the lane's coordinates anew in every phase: formed once, the per-lane addresses and constants the compiler derives from them
+        // ahead of time (some 35 registers) live beside the accumulators through every phase and are spilled
+        PAIR_LANE_ANEW;
+        const int64_t p = tile_id * TILE + pt;
+        const bool live = active && p < M;
+        const float *atile = acts + tile_id * (int64_t)(FIELD_ACT_ROWS * TILE);
+        const uint32_t *masks = reinterpret_cast<const uint32_t *>(atile + FIELD_HID_ROWS * TILE);
+        const f32x4 *wt = lds_fused;
+        RowFrag A;
+        f32x16 acc[1];
+        float own[16];
+        // dP2 = [d geo | d sdf]: both waves hold all of it
+        float gs = 0.f, gbeta = 0.f;
+        if (live && h == 0) {
+            const float s = sdf[p];
+            if (g_sdf) gs = g_sdf[p];
+            if (g_sigma) {
+                const float gsg = g_sigma[p];
+                const float sg = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
+                const float a = fabsf(s) / beta;
+                const float ex = expf(-a);
+                gs += gsg * (-half_ib2 * sg * sg * ex);
+                gbeta = gsg * (-one_ib2 * laplace_unit(s, beta) + one_ib * (0.5f * sg * ex * (fabsf(s) / (beta * beta))));
+            }
+        }
+        gb_acc += gbeta;
+        const uint32_t mw1 = masks[1 * 64 + lane] >> (16 * k), mw0 = masks[0 * 64 + lane] >> (16 * k);
+        float d2[32];
+        {
+            const f32x4 *gsrc = reinterpret_cast<const f32x4 *>(dgeo_scr + (tile_id * 64 + lane) * 16);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const f32x4 v = gsrc[q];
+#pragma unroll
+                for (int c = 0; c < 4; c++) d2[4 * q + c] = active ? v[c] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) d2[16 + r] = 0.f;
+        d2[16] = gs;  // tile 1, row 0 (only h == 0 lanes carry a non-zero gs)
+        // ---- layer s2: input S2 = rows 160..223 (no exchange: dP2 is known to both waves)
+        row_load_async(B[0], atile, 160 + 32 * k + i, h);
+        mfma_tiles_z_b3<32, 2, 1, 3>(wt, k, d2, acc, lane);       // (dP2 rows 24.. are zeros: k16 steps 0, 1, 2)
+        wt += FUSED_TS2(1);
+#pragma unroll
+        for (int r = 0; r < 16; r++) own[r] = mask_bit(mw1, r, acc[0][r]);             // mask S2 -> dP1, tile k
+        fused_wait<1>(B);
+        // the sdf row: d sdf of point 16 h + 4 j + q is `gs` of lane 16 h + 4 j + q (what scratch row 32 held in the one-wave form)
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float g = __shfl(gs, 16 * h + 4 * j + q);
+                wsdf = fmaf(g, B[0].v[j][q], wsdf);
+                bsdf += g;
+            }
+        // the two sums are needed after the tile loop only: pinned here, or the compiler sinks the 16 multiply-adds to the end of the
+        // trip and keeps the S2 row and the 16 exchanged values alive (in scratch memory) across all the phases in between
+        asm volatile("" : "+v"(wsdf), "+v"(bsdf));
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- layer s1: input S1 = rows 96..159
+        {
+            PAIR_LANE_ANEW;
+            RowSl Bs[1];
+            row_load_async(B[0], atile, 96 + 32 * k + i, h);
+            scr_put_tile(scrX, own, k, pt, h);
+            __syncthreads();                              // exchange 1 of 2: dP1 in X
+            mfma_tiles_scr_b3<2, 1>(wt, k, scrX, pt, h, acc, lane);
+            wt += FUSED_TS1(1);
+#pragma unroll
+            for (int r = 0; r < 16; r++) own[r] = mask_bit(mw0, r, acc[0][r]);         // mask S1 -> dP0, tile k
+            fused_wait<1>(B);
+            row_slices(B[0], Bs[0]);
+#pragma unroll
+            for (int mt = 0; mt < 2; mt++) {
+                scr_get(A, scrX, 32 * mt + i, h);
+                if (k == mt) dw_bias(A, b1);
+                dw_mfma_b3<1>(A, Bs, w1[mt]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- layer s0: input [enc | hash | topo] = rows 0..95 (k-step order); d(inputs) = W0^T dP0: tile 0 = enc kk 0..15,
+        // tile 1 = enc kk 16..19 + topo at r = 4, tile 2 = hash (16 h + r)
+        // wave 0: in tile 2 (rows 80..95 are unwritten padding: their lanes take row 79 -- k-step 39: zeros), wave 1: in tiles 0 and 1.
+        // The same two load statements in both waves (wave 0's second is a repeat it does not use): loads under a branch would make
+        // the compiler merge their destination registers behind it, with copies INTO registers whose data is still in flight
+        {
+            PAIR_LANE_ANEW;
+            row_load_async(B[0], atile, k == 0 ? 64 + min(i, 15) : i, h);
+            row_load_async(B[1], atile, k == 0 ? 64 + min(i, 15) : 32 + i, h);
+            scr_put_tile(scrY, own, k, pt, h);
+        }
+        __syncthreads();                                  // exchange 2 of 2: dP0 in Y
+        if (k == 0) {
+            PAIR_LANE_ANEW;
+            const int64_t p = tile_id * TILE + pt;
+            const bool live = active && p < M;
+            RowSl Bs[1];
+            f32x16(&e)[2] = wb;
+            mfma_tiles_scr_b3<3, 2>(wt, 0, scrY, pt, h, e, lane);
+            // the d/dx stage first (it frees the 32 registers of the input gradients), the weight gradient after it
+            float gx[3] = {0.f, 0.f, 0.f};
+            if (g_xc) {
+                float dsc[18];
+                enc_deriv_parked(atile, pt, h, dsc);       // S0 rows 0..35 hold the encoding of xc
+#pragma unroll
+                for (int kk = 0; kk < 18; kk++) {
+                    const float de = kk < 16 ? e[0][kk] : e[1][kk - 16];
+                    gx[kk % 3] += de * dsc[kk];
+                }
+                if (h == 0) {
+                    gx[0] += e[1][2];
+                    gx[2] += e[1][3];
+                } else {
+                    gx[1] += e[1][2];
+                }
+#pragma unroll
+                for (int d = 0; d < 3; d++) gx[d] += __shfl_xor(gx[d], 32);
+            }
+            if (live) {
+                if (g_xc && h == 0) {
+                    g_xc[p * 3 + 0] = gx[0];
+                    g_xc[p * 3 + 1] = gx[1];
+                    g_xc[p * 3 + 2] = gx[2];
+                }
+                if (g_topo) g_topo[p * 2 + h] = e[1][4];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            fused_wait<2>(B);
+            row_slices(B[0], Bs[0]);
+#pragma unroll
+            for (int mt = 0; mt < 2; mt++) {
+                scr_get(A, scrY, 32 * mt + i, h);
+                if (mt == 0) dw_bias(A, b0);
+                dw_mfma_b3<1>(A, Bs, wa[mt]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            PAIR_LANE_ANEW;
+            const int64_t p = tile_id * TILE + pt;
+            const bool live = active && p < M;
+            RowSl Bs[2];
+            f32x16 e[1];
+            mfma_tiles_scr_b3<3, 1>(wt, 2, scrY, pt, h, e, lane);
+            if (live && g_feat_s) {
+                f32x4 *o = reinterpret_cast<f32x4 *>(g_feat_s + p * 32 + 16 * h);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    f32x4 v;
+#pragma unroll
+                    for (int c = 0; c < 4; c++) v[c] = e[0][4 * q + c];
+                    o[q] = v;
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) max_s = max(max_s, __float_as_uint(fabsf(e[0][r])));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            fused_wait<2>(B);
+            row_slices(B[0], Bs[0]);
+            row_slices(B[1], Bs[1]);
+#pragma unroll
+            for (int mt = 0; mt < 2; mt++) {
+                scr_get(A, scrY, 32 * mt + i, h);
+                if (mt == 1) dw_bias(A, b0);
+                dw_mfma_b3_2(A, Bs, wa[mt][0], wb[mt]);
+                // (out tile 1's row reads and slicing stay behind out tile 0's products: hoisted, they are 40 more live registers)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const int lane = __lane_id(), h = lane >> 5, i = lane & 31;     // (not threadIdx.x: one register less across the tile loop)
+    if (gmax) {            // (only the waves k == 1 have seen d(hash))
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) max_s = max(max_s, (uint32_t)__shfl_xor((int)max_s, o));
+        if (lane == 0 && max_s) atomicMax(gmax + 0, max_s);
+    }
+    wsdf += __shfl_xor(wsdf, 32);
+    bsdf += __shfl_xor(bsdf, 32);
+    b1 += __shfl_xor(b1, 32);
+    b0 += __shfl_xor(b0, 32);
+    // the workgroup's partial = the sum of its four pairs', pairs 1, 2, 3 added to pair 0 in that order, half k to half k
+    float *red = reinterpret_cast<float *>(lds_fused) + k * PAIR_RED_FLOATS;
+    for (int src = 1; src < 4; src++) {
+        __syncthreads();
+        if (pair == src) {
+            float *q = acc_to_lds<1>(w1[0], red, lane);
+            q = acc_to_lds<1>(w1[1], q, lane);
+            q = acc_to_lds<1>(wa[0], q, lane);
+            q = acc_to_lds<1>(wa[1], q, lane);
+            if (k == 1) acc_to_lds<2>(wb, q, lane);
+            q += 2 * 1024;
+            q[0 * 64 + lane] = bsdf;
+            q[1 * 64 + lane] = b1;
+            q[2 * 64 + lane] = b0;
+            q[3 * 64 + lane] = wsdf;
+            q[4 * 64 + lane] = gb_acc;
+        }
+        __syncthreads();
+        if (pair == 0) {
+            const float *q = acc_add_lds<1>(w1[0], red, lane);
+            q = acc_add_lds<1>(w1[1], q, lane);
+            q = acc_add_lds<1>(wa[0], q, lane);
+            q = acc_add_lds<1>(wa[1], q, lane);
+            if (k == 1) acc_add_lds<2>(wb, q, lane);
+            q += 2 * 1024;
+            bsdf += q[0 * 64 + lane];
+            b1 += q[1 * 64 + lane];
+            b0 += q[2 * 64 + lane];
+            wsdf += q[3 * 64 + lane];
+            gb_acc += q[4 * 64 + lane];
+        }
+    }
+    if (pair != 0) return;
+    const int64_t pchunk = blockIdx.x;
+    if (k == 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) gb_acc += __shfl_xor(gb_acc, o);
+        if (lane == 0) ws[part.gb + blockIdx.x] = gb_acc;
+    }
+    // partial sums of this workgroup: layers s0, s1, s2 = part.dw[0..2]
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) {
+        dw_store_at<1>(ws + part.dw[1] + pchunk * 64 * 64, w1[mt], mt, 64, k, i, h);
+        dw_store_at<1>(ws + part.dw[0] + pchunk * 64 * 96, wa[mt], mt, 96, k == 0 ? 2 : 0, i, h);
+        if (k == 1) {
+            const f32x16(&w)[1] = reinterpret_cast<const f32x16(&)[1]>(wb[mt]);
+            dw_store_at<1>(ws + part.dw[0] + pchunk * 64 * 96, w, mt, 96, 1, i, h);
+        }
+    }
+    {   // s2, out tile 1: row 0 = the sdf row (accumulator row r = 0 of the lanes h == 0), the other 31 are zero; in tile k
+        f32x16 z[1];
+        acc_zero<1>(z);
+        if (h == 0) z[0][0] = wsdf;
+        dw_store_at<1>(ws + part.dw[2] + pchunk * 64 * 64, z, 1, 64, k, i, h);
+    }
+    if (h == 0) {
+        if (k == 0) ws[part.db[2] + pchunk * 64 + 32 + i] = i == 0 ? bsdf : 0.f;
+        ws[part.db[1] + pchunk * 64 + 32 * k + i] = b1;
+        ws[part.db[0] + pchunk * 64 + 32 * k + i] = b0;
     }
 }
 
@@ -2327,6 +2997,15 @@ extern "C" int64_t mh_field_bwd_fused_workspace_floats(int64_t M) {
 }
 extern "C" int64_t mh_field_dgeo_floats(int64_t M) { return n_tiles_for(M) * 64 * 16; }
 
+// With-colour b3 calls of at least this many points run the pair form (field_pair_*_kernel); smaller ones, the sdf-only pass and
+// the fp32 arithmetic keep the one-wave kernels.  A process-wide knob like mh_grid_stage_min_points: it only chooses between two
+// forms that give the same bits.
+static std::atomic<int64_t> g_pair_min_points{0};
+extern "C" int64_t mh_field_bwd_pair_min_points(int64_t set) {
+    if (set >= 0) g_pair_min_points.store(set, std::memory_order_relaxed);
+    return g_pair_min_points.load(std::memory_order_relaxed);
+}
+
 static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *albedo, const float *g_sdf,
                                 const float *g_sigma, const float *g_albedo, const float *wpackT, const float *beta,
                                 int32_t n_bands, int32_t with_color, const float *acts, float *dgeo_scratch,
@@ -2338,6 +3017,11 @@ static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *
     static MhOncePerDevice opted;
     const size_t lds_c = (size_t)(FUSED_TC2(b3) + FUSED_TC1(b3) + FUSED_TC0(b3)) * 16 + (size_t)(4 * SCR_FLOATS) * sizeof(float);
     const size_t lds_s = (size_t)(FUSED_TS2(b3) + FUSED_TS1(b3) + FUSED_TS0(b3)) * 16 + (size_t)(4 * SCR_FLOATS) * sizeof(float);
+    // pair form: the same packs + two scratch buffers per pair (136 KB colour, 160 KB sdf: the whole LDS of a CU)
+    const size_t pair_lds_c = (size_t)(FUSED_TC2(1) + FUSED_TC1(1) + FUSED_TC0(1)) * 16 + (size_t)(8 * SCR_FLOATS) * sizeof(float);
+    const size_t pair_lds_s = (size_t)(FUSED_TS2(1) + FUSED_TS1(1) + FUSED_TS0(1)) * 16 + (size_t)(8 * SCR_FLOATS) * sizeof(float);
+    static_assert((FUSED_TS2(1) + FUSED_TS1(1) + FUSED_TS0(1)) * 16 + 8 * SCR_FLOATS * 4 <= 160 * 1024, "pair form: LDS of one CU");
+    const bool pair = b3 && with_color && M >= g_pair_min_points.load(std::memory_order_relaxed);
     const int dev = mh_device();
     if (opted.need(dev)) {
         const int big_c = (int)((size_t)(FUSED_TC2(1) + FUSED_TC1(1) + FUSED_TC0(1)) * 16 + (size_t)(4 * SCR_FLOATS) * sizeof(float));
@@ -2347,7 +3031,9 @@ static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *
             hipFuncSetAttribute((const void *)field_fused_sdf_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big_s) != hipSuccess ||
             hipFuncSetAttribute((const void *)field_fused_sdf_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big_s) != hipSuccess ||
             hipFuncSetAttribute((const void *)field_fused_sdf_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big_s) != hipSuccess ||
-            hipFuncSetAttribute((const void *)field_fused_sdf_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big_s) != hipSuccess)
+            hipFuncSetAttribute((const void *)field_fused_sdf_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big_s) != hipSuccess ||
+            hipFuncSetAttribute((const void *)field_pair_color_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds_c) != hipSuccess ||
+            hipFuncSetAttribute((const void *)field_pair_sdf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds_s) != hipSuccess)
             return MH_ERR_LAUNCH;
         opted.mark(dev);
     }
@@ -2385,7 +3071,14 @@ static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *
     hipLaunchKernelGGL((field_fused_sdf_kernel<WC, B3_>), dim3((unsigned)blocks), dim3(FUSED_THREADS), lds_s, st, xc, sdf, g_sdf, \
                        g_sigma, wpackT, beta, (int)n_bands, acts, (const float *)(DGEO), g_xc, g_feat_s, g_topo,             \
                        workspace, ps, gmax_bits, M, n_tiles)
-    if (with_color) {
+    if (pair) {        // same grid, same workspace, same arguments: 8 waves per workgroup instead of 4
+        hipLaunchKernelGGL(field_pair_color_kernel, dim3((unsigned)blocks), dim3(PAIR_THREADS), pair_lds_c, st, albedo, g_albedo, wpackT,
+                           acts, dgeo_scratch, g_feat_c, workspace, pc, gmax_bits, M, n_tiles);
+        MH_CHECK_LAUNCH();
+        hipLaunchKernelGGL(field_pair_sdf_kernel, dim3((unsigned)blocks), dim3(PAIR_THREADS), pair_lds_s, st, xc, sdf, g_sdf, g_sigma,
+                           wpackT, beta, (int)n_bands, acts, (const float *)dgeo_scratch, g_xc, g_feat_s, g_topo, workspace, ps,
+                           gmax_bits, M, n_tiles);
+    } else if (with_color) {
         if (b3) FUSED_LAUNCH_COLOR(true); else FUSED_LAUNCH_COLOR(false);
         MH_CHECK_LAUNCH();
         if (b3) FUSED_LAUNCH_SDF(true, true, dgeo_scratch); else FUSED_LAUNCH_SDF(true, false, dgeo_scratch);

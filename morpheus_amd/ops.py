@@ -1091,14 +1091,19 @@ def _field_fwd(lib, xc, fs, fc, tp, beta_c, n_bands, with_color, opnd, need_grad
 # spilled 91 registers beside its 192 accumulators and measured equal to the fp32 form.
 # MORPHEUS_FIELD_BWD = "f32" keeps the native fp32 MFMA form (mh_field_bwd_fused; what the f32 mode always uses), "sdf" the
 # sliced form for the sdf-only pass alone (A/B).
+# The colour + sdf pass of "b3" runs the PAIR form of the two launches (two waves per SIMD, csrc/mlp.hip field_pair_*_kernel;
+# bit-identical outputs; same-box A/B in profiles/r07_field_bwd_pair.txt).  "b3w1" keeps the one-wave kernels for that pass too
+# (A/B, and what the pair form's tests compare with); the sdf-only pass runs the one-wave kernels either way.
 FIELD_BWD = os.environ.get("MORPHEUS_FIELD_BWD", "b3")
-if FIELD_BWD not in ("b3", "sdf", "f32"):
-    raise ValueError(f"MORPHEUS_FIELD_BWD={FIELD_BWD!r}: expected 'b3', 'sdf' or 'f32'")
+if FIELD_BWD not in ("b3", "b3w1", "sdf", "f32"):
+    raise ValueError(f"MORPHEUS_FIELD_BWD={FIELD_BWD!r}: expected 'b3', 'b3w1', 'sdf' or 'f32'")
+_PAIR_NEVER = 1 << 62         # mh_field_bwd_pair_min_points: no call is that large
+_pair_min_default = None      # the library's own threshold, read before the first call changes it
 
 
 def _field_wT(opnd, with_color: bool):
     """-> (transposed weight operand of the fused field backward, is it the bf16x3 pack?)"""
-    sliced = FIELD_BWD == "b3" or (FIELD_BWD == "sdf" and not with_color)
+    sliced = FIELD_BWD in ("b3", "b3w1") or (FIELD_BWD == "sdf" and not with_color)
     if sliced and opnd.mode == "b3" and opnd.wT3 is not None:
         return opnd.wT3[0], True
     return opnd.wT[0], False
@@ -1127,6 +1132,13 @@ def _field_bwd(lib, xc, wT, beta_c, acts, sdf, albedo, g_sdf, g_sigma, g_albedo,
     if raw_into is None:      # an empty query returns MH_OK without writing: the gradient must then be zeros, not heap contents
         raw = torch.empty(jp.raw_len + 1, device=dev) if M > 0 else torch.zeros(jp.raw_len + 1, device=dev)
     c = lambda t: None if t is None else t.contiguous()
+    if b3 and with_color:     # the form of the two launches follows FIELD_BWD at call time (a host-side choice, made at the launch)
+        global _pair_min_default
+        if _pair_min_default is None:
+            _pair_min_default = lib.mh_field_bwd_pair_min_points(-1)
+        want = _PAIR_NEVER if FIELD_BWD == "b3w1" else _pair_min_default
+        if lib.mh_field_bwd_pair_min_points(-1) != want:
+            lib.mh_field_bwd_pair_min_points(want)
     _timed("mh_field_bwd_fused_b3" if b3 else "mh_field_bwd_fused", ptr(xc), ptr(sdf), ptr(albedo if with_color else None), ptr(c(g_sdf)),
            ptr(c(g_sigma)), ptr(c(g_albedo)), ptr(wT), ptr(beta_c), n_bands, int(with_color), ptr(acts), ptr(dgeo), ptr(ws),
            ptr(raw) if raw_into is None else ctypes.c_void_p(raw_into), int(raw_into is not None), ptr(g_xc), ptr(g_fs), ptr(g_fc),
