@@ -108,6 +108,39 @@ int mh_grid_encode_fwd_binned(const float *x, const float *emb, const int32_t *o
  * way.  set < 0: query only.  Returns the value in force (default 2^20). */
 int64_t mh_grid_stage_min_points(int64_t set);
 
+/* ---- the grid encoder in full (csrc/hashgrid_general.hip) ------------------------------------
+ * Every switch of the reference operator (gridencoder.cu:61-378): C = 1, 2, 4 or 8 channels per level, gridtype 0 hash /
+ * 1 tiled, align_corners 0 / 1, interp 0 linear / 1 smoothstep; D = 3.  x [M,3] world units, emb [rows,C], offsets_host [L+1]
+ * and res_host [L] HOST arrays as above, out / grad [M, L*C] level-major and channel-minor, levels >= n_levels zero.  A point
+ * with any (x + bound) / (2 bound) outside [0,1] gets zero features, zero d/dx and adds nothing to the table gradient.
+ * The plain path: one lane per point, one level per wave, no brick staging; the default configuration (C = 2, hash, linear,
+ * not aligned) is served by mh_grid_encode_* above and gives the same cells here.
+ * mh_grid_general_bwd: grad_emb [rows,C] is ADDED to (zero it, or hand over a running sum) through emb_acc, DEVICE int64
+ * [rows*C + 1] scratch the call zeroes: terms are summed in 64-bit fixed point (one rounding each onto 2^-40 of the power of two
+ * above max |grad|, found by the call), so the table gradient is identical from run to run.  grad_x [M,3] optional, fully
+ * written; any L <= MH_MAX_LEVELS.
+ * mh_grid_grad_tv (kernel_grad_tv, gridencoder.cu:526-631): per point inside the box and per level (ALL L levels) the cell's row
+ * receives (weight / 6) r / sqrt(q + 1e-9) per channel, r / q the sums of the differences / squared differences to the right
+ * neighbour on every axis and to the left one where the cell index is > 0.  normalized != 0: x holds u in [0,1] already (bound
+ * unused).  Added to grad_emb IN PLACE through emb_acc (DEVICE int64 [rows*C], zeroed by the call; fixed point on the power of
+ * two above |weight|: identical from run to run); entries no point reaches are not written.
+ * mh_grid_grad_wd (kernel_grad_wd, :671-703): grad_emb[i] += 2 weight emb[i] / rows(level of i) over the whole table, in place.
+ * grad_emb needs 4-byte alignment only (it may be a view into a flat gradient bucket); rows are read as C-wide vectors where emb
+ * is aligned for it and element by element otherwise.
+ * Bad arguments return MH_ERR_ARG before any launch; M == 0 returns MH_OK without one. */
+int mh_grid_general_fwd(const float *x, const float *emb, const int32_t *offsets_host, const int32_t *res_host, float *out,
+                        int64_t M, int32_t L, int32_t n_levels, int32_t C, int32_t gridtype, int32_t align_corners,
+                        int32_t interp, float bound, void *stream);
+int mh_grid_general_bwd(const float *grad, const float *x, const float *emb, const int32_t *offsets_host,
+                        const int32_t *res_host, float *grad_emb, int64_t *emb_acc, float *grad_x, int64_t M, int32_t L,
+                        int32_t n_levels, int32_t C, int32_t gridtype, int32_t align_corners, int32_t interp, float bound,
+                        void *stream);
+int mh_grid_grad_tv(const float *x, const float *emb, const int32_t *offsets_host, const int32_t *res_host, float *grad_emb,
+                    int64_t *emb_acc, float weight, int64_t M, int32_t L, int32_t C, int32_t gridtype, int32_t align_corners,
+                    int32_t normalized, float bound, void *stream);
+int mh_grid_grad_wd(const float *emb, const int32_t *offsets_host, float *grad_emb, float weight, int32_t L, int32_t C,
+                    void *stream);
+
 /* ---- packed transmittance compositor -------------------------------------------------------
  * Samples of ray r are the contiguous range [ray_start[r], ray_start[r]+ray_cnt[r]) of the packed
  * arrays, ordered by t.  w_i = exp(-sum_{j<i} sigma_j dt_j) * (1 - exp(-sigma_i dt_i)).

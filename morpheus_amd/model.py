@@ -152,14 +152,31 @@ class MLP(nn.Module):
 
 
 class GridEncoder(nn.Module):
-    """Multires hash grid with the reference's table sizing (grid.py:104-147) on the HIP kernels."""
+    """Multires grid encoder with the reference's table sizing (grid.py:104-147) on the HIP kernels: D = 3, `level_dim` in
+    {1, 2, 4, 8}, `gridtype` 'hash' / 'tiled', `align_corners`, `interpolation` 'linear' / 'smoothstep'.
+
+    The defaults of `log2_hashmap_size` (15) and `desired_resolution` (128) are this project's model geometry, NOT the reference
+    constructor's (19 and None): scene_representation builds `GridEncoder()` bare.  `desired_resolution=None` takes the growth factor
+    from `per_level_scale` (2 when that is None too), as grid.py:108-109.
+
+    The default switches (level_dim 2, hash, linear, not aligned) run the specialised kernels of csrc/hashgrid.hip; every other
+    configuration -- and the default one with an input gradient at a level count other than 16 -- runs csrc/hashgrid_general.hip."""
 
     def __init__(self, input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=15,
-                 desired_resolution=128):
+                 desired_resolution=128, per_level_scale=None, gridtype='hash', align_corners=False, interpolation='linear'):
         super().__init__()
-        assert input_dim == 3 and level_dim == 2, "HIP encoder is specialised to D=3, C=2"
+        assert input_dim == 3, "HIP encoder is specialised to D=3"
+        if level_dim not in ops.GRID_CHANNELS:
+            raise ValueError(f"level_dim {level_dim}: expected one of {ops.GRID_CHANNELS}")
         self.num_levels, self.level_dim, self.base_resolution = num_levels, level_dim, base_resolution
-        self.per_level_scale = float(np.exp2(np.log2(desired_resolution / base_resolution) / (num_levels - 1)))
+        if desired_resolution is not None:
+            self.per_level_scale = float(np.exp2(np.log2(desired_resolution / base_resolution) / (num_levels - 1)))
+        else:
+            self.per_level_scale = float(2 if per_level_scale is None else per_level_scale)
+        self.input_dim, self.log2_hashmap_size = input_dim, log2_hashmap_size
+        self.gridtype, self.gridtype_id = gridtype, ops._grid_switch(ops.GRID_TYPES, gridtype, "gridtype")
+        self.interpolation, self.interp_id = interpolation, ops._grid_switch(ops.GRID_INTERPS, interpolation, "interpolation")
+        self.align_corners = bool(align_corners)
         self.output_dim = num_levels * level_dim
         offs, total = [], 0
         for i in range(num_levels):
@@ -173,9 +190,34 @@ class GridEncoder(nn.Module):
         self._res_np = ops.level_resolutions(num_levels, self.per_level_scale, base_resolution)
         self.n_params = total * level_dim
         self.embeddings = nn.Parameter(torch.empty(total, level_dim).uniform_(-1e-4, 1e-4))
+        self._default_switches = (level_dim == 2 and self.gridtype_id == 0 and self.interp_id == 0 and not self.align_corners)
 
     def forward(self, inputs, bound=1, max_level=None, group=1):
-        return ops.grid_encode(inputs, self.embeddings, self._offsets_np, self._res_np, float(bound), max_level, group)
+        # the specialised path's d/dx reduction is built for 16 levels; without an input gradient it takes any level count
+        needs_dx = torch.is_grad_enabled() and inputs.requires_grad
+        if self._default_switches and (self.num_levels == 16 or not needs_dx):
+            return ops.grid_encode(inputs, self.embeddings, self._offsets_np, self._res_np, float(bound), max_level, group)
+        return ops.grid_encode_general(inputs, self.embeddings, self._offsets_np, self._res_np, float(bound), max_level, self.level_dim,
+                                       self.gridtype_id, self.align_corners, self.interp_id)
+
+    def _grad_buffer(self):
+        if self.embeddings.grad is None:
+            raise ValueError('grad is None, should be called after loss.backward() and before optimizer.step()!')
+        return self.embeddings.grad
+
+    def grad_total_variation(self, weight=1e-7, inputs=None, bound=1, B=1000000):
+        """grid.py:173-193: add the total-variation gradient of the table, sampled at `inputs` ([..,3] in [-bound, bound]; None:
+        B uniform points of the box), to `embeddings.grad` in place.  Call after backward() and before the optimiser step."""
+        grad = self._grad_buffer()
+        normalized = inputs is None
+        if normalized:
+            inputs = torch.rand(B, self.input_dim, device=self.embeddings.device)
+        ops.grid_grad_tv(inputs, self.embeddings, grad, self._offsets_np, self._res_np, weight, float(bound), self.level_dim,
+                         self.gridtype_id, self.align_corners, normalized)
+
+    def grad_weight_decay(self, weight=0.1):
+        """grid.py:196-206: level-wise mean weight decay (each level's rows weigh 1 / rows), added to `embeddings.grad` in place."""
+        ops.grid_grad_wd(self.embeddings, self._grad_buffer(), self._offsets_np, weight, self.level_dim)
 
 
 # LaplaceDensity object -> the scene_representation whose step cache its get_beta() may use (registered by the model's training

@@ -314,6 +314,114 @@ def grid_encode_multi(x, embs, offsets_np, res_np, bound, max_level=None):
     return _GridEncode.apply(x.reshape(-1, 3), offsets_np, res_np, effective_levels(max_level, L), bound, 1, *embs)
 
 
+# ---- the grid encoder in full (csrc/hashgrid_general.hip): every channel count, grid type, alignment and interpolation ----------
+GRID_TYPES = {"hash": 0, "tiled": 1}          # grid.py:13-16
+GRID_INTERPS = {"linear": 0, "smoothstep": 1}  # grid.py:18-21
+GRID_CHANNELS = (1, 2, 4, 8)
+
+
+def _grid_switch(table: dict, value, what: str) -> int:
+    if value in table:
+        return table[value]
+    if isinstance(value, (int, np.integer)) and not isinstance(value, bool) and int(value) in table.values():
+        return int(value)
+    raise ValueError(f"{what} {value!r}: expected one of {tuple(table)}")
+
+
+def _grid_table(emb, offsets_np, C: int):
+    """the checks every general-grid call makes on its table: [rows, C] fp32 on the GPU with the rows the offsets describe"""
+    require_gpu(emb)
+    if C not in GRID_CHANNELS:
+        raise ValueError(f"level_dim {C}: the HIP grid encoder has C in {GRID_CHANNELS}")
+    if emb.dtype != torch.float32 or emb.dim() != 2 or emb.shape[1] != C or emb.shape[0] != int(offsets_np[-1]):
+        raise ValueError(f"embeddings {tuple(emb.shape)} {emb.dtype}: expected fp32 [{int(offsets_np[-1])}, {C}]")
+
+
+class _GridEncodeGeneral(torch.autograd.Function):
+    """grid.py:25-96 on mh_grid_general_fwd / _bwd.  Saves x and emb; cells and weights are recomputed in the backward (no dy_dx
+    tensor), the position gradient is computed only when x asks for one."""
+
+    @staticmethod
+    def forward(ctx, x, emb, offsets_np, res_np, n_levels, bound, C, gridtype, align, interp):
+        require_gpu(x)
+        _lib.load()
+        x = x.detach().contiguous().float()
+        emb = emb.detach().contiguous()
+        L = len(res_np)
+        o_np, o_p = _i32arr(offsets_np)
+        r_np, r_p = _i32arr(res_np)
+        M = x.shape[0]
+        out = torch.empty(M, L * C, dtype=torch.float32, device=x.device)
+        _timed("mh_grid_general_fwd", ptr(x), ptr(emb), o_p, r_p, ptr(out), M, L, n_levels, C, gridtype, align, interp, float(bound))
+        ctx.save_for_backward(x, emb)
+        ctx.meta = (o_np, r_np, n_levels, float(bound), L, C, gridtype, align, interp)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, emb = ctx.saved_tensors
+        o_np, r_np, n_levels, bound, L, C, gridtype, align, interp = ctx.meta
+        o_p, r_p = o_np.ctypes.data_as(ctypes.c_void_p), r_np.ctypes.data_as(ctypes.c_void_p)
+        grad = grad.contiguous().float()
+        M = x.shape[0]
+        g_emb = torch.zeros_like(emb)
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        emb_acc = torch.empty(emb.numel() + 1, dtype=torch.int64, device=emb.device)       # fixed-point table sum + max |grad|
+        _timed("mh_grid_general_bwd", ptr(grad), ptr(x), ptr(emb), o_p, r_p, ptr(g_emb), ptr(emb_acc), ptr(g_x), M, L, n_levels, C,
+               gridtype, align, interp, bound)
+        return (g_x, g_emb if ctx.needs_input_grad[1] else None, None, None, None, None, None, None, None, None)
+
+
+def grid_encode_general(x, emb, offsets_np, res_np, bound, max_level=None, C: int = 2, gridtype="hash", align_corners=False,
+                        interp="linear"):
+    """x [..,3] in world units -> [.., L*C] for any configuration of the reference operator (D = 3): C in {1, 2, 4, 8},
+    gridtype 'hash' / 'tiled', align_corners, interp 'linear' / 'smoothstep' (names or the reference's ids, grid.py:13-21).
+    Level-major, channel-minor; levels >= the effective count (grid.py:42) are zero."""
+    L = len(res_np)
+    C = int(C)
+    _grid_table(emb, offsets_np, C)
+    lead = list(x.shape[:-1])
+    out = _GridEncodeGeneral.apply(x.reshape(-1, 3), emb, offsets_np, res_np, effective_levels(max_level, L), float(bound), C,
+                                   _grid_switch(GRID_TYPES, gridtype, "gridtype"), int(bool(align_corners)),
+                                   _grid_switch(GRID_INTERPS, interp, "interpolation"))
+    return out.view(lead + [L * C])
+
+
+def _grid_grad_target(emb, grad, offsets_np, C):
+    _grid_table(emb, offsets_np, C)
+    require_gpu(grad)
+    if grad.dtype != torch.float32 or grad.shape != emb.shape or not grad.is_contiguous():
+        raise ValueError(f"gradient buffer {tuple(grad.shape)} {grad.dtype}: expected contiguous fp32 {tuple(emb.shape)}")
+
+
+@torch.no_grad()
+def grid_grad_tv(x, emb, grad, offsets_np, res_np, weight: float, bound: float = 1.0, C: int = 2, gridtype="hash",
+                 align_corners=False, normalized: bool = False):
+    """Total-variation gradient of the table (kernel_grad_tv, gridencoder.cu:526-631) at the points x [..,3], ADDED to `grad`
+    ([rows, C], contiguous; may be a view into a flat gradient bucket) in place.  normalized: x holds u in [0,1] already."""
+    C = int(C)
+    _grid_grad_target(emb, grad, offsets_np, C)
+    require_gpu(x)
+    x = x.detach().reshape(-1, 3).contiguous().float()
+    emb = emb.detach().contiguous()
+    _, o_p = _i32arr(offsets_np)
+    _, r_p = _i32arr(res_np)
+    acc = torch.empty(emb.numel(), dtype=torch.int64, device=emb.device)
+    _timed("mh_grid_grad_tv", ptr(x), ptr(emb), o_p, r_p, ptr(grad), ptr(acc), float(weight), x.shape[0], len(res_np), C,
+           _grid_switch(GRID_TYPES, gridtype, "gridtype"), int(bool(align_corners)), int(bool(normalized)), float(bound))
+    return grad
+
+
+@torch.no_grad()
+def grid_grad_wd(emb, grad, offsets_np, weight: float, C: int = 2):
+    """Level-wise mean weight decay (kernel_grad_wd, gridencoder.cu:671-703): grad[i] += 2 weight emb[i] / rows(level of i), in place."""
+    C = int(C)
+    _grid_grad_target(emb, grad, offsets_np, C)
+    _, o_p = _i32arr(offsets_np)
+    _timed("mh_grid_grad_wd", ptr(emb.detach().contiguous()), o_p, ptr(grad), float(weight), len(offsets_np) - 1, C)
+    return grad
+
+
 # ------------------------------------------------------------------------------------ compositor
 class _Composite(torch.autograd.Function):
     @staticmethod

@@ -1,5 +1,6 @@
 """GPU-box micro-benchmark of the hash-grid kernels (forward: gathered / brick-binned; backward: naive / brick-binned with
-the d/dx rows gathered or staged in LDS)."""
+the d/dx rows gathered or staged in LDS).  `--general`: the calls of csrc/hashgrid_general.hip instead -- forward and backward at
+2^20 uniform points per channel count and switch set, total variation at 10^6 points and weight decay on the default table."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -57,7 +58,35 @@ def run(x, tag):
         print(f"   fwd, levels 0..{nl - 1:2d} active: {t:.3f} ms")
 
 
-o, d, t, rid = [v.to(dev) for v in synth.frame_rays(0, 128, 128)]
-ri, ts, te, xyz, rs, rc = ops.sample_uniform(o[0], d[0], synth.ray_jitter(16384).to(dev), 128, 1.01, with_xyz=True)
-run(xyz, "rays 16384x128")
-run((torch.rand(2097152, 3, device=dev) * 2 - 1), "uniform random")
+def run_general():
+    st = torch.cuda.current_stream().cuda_stream
+    M = 1 << 20
+    x = torch.rand(M, 3, device=dev) * 2 - 1
+    for C, gridtype, align, interp in ((2, 0, 0, 0), (2, 0, 0, 1), (2, 1, 1, 1), (1, 0, 0, 0), (4, 0, 0, 0), (8, 0, 0, 0)):
+        e = synth.hash_tensor((int(offs[-1]), C), 9001, 0.1).to(dev)
+        out = torch.empty(M, 16 * C, device=dev); grad = torch.randn(M, 16 * C, device=dev)
+        g_emb = torch.zeros_like(e); g_x = torch.empty(M, 3, device=dev); acc = torch.empty(e.numel() + 1, dtype=torch.int64, device=dev)
+        tag = f"C={C} {'tiled' if gridtype else 'hash'} align={align} {'smoothstep' if interp else 'linear'}"
+        t = timeit(lambda: lib.mh_grid_general_fwd(x.data_ptr(), e.data_ptr(), P(o_p), P(r_p), out.data_ptr(), M, 16, 16, C, gridtype, align, interp, 1.01, st))
+        print(f"[general M={M} {tag}] fwd {t:.3f} ms")
+        for dx in (False, True):
+            t = timeit(lambda: lib.mh_grid_general_bwd(grad.data_ptr(), x.data_ptr(), e.data_ptr(), P(o_p), P(r_p), g_emb.data_ptr(), acc.data_ptr(), g_x.data_ptr() if dx else None, M, 16, 16, C, gridtype, align, interp, 1.01, st))
+            print(f"   bwd dx={int(dx)}: {t:.3f} ms")
+    B = 1000000
+    u = torch.rand(B, 3, device=dev)
+    for C in (2, 8):
+        e = synth.hash_tensor((int(offs[-1]), C), 9001, 0.1).to(dev)
+        g = torch.zeros_like(e); acc = torch.empty(e.numel(), dtype=torch.int64, device=dev)
+        t = timeit(lambda: lib.mh_grid_grad_tv(u.data_ptr(), e.data_ptr(), P(o_p), P(r_p), g.data_ptr(), acc.data_ptr(), 1e-7, B, 16, C, 0, 0, 1, 1.0, st))
+        print(f"[general C={C}] total variation B={B}, default table: {t:.3f} ms")
+        t = timeit(lambda: lib.mh_grid_grad_wd(e.data_ptr(), P(o_p), g.data_ptr(), 0.1, 16, C, st), 20)
+        print(f"[general C={C}] weight decay, default table ({e.numel()} entries): {t:.3f} ms")
+
+
+if "--general" in sys.argv:
+    run_general()
+else:
+    o, d, t, rid = [v.to(dev) for v in synth.frame_rays(0, 128, 128)]
+    ri, ts, te, xyz, rs, rc = ops.sample_uniform(o[0], d[0], synth.ray_jitter(16384).to(dev), 128, 1.01, with_xyz=True)
+    run(xyz, "rays 16384x128")
+    run((torch.rand(2097152, 3, device=dev) * 2 - 1), "uniform random")
