@@ -327,6 +327,13 @@ int32_t mh_warp_regen_dpre4(int64_t M);
 int64_t mh_warp_wgrad_workspace_floats(int64_t M);
 int mh_warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
                      const void *w3T_t, int32_t regen_dpre4, float *workspace, float *dw_raw, float *db_raw, int64_t M, void *stream);
+/* Line words: mh_warp_fwd_b3 parks, in the dead rows of the tile's H0 block (from row 40 on: [net][hidden layer 1..5][half h]
+ * uint64, 160 bytes), which of the tile's parked rows carry a non-zero: bit 16 t + r of half h <-> row 32 t + (r & 3) + 8 (r >> 2)
+ * + 4 h of that layer's H block.  The per-layer kernels of mh_warp_wgrad_b3 (large batches) fetch a zero line in place of a row
+ * whose bit is 0 -- of an H block and of the dPre block masked by the same ReLU signs; every result keeps its bits.
+ * mh_warp_skip_zero_lines: process-wide switch of that skipping (1 = on, the default; 0 = every row is fetched; set < 0: query
+ * only).  Returns the value in force.  The words are parked either way. */
+int64_t mh_warp_skip_zero_lines(int64_t set);
 int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
                    const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
                    float *out_topo, float *acts, int64_t M, void *stream);

@@ -1947,6 +1947,20 @@ struct WgFrag {
 // instructions, so the counted waits stand): its values only reach dW rows / columns of pad features, which nobody gathers.
 __device__ __forceinline__ int wg_row(int row, int live) { return row < live ? row : live - 1; }
 
+// Line words (round 8; mlp_b3.hip: b3_park_line_word): the b3 warp forward parks, per tile, net, hidden layer and lane half, a
+// 64-bit word whose bit 16 t + r says that row 32 t + acc_row(r, h) of that layer's H block -- and of the dPre block masked by the
+// same ReLU signs -- has a non-zero among its 32 points.  A lane whose row's bit is 0 points its four loads at wg_zero_line
+// instead: the same number of load instructions (the counted waits stand, nothing is branched around), the registers receive
+// +0 where the row holds +0 / -0, and the row's 128-byte line is not fetched from memory at all -- the zero line stays in the
+// cache.  A zero operand row adds exact zeros to sums that start at +0, so every result keeps its bits.
+__device__ float wg_zero_line[16];
+// row 32 * tile + i of a block -> (half, register) of the chain lane that made it: which word, which bit
+__device__ __forceinline__ int wg_line_half(int i) { return (i >> 2) & 1; }
+__device__ __forceinline__ int wg_line_bit(int tile, int i) { return 16 * (tile & 1) + (i & 3) + 4 * (i >> 3); }
+__device__ __forceinline__ const float *wg_line_ptr(uint32_t word, int bit, const float *row) {
+    return ((word >> bit) & 1u) ? row : wg_zero_line;
+}
+
 template <int IT>
 __device__ __forceinline__ void wg_load(WgFrag<IT> &f, const float *__restrict__ acts, const float *__restrict__ dpre,
                                         int64_t t, int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off,
@@ -1976,6 +1990,33 @@ __device__ __forceinline__ void wg_load_async(WgFrag<IT> &f, const float *__rest
 #pragma unroll
     for (int n = 0; n < IT; n++) {
         const float *b = acts + t * acts_tile_floats + act_off + (int64_t)wg_row(32 * n + i, in_live) * TILE + 16 * h;
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(f.b[n][0]) : "v"(b) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(f.b[n][1]) : "v"(b) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(f.b[n][2]) : "v"(b) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off offset:48" : "=v"(f.b[n][3]) : "v"(b) : "memory");
+    }
+}
+
+// The same with the B rows chosen by the tile's line words (`lw`: the lane's half of H's 64-bit word).  The word is fetched by an
+// ordinary load, NOT an asm one: the compiler takes an asm load's output as valid at once, and with this kernel's register
+// pressure it copied the in-flight pair to its spill registers (seen in the ISA).  An ordinary load in between only makes the
+// counted waits cover more (vmcnt counts in issue order); hipcc's own wait before the word's use is a vmcnt(0) that stands where
+// the older register set is waited for a few instructions later anyway.
+template <int IT>
+__device__ __forceinline__ void wg_load_async_lw(WgFrag<IT> &f, uint2 lw, const float *__restrict__ acts,
+                                                 const float *__restrict__ dpre, int64_t t, int64_t acts_tile_floats,
+                                                 int64_t dpre_tile_floats, int act_off, int dpre_off, int mt, int i, int h, int in_live,
+                                                 int out_live) {
+    const uint32_t w[2] = {lw.x, lw.y};
+    const float *a = dpre + t * dpre_tile_floats + dpre_off + (int64_t)wg_row(32 * mt + i, out_live) * TILE + 16 * h;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(f.a[0]) : "v"(a) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(f.a[1]) : "v"(a) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(f.a[2]) : "v"(a) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:48" : "=v"(f.a[3]) : "v"(a) : "memory");
+#pragma unroll
+    for (int n = 0; n < IT; n++) {
+        const float *b = wg_line_ptr(w[n >> 1], wg_line_bit(n, i),
+                                     acts + t * acts_tile_floats + act_off + (int64_t)wg_row(32 * n + i, in_live) * TILE + 16 * h);
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(f.b[n][0]) : "v"(b) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(f.b[n][1]) : "v"(b) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(f.b[n][2]) : "v"(b) : "memory");
@@ -2123,11 +2164,12 @@ __device__ __forceinline__ void wg_mma_b3(const WgFrag<IT> &f, f32x16 (&acc)[IT]
     }
 }
 
-template <int IT>
+// LW: the B rows (an H block of the b3 warp forward) are chosen by the tile's line words at `lw_off` floats into the acts tile
+template <int IT, bool LW = false>
 __device__ __forceinline__ void wgrad_body_b3(const float *__restrict__ acts, const float *__restrict__ dpre,
                                               int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off, int dpre_off,
                                               int out_pad, float *__restrict__ dw_part, float *__restrict__ db_part,
-                                              int64_t n_tiles, int n_chunks, int chunk, int in_live, int out_live) {
+                                              int64_t n_tiles, int n_chunks, int chunk, int in_live, int out_live, int lw_off = 0) {
     const int lane = threadIdx.x & 63, mt = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
     const int64_t st = n_chunks;
@@ -2139,26 +2181,45 @@ __device__ __forceinline__ void wgrad_body_b3(const float *__restrict__ acts, co
     constexpr int NL = 4 + 4 * IT;
     const int64_t n_my = chunk < n_tiles ? (n_tiles - chunk + st - 1) / st : 0;
     const int64_t last = chunk + (n_my > 0 ? n_my - 1 : 0) * st;
+    // the lane's half of a tile's word; lw0 / lw1: the word of the tile f0 / f1 is loaded for next, fetched one MFMA block ahead
+    const uint2 *lwp = reinterpret_cast<const uint2 *>(acts + lw_off) + wg_line_half(i);
+    uint2 lw0 = make_uint2(0u, 0u), lw1 = make_uint2(0u, 0u);
 #define WG_TILE(k) ((chunk + (k) * st) <= last ? (chunk + (k) * st) : last)
-#define WG_LOAD(f, k) wg_load_async<IT>(f, acts, dpre, WG_TILE(k), acts_tile_floats, dpre_tile_floats, act_off, dpre_off, mt, i, h, in_live, out_live)
+#define WG_LW(k) lwp[WG_TILE(k) * (acts_tile_floats / 2)]
+#define WG_LOAD(f, w, k)                                                                                                         \
+    do {                                                                                                                         \
+        if (LW)                                                                                                                  \
+            wg_load_async_lw<IT>(f, w, acts, dpre, WG_TILE(k), acts_tile_floats, dpre_tile_floats, act_off, dpre_off, mt, i, h,  \
+                                 in_live, out_live);                                                                             \
+        else                                                                                                                     \
+            wg_load_async<IT>(f, acts, dpre, WG_TILE(k), acts_tile_floats, dpre_tile_floats, act_off, dpre_off, mt, i, h, in_live, \
+                              out_live);                                                                                         \
+    } while (0)
     if (n_my > 0) {
         WgFrag<IT> f0, f1;
-        WG_LOAD(f0, 0);
+        if (LW) {
+            lw0 = WG_LW(0);
+            lw1 = WG_LW(1);
+        }
+        WG_LOAD(f0, lw0, 0);
         for (int64_t k = 0; k < n_my; k += 2) {
-            WG_LOAD(f1, k + 1);
+            WG_LOAD(f1, lw1, k + 1);
             wg_wait<NL>();  // f0 landed
             landed(f0);
+            if (LW) lw0 = WG_LW(k + 2);
             wg_mma_b3<IT>(f0, acc, bsum);
             __builtin_amdgcn_sched_barrier(0);
-            WG_LOAD(f0, k + 2);
+            WG_LOAD(f0, lw0, k + 2);
             wg_wait<NL>();  // f1 landed
             landed(f1);
+            if (LW) lw1 = WG_LW(k + 3);
             if (k + 1 < n_my) wg_mma_b3<IT>(f1, acc, bsum);
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 #undef WG_LOAD
+#undef WG_LW
 #undef WG_TILE
     const int in_pad = 32 * IT;
     float *dw = dw_part + (int64_t)chunk * out_pad * in_pad;
@@ -2213,7 +2274,7 @@ template <int IT>
 __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ acts, const float *__restrict__ dpre,
                                                    int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off, int dpre_off,
                                                    float *__restrict__ dw_part, float *__restrict__ db_part, int64_t n_tiles,
-                                                   int n_chunks, int chunk, int in_live) {
+                                                   int n_chunks, int chunk, int in_live, int lwa_off = -1, int lwb_off = -1) {
     // B slices: [buffer 2][in tile IT][plane 3][step 2][lane 64] float4
     constexpr int BUF_F4 = IT * 6 * 64;
     const int lane = threadIdx.x & 63, mt = threadIdx.x >> 6;
@@ -2230,11 +2291,32 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
     constexpr int NS = WG_REG_SETS;           // register sets of raw rows: NS - 1 tiles (8 KB per wave each) in flight
     WgRaw raw[NS];
     WgSl as[2];
+    // Line words (wg_line_ptr): lwa_off / lwb_off = floats from the acts tile's start to the word of the dPre block / of the
+    // activation block, -1 = the operand has none (every row is fetched: `force`).  The lane's dword of each word is fetched ONE step
+    // ahead of the rows it chooses, at the head of the step and before that step's row loads: vmcnt counts in issue order, so when it
+    // is taken (behind the 8 row loads of its own step) everything older has landed -- the rows of the tile whose slicing opens this
+    // step anyway.  Two registers; a ring as deep as the raw sets cost six and spilled (profiles/r08_zero_lines.txt).
+    const int mtu = __builtin_amdgcn_readfirstlane(mt), btu = mtu & (IT - 1);
+    const uint32_t force_a = lwa_off < 0 ? ~0u : 0u, force_b = lwb_off < 0 ? ~0u : 0u;
+    const uint32_t *lwa0 = reinterpret_cast<const uint32_t *>(acts) + ((lwa_off < 0 ? 0 : lwa_off) + (mtu >> 1));
+    const uint32_t *lwb0 = reinterpret_cast<const uint32_t *>(acts) + ((lwb_off < 0 ? 0 : lwb_off) + (btu >> 1));
+    const int lwo = 2 * wg_line_half(i);
+    const int bit_a = wg_line_bit(mtu, i), bit_b = wg_line_bit(btu, i);
+    uint2 lwn;            // the words of the tile the NEXT WG_LD loads
 #define WG_T(k) ((chunk + (k) * st) <= last ? (chunk + (k) * st) : last)
+#define WG_LW(k)                                                                     \
+    do {                                                                             \
+        const int64_t tw_ = WG_T(k);                                                 \
+        lwn.x = (lwa0 + tw_ * acts_tile_floats)[lwo];                                \
+        lwn.y = (lwb0 + tw_ * acts_tile_floats)[lwo];                                \
+    } while (0)
 #define WG_LD(set, k)                                                                \
     do {                                                                             \
         const int64_t t_ = WG_T(k);                                                  \
-        wg_raw_load(raw[set], a0 + t_ * dpre_tile_floats, b0 + t_ * acts_tile_floats); \
+        const float *pa_ = wg_line_ptr(lwn.x | force_a, bit_a, a0 + t_ * dpre_tile_floats); \
+        const float *pb_ = wg_line_ptr(lwn.y | force_b, bit_b, b0 + t_ * acts_tile_floats); \
+        WG_LW((k) + 1);                                                              \
+        wg_raw_load(raw[set], pa_, pb_);                                             \
     } while (0)
     // slice raw set `set` (tile k): dPre slices -> as[k & 1], activation slices -> LDS buffer k & 1
 #define WG_SPLIT(set, par, REAL)                                                                                          \
@@ -2304,6 +2386,8 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
     } while (0)
     if (n_my > 0) {
 #pragma unroll
+        WG_LW(0);
+#pragma unroll
         for (int q = 0; q < NS; q++) WG_LD(q, q);
         __builtin_amdgcn_sched_barrier(0);
         WG_SPLIT(0, 0, true);
@@ -2335,6 +2419,7 @@ __device__ __forceinline__ void wgrad_regs_b3_body(const float *__restrict__ act
 #undef WG_MMA
 #undef WG_SPLIT
 #undef WG_LD
+#undef WG_LW
 #undef WG_T
     const int in_pad = 32 * IT;
     float *dw = dw_part + (int64_t)chunk * 128 * in_pad;
@@ -2350,9 +2435,10 @@ template <int IT>
 __global__ __launch_bounds__(256, WG_REG_WAVES) void wgrad_regs_b3_kernel(const float *__restrict__ acts, const float *__restrict__ dpre,
                                                                 int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off,
                                                                 int dpre_off, float *__restrict__ dw_part,
-                                                                float *__restrict__ db_part, int64_t n_tiles, int n_chunks, int in_live) {
+                                                                float *__restrict__ db_part, int64_t n_tiles, int n_chunks, int in_live,
+                                                                int lwa_off, int lwb_off) {
     wgrad_regs_b3_body<IT>(acts, dpre, acts_tile_floats, dpre_tile_floats, act_off, dpre_off, dw_part, db_part, n_tiles, n_chunks,
-                           (int)blockIdx.x, in_live);
+                           (int)blockIdx.x, in_live, lwa_off, lwb_off);
 }
 
 // ---- layer 4 of a warp net with dPre4 REGENERATED instead of read (round 6) ------------------------------------
@@ -2377,7 +2463,7 @@ struct WgRegenRaw {
 __global__ __launch_bounds__(256, WG_REG_WAVES) void wgrad_regen_b3_kernel(
     const float *__restrict__ acts, const float *__restrict__ g5, int nout, int64_t M, const f32x4 *__restrict__ w3T,
     int64_t acts_tile_floats, int act_off, int mask_off, float *__restrict__ dw_part, float *__restrict__ db_part, int64_t n_tiles,
-    int n_chunks) {
+    int n_chunks, int lwb_off) {
     constexpr int IT = 4, NS = 3, BUF_F4 = IT * 6 * 64;
     const int chunk = (int)blockIdx.x;
     const int lane = threadIdx.x & 63, mt = threadIdx.x >> 6;
@@ -2399,12 +2485,19 @@ __global__ __launch_bounds__(256, WG_REG_WAVES) void wgrad_regen_b3_kernel(
     float bsum = 0.f;
     WgRegenRaw raw[NS];
     WgSl as[2];
+    // H4's rows by their line words, fetched one step ahead as in wgrad_regs_b3_body (lwb_off < 0: every row is fetched)
+    const int mtu = __builtin_amdgcn_readfirstlane(mt);
+    const uint32_t force_b = lwb_off < 0 ? ~0u : 0u;
+    const uint32_t *lwb0 = reinterpret_cast<const uint32_t *>(acts) + ((lwb_off < 0 ? 0 : lwb_off) + (mtu >> 1));
+    const int lwo = 2 * wg_line_half(i), bit_b = wg_line_bit(mtu, i);
+    uint32_t lwn;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #define RG_T(k) ((chunk + (k) * st) <= last ? (chunk + (k) * st) : last)
 #define RG_LD(set, k)                                                                                   \
     do {                                                                                                \
         const int64_t t_ = RG_T(k);                                                                     \
-        const f32x4 *b4_ = reinterpret_cast<const f32x4 *>(b0 + t_ * acts_tile_floats);                 \
+        const f32x4 *b4_ = reinterpret_cast<const f32x4 *>(wg_line_ptr(lwn | force_b, bit_b, b0 + t_ * acts_tile_floats)); \
+        lwn = (lwb0 + RG_T((k) + 1) * acts_tile_floats)[lwo];                                           \
         _Pragma("unroll") for (int j = 0; j < 4; j++) raw[set].b[j] = b4_[j];                           \
         raw[set].m = m0[t_ * (acts_tile_floats / 2)];                                                   \
         const int64_t p_ = t_ * TILE + i;                                                               \
@@ -2487,6 +2580,7 @@ __global__ __launch_bounds__(256, WG_REG_WAVES) void wgrad_regen_b3_kernel(
         __builtin_amdgcn_sched_barrier(0);                                                  \
     } while (0)
     if (n_my > 0) {
+        lwn = (lwb0 + RG_T(0) * acts_tile_floats)[lwo];
 #pragma unroll
         for (int q = 0; q < NS; q++) RG_LD(q, q);
         __builtin_amdgcn_sched_barrier(0);
@@ -2516,15 +2610,16 @@ __global__ __launch_bounds__(256, WG_REG_WAVES) void wgrad_regen_b3_kernel(
     if (g == 0) db_part[(int64_t)chunk * 128 + 32 * mt + i] = bsum;
 }
 
-template <int IT, bool B3 = false>
+template <int IT, bool B3 = false, bool LW = false>
 __global__ __launch_bounds__(256, 1) void wgrad_kernel(const float *__restrict__ acts, const float *__restrict__ dpre,
                                                        int64_t acts_tile_floats, int64_t dpre_tile_floats, int act_off,
                                                        int dpre_off, int out_pad, float *__restrict__ dw_part,
                                                        float *__restrict__ db_part, int64_t n_tiles, int n_chunks, int in_live,
-                                                       int out_live) {
+                                                       int out_live, int lw_off) {
+    static_assert(B3 || !LW, "line words belong to the b3 warp forward's tiles");
     if (B3)
-        wgrad_body_b3<IT>(acts, dpre, acts_tile_floats, dpre_tile_floats, act_off, dpre_off, out_pad, dw_part, db_part, n_tiles,
-                          n_chunks, (int)blockIdx.x, in_live, out_live);
+        wgrad_body_b3<IT, LW>(acts, dpre, acts_tile_floats, dpre_tile_floats, act_off, dpre_off, out_pad, dw_part, db_part, n_tiles,
+                              n_chunks, (int)blockIdx.x, in_live, out_live, lw_off);
     else
         wgrad_body<IT>(acts, dpre, acts_tile_floats, dpre_tile_floats, act_off, dpre_off, out_pad, dw_part, db_part, n_tiles,
                        n_chunks, (int)blockIdx.x, in_live, out_live);
@@ -2758,11 +2853,17 @@ struct WgRegenHost {
     int64_t M;
 };
 
+// line words of the b3 warp forward's tiles (wg_line_ptr): floats from the acts tile's start to the word of each layer's dPre
+// block (a) / activation block (b), -1 where the operand has none
+struct WgLineHost {
+    int a_off[WG_MAX_LAYERS], b_off[WG_MAX_LAYERS];
+};
+
 static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
                       int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
                       const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
                       const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles, void *stream,
-                      bool b3, const WgRegenHost *regen = nullptr) {
+                      bool b3, const WgRegenHost *regen = nullptr, const WgLineHost *lines = nullptr) {
     if (n_tiles == 0 || n_layers == 0) return MH_OK;
     if (!acts || !dpre || !act_off_host || !dpre_off_host || !in_feats_host || !out_feats_host || !workspace || !dw_raw ||
         !db_raw || n_layers < 0 || n_layers > WG_MAX_LAYERS || n_tiles < 0)
@@ -2815,20 +2916,27 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
         all.dw_off[l] = dw_poff[l];
         all.db_off[l] = db_poff[l];
         all.first_block[l + 1] = all.first_block[l] + chunks;
+        const int lwa = lines ? lines->a_off[l] : -1, lwb = lines ? lines->b_off[l] : -1;
         if (per_layer && b3 && out == 128 && in == 128 && regen && regen->on[l]) {
             hipLaunchKernelGGL(wgrad_regen_b3_kernel, dim3((unsigned)chunks), dim3(256), 2 * 4 * 6 * 1024, mh_stream(stream), acts,
                                regen->g5[l], regen->nout[l], regen->M, regen->w3T[l], acts_tile_floats, (int)act_off_host[l],
-                               regen->mask_off[l], workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks);
+                               regen->mask_off[l], workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, lwb);
             MH_CHECK_LAUNCH();
         } else if (per_layer && b3 && out == 128 && (in == 128 || in == 64)) {
             if (in == 128)
                 hipLaunchKernelGGL(wgrad_regs_b3_kernel<4>, dim3((unsigned)chunks), dim3(256), 2 * 4 * 6 * 1024, mh_stream(stream),
                                    acts, dpre, acts_tile_floats, dpre_tile_floats, (int)act_off_host[l], (int)dpre_off_host[l],
-                                   workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, in_live);
+                                   workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, in_live, lwa, lwb);
             else
                 hipLaunchKernelGGL(wgrad_regs_b3_kernel<2>, dim3((unsigned)chunks), dim3(256), 2 * 2 * 6 * 1024, mh_stream(stream),
                                    acts, dpre, acts_tile_floats, dpre_tile_floats, (int)act_off_host[l], (int)dpre_off_host[l],
-                                   workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, in_live);
+                                   workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, in_live, lwa, lwb);
+            MH_CHECK_LAUNCH();
+        } else if (per_layer && b3 && in == 128 && lwb >= 0) {
+            // (the warp nets' output layers: H5's rows by its line words, dPre5 has none)
+            hipLaunchKernelGGL((wgrad_kernel<4, true, true>), dim3((unsigned)chunks), dim3((unsigned)(out / 32) * 64), 0, mh_stream(stream),
+                               acts, dpre, acts_tile_floats, dpre_tile_floats, (int)act_off_host[l], (int)dpre_off_host[l], out,
+                               workspace + dw_poff[l], workspace + db_poff[l], n_tiles, chunks, in_live, out_live, lwb);
             MH_CHECK_LAUNCH();
         } else if (per_layer) {
             const dim3 grid((unsigned)chunks), block((unsigned)(out / 32) * 64);
@@ -2836,11 +2944,11 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
     if (b3)                                                                                                   \
         hipLaunchKernelGGL((wgrad_kernel<IT, true>), grid, block, 0, mh_stream(stream), acts, dpre, acts_tile_floats, \
                            dpre_tile_floats, (int)act_off_host[l], (int)dpre_off_host[l], out, workspace + dw_poff[l], \
-                           workspace + db_poff[l], n_tiles, chunks, in_live, out_live);                       \
+                           workspace + db_poff[l], n_tiles, chunks, in_live, out_live, 0);                    \
     else                                                                                                      \
         hipLaunchKernelGGL((wgrad_kernel<IT, false>), grid, block, 0, mh_stream(stream), acts, dpre, acts_tile_floats, \
                            dpre_tile_floats, (int)act_off_host[l], (int)dpre_off_host[l], out, workspace + dw_poff[l], \
-                           workspace + db_poff[l], n_tiles, chunks, in_live, out_live)
+                           workspace + db_poff[l], n_tiles, chunks, in_live, out_live, 0)
             switch (in / 32) {
                 case 1: WG_LAUNCH(1); break;
                 case 2: WG_LAUNCH(2); break;
@@ -2949,6 +3057,15 @@ static WarpWg warp_wg_geometry() {
     return w;
 }
 
+// Process-wide switch of the per-layer b3 kernels' line-word skipping (wg_line_ptr; 1 = on, the default; set < 0 only reads it).
+// Off, every parked row is fetched as before round 8 -- the same bits either way: it serves the A/B and the tests.  The forward
+// parks the words regardless.
+static std::atomic<int64_t> g_warp_skip_zero_lines{1};
+extern "C" int64_t mh_warp_skip_zero_lines(int64_t set) {
+    if (set >= 0) g_warp_skip_zero_lines.store(set ? 1 : 0, std::memory_order_relaxed);
+    return g_warp_skip_zero_lines.load(std::memory_order_relaxed);
+}
+
 // dPre4 is regenerated by the large-batch (one launch per layer) weight-gradient path only
 extern "C" int32_t mh_warp_regen_dpre4(int64_t M) { return M > 0 && n_tiles_for(M) >= WG_PER_LAYER_TILES ? 1 : 0; }
 
@@ -2975,8 +3092,19 @@ extern "C" int mh_warp_wgrad_b3(const float *acts, const float *dpre, const floa
         rg.w3T[k] = reinterpret_cast<const f32x4 *>(net ? w3T_t : w3T_d);
         rg.mask_off[k] = WARP_HID_ROWS * TILE + (net * 5 + 4) * 64 * 2;
     }
+    // word `j` of a net = its hidden layer j + 1: the mask of dPre_j (j <= 4) and of H_(j+1), the input of layer j + 1
+    WgLineHost ln;
+    for (int k = 0; k < WG_MAX_LAYERS; k++) ln.a_off[k] = ln.b_off[k] = -1;
+    for (int net = 0; net < 2; net++)
+        for (int l = 0; l < 6; l++) {
+            const int word0 = WARP_LINE_ROW * TILE + (net * 5) * 4;      // 4 floats = the two halves' 64-bit words of a layer
+            if (l <= 4) ln.a_off[net * 6 + l] = word0 + l * 4;
+            if (l >= 1) ln.b_off[net * 6 + l] = word0 + (l - 1) * 4;
+        }
+    const bool skip = g_warp_skip_zero_lines.load(std::memory_order_relaxed) != 0;
     return wgrad_impl(acts, dpre, (int64_t)WARP_ACT_ROWS * TILE, (int64_t)WARP_DPRE_ROWS * TILE, 12, w.act_off, w.dpre_off, w.in, w.out,
-                      w.in_live, w.out_live, workspace, dw_raw, db_raw, n_tiles_for(M), stream, true, regen_dpre4 ? &rg : nullptr);
+                      w.in_live, w.out_live, workspace, dw_raw, db_raw, n_tiles_for(M), stream, true, regen_dpre4 ? &rg : nullptr,
+                      skip ? &ln : nullptr);
 }
 
 // ---- fused field backward (backward-data + weight gradients, see field_fused_*_kernel) ---------------------------------

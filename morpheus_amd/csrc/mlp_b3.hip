@@ -379,6 +379,31 @@ __device__ __forceinline__ void b3_interleave() {
     }
 }
 
+// ---- line words (round 8) -------------------------------------------------------------------------------------------------
+// A parked row [feature][32 points] is one 128-byte line, and the 32 points of a tile are consecutive samples of a ray: a ReLU
+// unit that is off stays off along most of it, so a quarter to a half of the parked lines are all zero.  The sign word a lane parks
+// (bit 16 t + r <-> its value of row 32 t + acc_row(r, h) is non-zero), OR-ed over the 32 lanes of its half, says which rows of the
+// tile carry anything: one 64-bit word per (net, layer, half), parked in the dead rows 40.. of the tile's H0 block (WARP_LINE_ROW).
+// A bit is 0 only when all 32 stored values of the row are zero bits (a partial tile's lanes past M store their values too and
+// count).  dPre_l is masked by the same sign words, so the word of H_(l+1) is the word of the dPre_l block as well; the weight-
+// gradient kernels (mlp.hip: wg_line_ptr) fetch a 64-byte zero line instead of a row whose bit is 0.
+// Row DPP only (no LDS pipe): four shifts leave lane 15 of every row with its row's OR, row_bcast15 hands it on to the odd rows:
+// lanes 31 and 63 hold their half's OR.
+__device__ __forceinline__ uint32_t b3_or_half(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);      // row_shr:1
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);      // row_shr:2
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);      // row_shr:4
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);      // row_shr:8
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1, 3
+    return v;
+}
+// words of layer `idx` = net * 5 + (hidden layer - 1): lane 31 of each half stores its half's word
+__device__ __forceinline__ void b3_park_line_word(float *__restrict__ tile, int idx, int pt, int h, uint32_t lo, uint32_t hi) {
+    lo = b3_or_half(lo);
+    hi = b3_or_half(hi);
+    if (pt == 31) reinterpret_cast<uint2 *>(tile + WARP_LINE_ROW * TILE)[idx * 2 + h] = make_uint2(lo, hi);
+}
+
 template <int NW, bool PARK>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
     const float *__restrict__ x, const int32_t *__restrict__ slot, const float *__restrict__ bias0_d,
@@ -407,7 +432,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #pragma unroll
     for (int k = 20; k < 24; k++) bin0[k] = 0.f;
     if (PARK) {
-        // k-step ordered; the pad rows 40..63 are neither written nor read (wg_row; profiles/r06_ab_pad_rows.txt)
+        // k-step ordered; the pad rows 40..63 hold no activations (wg_row; profiles/r06_ab_pad_rows.txt): the first 160 bytes of
+        // row 40 take the tile's line words (b3_park_line_word), the rest is neither written nor read
 #pragma unroll
         for (int k = 0; k < 20; k++) tile[(2 * k + h) * TILE + pt] = bin0[k];
     }
@@ -455,7 +481,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
             asm volatile("" : "+v"(mt[2]), "+v"(mt[3]));
             b3_interleave<48, B3_Q_FILL>();
             __builtin_amdgcn_sched_barrier(0);
-            if (PARK) mk[(net * 5 + l - 1) * 64 + lane] = make_uint2(mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+            if (PARK) {
+                mk[(net * 5 + l - 1) * 64 + lane] = make_uint2(mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+                b3_park_line_word(tile, net * 5 + l - 1, pt, h, mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+            }
             if (net == 0) B3_STAMP((l - 1) * 8 + 1);
             // ---- Q2
             b3_acc_bias_row<2, 2, 4>(acc, h, row);
@@ -512,7 +541,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
         asm volatile("" : "+v"(mt[2]), "+v"(mt[3]));
         b3_interleave<24, 12>();
         __builtin_amdgcn_sched_barrier(0);
-        if (PARK) mk[(net * 5 + 4) * 64 + lane] = make_uint2(mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+        if (PARK) {
+            mk[(net * 5 + 4) * 64 + lane] = make_uint2(mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+            b3_park_line_word(tile, net * 5 + 4, pt, h, mt[0] | (mt[1] << 16), mt[2] | (mt[3] << 16));
+        }
 #pragma unroll
         for (int s = 4; s < 8; s++) b3_l5_step(slot1, bh, bm, bl, o[0], lane, s);
         b3_point<0>();                                     // slot 1 is free (net 0: the other net's L0 has landed)

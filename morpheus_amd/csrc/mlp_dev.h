@@ -14,6 +14,9 @@
 #define WARP_HID_ROWS (64 + 2 * 640)        // activations proper
 #define WARP_ACT_ROWS (WARP_HID_ROWS + 40)  // + ReLU masks: 10 layers x 64 lanes x 2 dwords = 40 rows of 32
 #define WARP_DPRE_ROWS (2 * 672)
+// b3 only: "this row of the tile has a non-zero" words, [net][hidden layer 1..5][half h] uint64 (bit 16t+r <-> row
+// 32t + acc_row(r,h)), 160 bytes at the head of H0's dead rows (40..63 carry no encoding value)
+#define WARP_LINE_ROW 40
 #define WARP_NET_WPACK (5120 + 4 * 16384 + 4096)       // fwd pack floats per net
 #define WARP_NET_WPACKT (4096 /*T5*/ + 4 * 16384 + 8192 /*T0: MT=2,KS=64*/)
 #define WARP_NET_BIAS (4 * 128 + 32)
