@@ -26,6 +26,7 @@
  *                               models/decoders.py:59-64, models/encodings.py:35-57,
  *                               models/density.py:22-31 -- plain PyTorch in the reference
  *   mh_mlp_wgrad                the weight-gradient GEMMs autograd ran for those MLPs
+ *   mh_adam_step / mh_adan_step torch.optim.Adam (morpheus.py:154-155) / models/optimizer.py:101-256 (Adan, morpheus.py:146-150)
  * The warp / field entries exist in two arithmetic forms of the SAME interface -- fp32 in, fp32 out, same parked tiles:
  * native fp32 MFMA (no suffix) and exact three-way bf16 splits (_b3: fp32-faithful, what the Python side calls by default --
  * morpheus_amd/ops.py, MORPHEUS_MLP); mh_b3_slice cuts the weight operands of the latter.
@@ -441,6 +442,36 @@ int mh_adam_step(float *params, const float *grads, float *exp_avg, float *exp_a
 int mh_adam_step_dev(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t n_segs,
                      const int64_t *seg_end_host, const float *seg_lr_host, const float *seg_flag_dev, int64_t *seg_step_dev,
                      float *seg_scratch_dev, float beta1, float beta2, float eps, void *stream);
+
+/* ---- optimiser: fused Adan over one flat fp32 bucket (csrc/adan.hip) ---------------------------------------------------
+ * Replaces Adan(model.get_params_all(5 lr), eps=1e-8, weight_decay=2e-5, max_grad_norm=5.0, foreach=False), morpheus.py:146-150,
+ * the rule of models/optimizer.py:101-256 (_single_tensor_adan, every operator rounded in its order).  params / grads / exp_avg /
+ * exp_avg_sq / exp_avg_diff / neg_pre_grad: [n] fp32 device buffers, 16-byte aligned, cut into the segments of mh_adam_step
+ * (n_segs <= 160).  HOST arrays per segment: seg_end_host (exclusive ends, last == n), seg_lr_host (its group's learning rate, a
+ * double as Python holds it), seg_step_host (its GROUP's 1-based step count: Adan counts per group, whether or not a parameter
+ * had a gradient), seg_flag_host (bit 0: no gradient this time -- value and all four states keep their bits; bit 1: the
+ * parameter's first gradient -- neg_pre_grad starts as -c g; a group step of 1 implies it).  Step sizes, bias corrections and the
+ * decay factor are formed in double on the host and rounded to fp32.  betas in [0, 1); eps, weight_decay, max_grad_norm >= 0.
+ * max_grad_norm > 0: c = min(max_grad_norm / (sqrt(sum g g) + eps), 1) over the segments that have a gradient, summed in double
+ * in a fixed order (no atomics: the same bits on every run), rounded once to fp32 and left on the device; the gradients are scaled
+ * by it IN PLACE, as the reference scales p.grad.  max_grad_norm == 0: c = 1, no norm pass, grads are only read.
+ * workspace: mh_adan_workspace_bytes() bytes, 16-byte aligned; its first three floats are c, the sum of squares and the norm of
+ * the last call; the segment table follows.  The host never reads it: no synchronisation.
+ * Bad arguments return MH_ERR_ARG before any launch; n == 0 returns MH_OK without one. */
+int64_t mh_adan_workspace_bytes(void);
+int mh_adan_step(float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *exp_avg_diff, float *neg_pre_grad,
+                 int64_t n, int32_t n_segs, const int64_t *seg_end_host, const double *seg_lr_host, const int64_t *seg_step_host,
+                 const int32_t *seg_flag_host, double beta1, double beta2, double beta3, double eps, double weight_decay,
+                 double max_grad_norm, int32_t no_prox, void *workspace, void *stream);
+/* The same step with "has a gradient" ON THE DEVICE, for data-parallel runs: seg_flag_dev [n_segs] > 0 = the segment is stepped
+ * (the all-reduced has-gradient flags of the bucket; 0, a negative value or NaN: skipped); seg_seen_dev [n_segs] int64 in/out =
+ * how many gradients the segment has seen: it goes up where the flag is positive, and 0 before makes this the first gradient.
+ * Group steps advance unconditionally, so they still come from the host. */
+int mh_adan_step_dev(float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *exp_avg_diff, float *neg_pre_grad,
+                     int64_t n, int32_t n_segs, const int64_t *seg_end_host, const double *seg_lr_host,
+                     const int64_t *seg_step_host, const float *seg_flag_dev, int64_t *seg_seen_dev, double beta1, double beta2,
+                     double beta3, double eps, double weight_decay, double max_grad_norm, int32_t no_prox, void *workspace,
+                     void *stream);
 
 /* ---- caller-side glue as single launches (csrc/losses.hip) -------------------------------------------------------------
  * Per-sample means of the training losses.  kind: 0 a, 1 a^2, 2 |a|, 3 binary entropy in bits of clamp(a, 1e-5, 1 - 1e-5)
