@@ -735,6 +735,47 @@ int mh_icp_transform(const float *src, int64_t N, const double *T_host, float *o
 int mh_icp_sums(const float *p, int64_t N, const float *target, int64_t Nt, const int32_t *idx, const float *d2,
                 void *workspace, double *sums, void *stream);
 
+/* ---- pose initialisation (preprocess/pose_init/registrate.py of the reference: mask2camera, and the robust rigid registration
+ * it hands to the external program FRICP, method 3; csrc/poseinit.hip) ------------------------------------------------------------
+ * Every fp32 and float64 expression below is evaluated operator by operator, round to nearest, no FMA, in the written order
+ * (tests/poseinit_oracle.py is written from this text).  All counts are in [0, 2^31).
+ *   masked back-projection (mh_depth_points_count, mh_depth_points_emit): depth [H][W] fp32 in metres, mask [H][W] uint8, H, W in
+ *     [0, 16384].  Pixel (u, v) = (column, row) is KEPT when mask[v][u] != 0 and depth[v][u] > 0 (false for a NaN depth).  fx, fy,
+ *     cx, cy are HOST doubles, fx and fy non-zero, none a NaN.  With d = depth[v][u], in float64 from the fp32 depth, one rounding:
+ *       x = (float)(((double)d * ((double)u - cx)) / fx),  y = (float)(((double)d * ((double)v - cy)) / fy),  z = d
+ *     -- the pixel's integer coordinates, as mask2camera has them (no half-pixel offset).  The image is cut, in row-major pixel
+ *     order i = v*W + u, into tiles of mh_depth_points_tile() pixels (host only).  mh_depth_points_count: counts [tiles] DEVICE
+ *     int64, the kept pixels of each tile, tiles = ceil(H*W / tile).  The caller's exclusive prefix sum tile_start (DEVICE int64
+ *     [tiles], or [tiles + 1] with the total behind) is integer and exact in any order; n = the total, as the caller read it.
+ *     mh_depth_points_emit: points [n,3] fp32 in row-major pixel order (the order of numpy.nonzero(mask)); pixel [n] int32 or
+ *     NULL: the index i of every point.  A point whose place falls outside [0, n) is not written.  H == 0, W == 0 or (emit)
+ *     n == 0 return MH_OK without a launch.
+ *   k nearest distances (mh_knn_d2): points [N,3] fp32, k in [1, 8].  For point i, over all j != i (excluded by INDEX: another
+ *     point with the same coordinates counts, with d2 = 0): dx = p_i.x - p_j.x, dy, dz likewise, d2 = (dx*dx + dy*dy) + dz*dz in
+ *     fp32, as in mh_nn_search.  out_d2 [N][k] fp32: the k smallest admissible d2 in ascending order; a d2 is admissible when
+ *     d2 < +inf (a NaN or an overflowed d2 never enters); entries for which none is left are +inf.  Exact brute force over all
+ *     N * N pairs; values only, so equal d2 need no tie rule.  mh_knn_tile_points: points per LDS tile (host only; for tests; 256
+ *     points per workgroup).
+ *   Welsch-weighted sums (mh_icp_wsums): mh_icp_sums with a weight per correspondence.  inv_2nu2 = 1 / (2 nu^2) is a HOST
+ *     double, >= 0 and finite.  Over the points i with 0 <= idx[i] < Nt, with p = p[i], q = target[idx[i]] and dd = d2[i] (fp32
+ *     values taken to float64; dd finite), all in float64:
+ *       w = exp(-dd * inv_2nu2)   (the device's float64 exp: within an ulp or so of the correctly rounded value);  wp_a = w * p_a;
+ *     sums [19] DEVICE doubles = {sum w, sum w*dd, sum wp_a (3), sum w*q_b (3), sum wp_a*q_b (9, at 8 + 3a + b), sum (1.0 - w),
+ *     the number of such i}.  The partition of the points, the order of every addition and the meeting of lanes, wavefronts and
+ *     workgroups are mh_icp_sums': with inv_2nu2 = 0 (w = 1.0) sums[0..16] are the bytes mh_icp_sums returns, and the rigid
+ *     motion of the weighted least-squares problem comes from sums[0..16] by the same formulas.  The same bytes run to run.
+ *     workspace: mh_icp_wsums_workspace_bytes() DEVICE bytes (host only).
+ * Bad arguments return MH_ERR_ARG before any launch; N == 0 returns MH_OK without a launch and writes nothing. */
+int32_t mh_depth_points_tile(void);
+int mh_depth_points_count(const float *depth, const uint8_t *mask, int32_t H, int32_t W, int64_t *counts, void *stream);
+int mh_depth_points_emit(const float *depth, const uint8_t *mask, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                         const int64_t *tile_start, int64_t n, float *points, int32_t *pixel, void *stream);
+int32_t mh_knn_tile_points(void);
+int mh_knn_d2(const float *points, int64_t N, int32_t k, float *out_d2, void *stream);
+int64_t mh_icp_wsums_workspace_bytes(void);
+int mh_icp_wsums(const float *p, int64_t N, const float *target, int64_t Nt, const int32_t *idx, const float *d2, double inv_2nu2,
+                 void *workspace, double *sums, void *stream);
+
 /* ---- TSDF fusion (run_tsdf_fusion / back_proj_frame, tools/vis.py:251-361 of the reference: Open3D's ScalableTSDFVolume on the
  * host there; csrc/tsdf.hip) ----------------------------------------------------------------------------------------------------
  * RGB-D frames are fused into a truncated signed distance volume whose zero set mh_mc_*_masked extracts.  The rules restate

@@ -1,10 +1,11 @@
-"""The bottom layer of the mesh tool chain, what mesh, tsdf, meshrender and mesheval all need: host arrays and their pointers for
+"""The bottom layer of the mesh tool chain, what mesh, tsdf, meshrender, mesheval and poseinit all need: host arrays and their pointers for
 the C ABI, camera poses and intrinsics, the checks on mesh and point arrays, mh_icp_transform, the memory cap, the device refusal.
 Every pose goes through ONE sequence of numpy operations (world_to_camera): the kernels get the same bytes whichever module asks.
 
 Import order, at module level only (no import of the package inside a function body):
     geometry <- mesh <- tsdf
     geometry <- meshrender <- mesheval          (meshrender and mesheval may also import mesh)
+    geometry <- meshrender <- mesheval <- poseinit
 geometry itself imports only _lib and chunking.
 """
 from __future__ import annotations
