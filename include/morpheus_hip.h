@@ -27,6 +27,9 @@
  *                               models/density.py:22-31 -- plain PyTorch in the reference
  *   mh_mlp_wgrad                the weight-gradient GEMMs autograd ran for those MLPs
  *   mh_adam_step / mh_adan_step torch.optim.Adam (morpheus.py:154-155) / models/optimizer.py:101-256 (Adan, morpheus.py:146-150)
+ *   mh_freq_encode_fwd / _bwd   external/encoders/freqencoder/src/freqencoder.cu:28-94 (freq.py:15-52), and the progressive
+ *                               max_level of FreqEncoder_torch, models/encodings.py:35-57
+ *   mh_sh_encode_fwd / _bwd     external/encoders/shencoder/src/shencoder.cu:28-end (sphere_harmonics.py:14-58)
  * The warp / field entries exist in two arithmetic forms of the SAME interface -- fp32 in, fp32 out, same parked tiles:
  * native fp32 MFMA (no suffix) and exact three-way bf16 splits (_b3: fp32-faithful, what the Python side calls by default --
  * morpheus_amd/ops.py, MORPHEUS_MLP); mh_b3_slice cuts the weight operands of the latter.
@@ -916,6 +919,44 @@ int mh_mc_emit_sparse(const float *pool_tsdf, const float *pool_weight, const in
                       float *vertices, int32_t *triangles, void *stream);
 int mh_tsdf_sparse_vertex_colors(const float *vertices, int64_t V, const float *pool_color, const int32_t *slot, int32_t nbx,
                                  int32_t nby, int32_t nbz, int32_t capacity, float *out, void *stream);
+
+/* ---- frequency and spherical-harmonics encoders (csrc/encoders.hip) ---------------------------
+ * The reference's other two native encoders.  No entry point synchronises with the host; B == 0 returns MH_OK without a launch;
+ * a null pointer with B > 0 or an argument outside the stated range returns MH_ERR_ARG before any device call.  Buffers that are
+ * 16-byte aligned are moved 16 bytes a lane; others are served by the same kernels a dword at a time, with the same results.
+ *
+ * mh_freq_encode_fwd: x [B,D] -> out [B,C], C = D + 2 D degree; 1 <= D <= 8, 0 <= degree <= 16, 0 <= n_keep <= degree.
+ *   columns [0, D): x, copied bit for bit; then for band f = 0 .. degree-1 a block of D sines and a block of D cosines of
+ *   2^f x[d] (freqencoder.cu:28-58; FreqEncoder_torch's layout, encodings.py:42-55).  The blocks of the bands f >= n_keep are
+ *   written as +0.0: the progressive max_level of FreqEncoder_torch, which the reference's CUDA kernel does not have.
+ *   The argument is ldexpf(x, f), exact, and sine and cosine both come from that one argument (sincosf).  The reference takes the
+ *   cosine as __sinf(arg + pi/2): the addition throws away up to half an ulp of an argument as large as 2^(degree-1) |x|, an error
+ *   of that size in the result, and __sinf is the fast approximation.  Neither is reproduced here.
+ * mh_freq_encode_bwd: grad [B,C] -> grad_x [B,D], WRITTEN (not accumulated):
+ *   grad_x[d] = grad[d] + sum_{f < n_keep} 2^f (g_sin[f,d] cos(2^f x[d]) - g_cos[f,d] sin(2^f x[d]))        (freqencoder.cu:63-94)
+ *   with sine and cosine recomputed from x as in the forward (the forward's output is not an operand: nothing of B C floats is
+ *   kept alive for the backward).  Order: the sum starts from grad[d]; bands ascending; per band two rounded products, their
+ *   rounded difference, the exact scaling by 2^f, one rounded addition.
+ *
+ * mh_sh_encode_fwd: x [B,3] -> out [B, degree^2], 1 <= degree <= 8.  Column c = l^2 + l + m (0 <= l < degree, -l <= m <= l) holds the
+ *   real spherical harmonic in the reference's convention (shencoder.cu:50-120): polynomials in (x, y, z) with x^2 + y^2 + z^2 = 1
+ *   already substituted, evaluated as they stand for ANY input -- nothing is normalised:
+ *     m = 0:  K(l,0) P_l(z)
+ *     m > 0:  (-1)^m sqrt(2) K(l,m)   T(l,m)(z)   Re (x + iy)^m
+ *     m < 0:  (-1)^m sqrt(2) K(l,|m|) T(l,|m|)(z) Im (x + iy)^|m|
+ *   K(l,m) = sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!), T(l,m) = d^m P_l / dz^m, P_l the Legendre polynomial.  The evaluation is the
+ *   straight-line fp32 program of csrc/sh_table.inc (generated by tools/make_sh_table.py from this definition; every operator
+ *   rounded on its own, one fixed order), so the result is that program's, bit for bit.
+ * mh_sh_encode_bwd: grad [B, degree^2] -> grad_x [B,3], WRITTEN: grad_x[a] = sum_c grad[c] dY_c/dx_a, the derivative polynomials
+ *   evaluated by the same program (the reference stores dy_dx [B, 3 degree^2] in the forward and reads it back,
+ *   sphere_harmonics.py:27-34; here nothing is stored).  Order: each sum starts at +0; columns ascending; the product
+ *   grad[c] (dY_c/dx_a) is rounded, then added to the running sum.  A derivative that is identically zero (d/dx and d/dy of the
+ *   m = 0 columns, d/dy of m = 1, d/dx of m = -1, d/dz of |m| = l) contributes no term. */
+int mh_freq_encode_fwd(const float *x, int64_t B, int32_t D, int32_t degree, int32_t n_keep, float *out, void *stream);
+int mh_freq_encode_bwd(const float *x, const float *grad, int64_t B, int32_t D, int32_t degree, int32_t n_keep, float *grad_x,
+                       void *stream);
+int mh_sh_encode_fwd(const float *x, int64_t B, int32_t degree, float *out, void *stream);
+int mh_sh_encode_bwd(const float *x, const float *grad, int64_t B, int32_t degree, float *grad_x, void *stream);
 
 #ifdef __cplusplus
 }

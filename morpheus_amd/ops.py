@@ -1691,6 +1691,79 @@ def weighted_sum(pairs):
     return _WeightedSum.apply(wt, *[t for _, t in pairs])
 
 
+# ------------------------------------------------------------------------------------ frequency / spherical-harmonics encoders
+def _encoder_rows(x, D: Optional[int], what: str):
+    """the [B, D] fp32 contiguous rows of a device tensor (any dtype an autocast caller may hand over); D None: any width"""
+    require_gpu(x)
+    if x.dim() != 2 or (D is not None and x.shape[1] != D):
+        raise _lib.MorpheusHipError(f"{what}: expected [B, {'D' if D is None else D}] rows, got {tuple(x.shape)}")
+    return x.detach().contiguous().float()
+
+
+class _FreqEncode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, degree, n_keep):
+        ctx.set_materialize_grads(False)
+        x_c = _encoder_rows(x, None, "freq_encode")
+        B, D = x_c.shape
+        out = torch.empty(B, D + 2 * D * degree, device=x_c.device)
+        _timed("mh_freq_encode_fwd", ptr(x_c), B, D, degree, n_keep, ptr(out))
+        ctx.save_for_backward(x_c)              # the forward's output is not an operand of the backward
+        ctx.args = (degree, n_keep, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        (x_c,) = ctx.saved_tensors
+        degree, n_keep, dtype = ctx.args
+        B, D = x_c.shape
+        g_x = torch.empty_like(x_c)
+        _timed("mh_freq_encode_bwd", ptr(x_c), ptr(g.contiguous().float()), B, D, degree, n_keep, ptr(g_x))
+        return g_x.to(dtype), None, None
+
+
+def freq_encode(x, degree: int, n_keep: Optional[int] = None):
+    """x [B, D] (1 <= D <= 8) -> [B, D + 2 D degree] fp32: x, then per band f < degree a block of D sines and a block of D cosines of
+    2^f x (freqencoder.cu:28-58); the blocks of the bands f >= n_keep (default: degree) are zero, as FreqEncoder_torch's max_level
+    leaves them (encodings.py:35-57).  One launch each way; the backward recomputes sine and cosine from x and runs only when x
+    needs a gradient.  Under autocast: fp32 in, fp32 out (the reference's custom_fwd(cast_inputs=torch.float32))."""
+    degree = int(degree)
+    n_keep = degree if n_keep is None else int(n_keep)
+    return _FreqEncode.apply(x, degree, n_keep)
+
+
+class _SHEncode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, degree):
+        ctx.set_materialize_grads(False)
+        x_c = _encoder_rows(x, 3, "sh_encode")
+        B = x_c.shape[0]
+        out = torch.empty(B, degree * degree, device=x_c.device)
+        _timed("mh_sh_encode_fwd", ptr(x_c), B, degree, ptr(out))
+        ctx.save_for_backward(x_c)              # no dy_dx [B, 3 degree^2] is kept: the backward evaluates the derivative polynomials
+        ctx.args = (degree, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None
+        (x_c,) = ctx.saved_tensors
+        degree, dtype = ctx.args
+        g_x = torch.empty_like(x_c)
+        _timed("mh_sh_encode_bwd", ptr(x_c), ptr(g.contiguous().float()), x_c.shape[0], degree, ptr(g_x))
+        return g_x.to(dtype), None
+
+
+def sh_encode(x, degree: int):
+    """x [B, 3] -> [B, degree^2] fp32 (1 <= degree <= 8): the real spherical harmonics in the reference's convention, polynomials
+    evaluated as they stand (shencoder.cu:28-120; include/morpheus_hip.h states them).  One launch each way, the backward only when x
+    needs a gradient."""
+    return _SHEncode.apply(x, int(degree))
+
+
 # ------------------------------------------------------------------------------------------ HIP-graph hygiene
 def graph_memset_nodes(graph: "torch.cuda.CUDAGraph"):
     """(nodes, memset nodes, smallest memset in bytes) of a captured, not yet instantiated graph (`CUDAGraph(keep_graph=True)`)."""
