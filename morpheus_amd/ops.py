@@ -1423,7 +1423,7 @@ class _MaskedMean(torch.autograd.Function):
         b_c = None if b is None else b.detach().contiguous().float()
         assert a_c.dim() >= 1 and (b_c is None or b_c.shape == a_c.shape)
         M = a_c.shape[0]
-        C = max(a_c.numel() // max(M, 1), 1)
+        C = max(math.prod(a_c.shape[1:]), 1)          # from the trailing shape: an empty [0, 3] tensor still has C = 3
         w_c = None if w_row is None else w_row.detach().reshape(-1).contiguous().float()
         assert w_c is None or w_c.numel() == M
         nv = None if n_valid is None else n_valid.detach().reshape(1).to(torch.int32).contiguous()
@@ -1440,11 +1440,11 @@ class _MaskedMean(torch.autograd.Function):
             return None, None, None, None, None
         a_c, b_c, w_c, nv, out = ctx.saved_tensors
         M = a_c.shape[0]
-        C = max(a_c.numel() // max(M, 1), 1)
+        C = max(math.prod(a_c.shape[1:]), 1)
         want_a, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and b_c is not None
         g_a = torch.empty_like(a_c) if want_a else None
         g_b = torch.empty_like(b_c) if want_b else None
-        if want_a or want_b:
+        if (want_a or want_b) and a_c.numel():        # (an empty gradient has no address to hand over: nothing to launch)
             launch("mh_masked_mean_bwd", ctx.kind, ptr(a_c), ptr(b_c), ptr(w_c), M, C, ptr(nv), ptr(out),
                    ptr(g.reshape(1).contiguous().float()), ptr(g_a), ptr(g_b))
         return None, g_a, g_b, None, None

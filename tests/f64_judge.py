@@ -8,9 +8,11 @@ Where the scale is 0 the value must be the yardstick's exactly.  The callers dif
 
     caller                         factor  floor      count threshold                           slack  restatement at zero scale
     step_f64_oracle.judge          2       4 U        the floor                                 2      asserted exact
+    losses_f64_oracle.judge        2       4 U (*)    the floor                                 2      asserted exact
     glue_f64_oracle.judge          3       count x U  max(99.9th pct of the restatement, floor)  2      not asserted
     util.assert_close_vs_f64       2       tol        the floor (scale = max(|f64|, rel floor))  2      no scale is 0
     grid_f64_cases.gate            3       2^-22      (per-level norms through `within` alone: no element count)
+    (*) sums and the rotated direction: the kernel's own chain of roundings x U (mean_depth, render_depth, pose_forward_floor)
 """
 import json
 import os
