@@ -958,6 +958,50 @@ int mh_freq_encode_bwd(const float *x, const float *grad, int64_t B, int32_t D, 
 int mh_sh_encode_fwd(const float *x, int64_t B, int32_t degree, float *out, void *stream);
 int mh_sh_encode_bwd(const float *x, const float *grad, int64_t B, int32_t degree, float *grad_x, void *stream);
 
+/* ---- nerfacc's volume-rendering functions (csrc/volrend.hip; morpheus_amd/volrend.py is their Python face) ---------------
+ * render_transmittance / render_weight _from_density / _from_alpha, accumulate_along_rays and pack_info of nerfacc 0.5.x under
+ * their own names, forward and backward.  nerfacc is third-party, un-vendored and not installed where this library is built: the
+ * definitions are restated as recalled and are NOT verified against it (tools/check_against_nerfacc.py compares on a machine
+ * that has it).  mh_composite_* above stays the fused form of the shipped render loop; these are its parts.  Purely additive:
+ * MH_ABI_VERSION is unchanged (the precedent is mh_subdiv_*).
+ * Samples of ray r are [ray_start[r], ray_start[r] + ray_cnt[r]) of the packed arrays, ordered by t; x_i = sigma_i (te_i - ts_i).
+ *   density form (alpha_form = 0): alpha_i = -expm1f(-x_i);  T_i = expf(-sum_{j<i} x_j)
+ *   alpha form   (alpha_form = 1): alpha_i = values_i, taken as <= 1;  T_i = prod_{j<i} (1 - alpha_j); t_starts / t_ends may be NULL
+ *   both: w_i = T_i alpha_i.  One wavefront per ray, 64-sample chunks, a wave scan and a scalar carry; the exclusive sum takes
+ *   the lane below instead of subtracting the sample's own term where x_i >= 1 (the compositor's rule), the exclusive product
+ *   always does.  sigma = +inf: the sample takes the remaining transmittance, exact zeros behind it; a NaN stays in its ray.
+ * mh_pack_info: ray_indices int32 or int64 [M], NON-DECREASING (not checked) -> ray_start, ray_cnt int32 [N], for every ray,
+ *   the rays no sample names included (count 0); a bisection per ray, one launch, no host synchronisation; indices outside
+ *   [0, N) belong to no ray; every read is inside [0, M).  M < 2^31.
+ * mh_ray_weights_fwd: writes weights, trans, alphas [M], each of which may be NULL (not all three).
+ * mh_ray_weights_bwd: g_weights, g_trans, g_alphas [M] may each be NULL (= zeros; g_alphas must be NULL in alpha form);
+ *   writes d_values [M] = dL/dsigma or dL/dalpha for every sample a ray owns.
+ *   density: dL/dx_i = (g_w_i T_i + g_a_i)(1 - alpha_i) - sum_{j>i} (g_w_j w_j + g_T_j T_j), d_sigma_i = (te_i - ts_i) dL/dx_i;
+ *            one reverse pass that READS `trans`, the forward's output (required).
+ *   alpha:   dL/dalpha_i = g_w_i T_i - sum_{j>i} (g_w_j alpha_j + g_T_j) prod_{k<j, k != i} (1 - alpha_k) -- the product with
+ *            factor i left out, never T_j / (1 - alpha_i): finite and correct at alpha_i = 1.  A forward pass parks the product
+ *            of the non-zero factors and the count of zero factors in d_values, a reverse pass forms one suffix sum per count;
+ *            `trans` is not read and may be NULL.
+ * mh_accumulate_fwd: out [N, D] = sum_{i in ray} weights_i values[i, :], values [M, D], 1 <= D <= 256; values NULL = a column
+ *   of ones (D must be 1).  A ray without samples writes exact zeros; no atomics: a ray's sums do not depend on other rays.
+ *   D <= 4: a lane per sample, sums in registers; larger D: the power of two >= D (at most 64) lanes per sample.
+ * mh_accumulate_bwd: g_out [N, D] -> d_weights [M] = sum_c g_out[ray, c] values[i, c] (values NULL: g_out[ray, 0]) and
+ *   d_values [M, D] = weights_i g_out[ray, :]; either may be NULL (not both); d_values needs values and weights.
+ * Bad arguments (a NULL required pointer, N < 0, D outside 1 .. 256) return MH_ERR_ARG before any launch; N == 0 returns MH_OK
+ * without one. */
+int mh_pack_info(const void *ray_indices, int32_t idx_is_i64, int64_t M, int32_t N, int32_t *ray_start, int32_t *ray_cnt,
+                 void *stream);
+int mh_ray_weights_fwd(const float *values, const float *t_starts, const float *t_ends, int32_t alpha_form,
+                       const int32_t *ray_start, const int32_t *ray_cnt, int32_t N, float *weights, float *trans, float *alphas,
+                       void *stream);
+int mh_ray_weights_bwd(const float *values, const float *t_starts, const float *t_ends, int32_t alpha_form,
+                       const int32_t *ray_start, const int32_t *ray_cnt, int32_t N, const float *trans, const float *g_weights,
+                       const float *g_trans, const float *g_alphas, float *d_values, void *stream);
+int mh_accumulate_fwd(const float *weights, const float *values, int32_t D, const int32_t *ray_start, const int32_t *ray_cnt,
+                      int32_t N, float *out, void *stream);
+int mh_accumulate_bwd(const float *weights, const float *values, int32_t D, const int32_t *ray_start, const int32_t *ray_cnt,
+                      int32_t N, const float *g_out, float *d_weights, float *d_values, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 SO = os.path.join(OUT_DIR, "libmorpheus_hip.so")
 SOURCES = ["hashgrid.hip", "hashgrid_general.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_b3.hip", "optim.hip", "wnorm.hip", "normal.hip", "graph.hip", "losses.hip",
-           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip"]
+           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip", "volrend.hip"]
 HEADER = os.path.join(HERE, "..", "include", "morpheus_hip.h")      # the C ABI; _lib.py binds the library from this text
 HEADERS = [os.path.join(CSRC, "common.h"), HEADER]
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar fp32 adds / muls of the epilogues into v_pk_* instructions, which

@@ -23,6 +23,12 @@ sites and prints the differences:
   4. visibility pruning -- `sampling(sigma_fn=..., alpha_thre=..., early_stop_eps=...)` with one closed-form density through
      both: the difference of the kept sets (csrc/visibility.hip restates nerfacc's rule from recall).
 
+  5. the volume-rendering functions under their own names -- `morpheus_amd.volrend` against nerfacc function by function on
+     nerfacc's samples: pack_info, render_transmittance / render_weight _from_density / _from_alpha, accumulate_along_rays
+     (values None, 1, 3 and 48 channels), render_visibility_from_density, rendering(), and the gradients to sigmas, alphas and
+     values of one mixed loss.  At alpha == 1 nerfacc's alpha gradient is expected to be inf / NaN and this build's finite
+     (volrend.py): that row is printed and not counted.
+
 It cannot run in the build container (no nerfacc, no GPU); tests/test_host.py only checks that it imports and fails with its own
 message there.
 """
@@ -142,6 +148,77 @@ def main(argv=None) -> int:
               f"{len(kh)} of {ri_h.numel()}; only nerfacc {len(kn - kh)}, only this build {len(kh - kn)}")
         # samples within rounding of a threshold may fall either way (tests/test_gpu_visibility.py caps them at 0.1 %)
         ok &= len(kn ^ kh) <= max(1, ri_n.numel() // 1000)
+    # ---- 5. morpheus_amd.volrend, function by function (signatures, shapes and numbers; recalled, this case pins them)
+    from morpheus_amd import volrend
+
+    def rel(a, b):
+        return float((a.float() - b.float()).abs().max() / b.float().abs().max().clamp(min=1e-30))
+
+    def row(name, a, b, tol=1e-5, count=True):
+        nonlocal ok
+        same_shape = tuple(a.shape) == tuple(b.shape)
+        err = rel(a, b) if same_shape and a.numel() else (0.0 if same_shape else float("inf"))
+        print(f"volrend: {name:44s} shape {tuple(a.shape)} vs nerfacc {tuple(b.shape)}; max |difference| / max |nerfacc| = {err:.3e}")
+        if count:
+            ok &= same_shape and err <= tol
+
+    row("pack_info", volrend.pack_info(ri_n, N), nerfacc.pack_info(ri_n, N), tol=0.0)
+    packed = dict(ray_indices=ri_n, n_rays=N)
+    sg_h, sg_n = sig.clone().requires_grad_(True), sig.clone().requires_grad_(True)
+    rgb_h, rgb_n = rgb.clone().requires_grad_(True), rgb.clone().requires_grad_(True)
+    probe = torch.sin(torch.arange(ri_n.numel(), device=dev) * 0.37)
+    losses = []
+    for mod, sg, cl in ((volrend, sg_h, rgb_h), (nerfacc, sg_n, rgb_n)):
+        w, T, al = mod.render_weight_from_density(ts_n, te_n, sg, **packed)
+        acc = [mod.accumulate_along_rays(w, values=v, **packed) for v in (None, tm[:, None], cl, cl.repeat(1, 16))]
+        losses.append((w, T, al, acc, (w * probe).sum() + (T * probe).sum() + (al * probe).sum() + sum((x * x).sum() for x in acc)))
+    for name, a, b in zip(("render_weight_from_density: weights", "render_weight_from_density: trans", "render_weight_from_density: alphas"),
+                          losses[0][:3], losses[1][:3]):
+        row(name, a.detach(), b.detach())
+    for name, a, b in zip(("accumulate_along_rays(values=None)", "accumulate_along_rays, 1 channel", "accumulate_along_rays, 3 channels",
+                           "accumulate_along_rays, 48 channels"), losses[0][3], losses[1][3]):
+        row(name, a.detach(), b.detach())
+    losses[0][4].backward()
+    losses[1][4].backward()
+    row("d loss / d sigmas", sg_h.grad, sg_n.grad, tol=1e-4)
+    row("d loss / d values", rgb_h.grad, rgb_n.grad, tol=1e-4)
+    T_h, a_h = volrend.render_transmittance_from_density(ts_n, te_n, sig, **packed)
+    T_n, a_n = nerfacc.render_transmittance_from_density(ts_n, te_n, sig, **packed)
+    row("render_transmittance_from_density: trans", T_h, T_n)
+    row("render_transmittance_from_density: alphas", a_h, a_n)
+    alphas = a_n.detach().clamp(max=0.999)
+    al_h, al_n = alphas.clone().requires_grad_(True), alphas.clone().requires_grad_(True)
+    for mod, al in ((volrend, al_h), (nerfacc, al_n)):
+        w, T = mod.render_weight_from_alpha(al, **packed)
+        ((w * probe).sum() + (T * probe).sum()).backward()
+        if mod is volrend:
+            w_a, T_a = w.detach(), T.detach()
+    row("render_weight_from_alpha: weights", w_a, w.detach())
+    row("render_weight_from_alpha: trans", T_a, T.detach())
+    row("render_transmittance_from_alpha", volrend.render_transmittance_from_alpha(alphas, **packed),
+        nerfacc.render_transmittance_from_alpha(alphas, **packed))
+    row("d loss / d alphas (alphas < 1)", al_h.grad, al_n.grad, tol=1e-4)
+    opaque = alphas.clone()
+    opaque[::97] = 1.0
+    op_h, op_n = opaque.clone().requires_grad_(True), opaque.clone().requires_grad_(True)
+    for mod, al in ((volrend, op_h), (nerfacc, op_n)):
+        w, T = mod.render_weight_from_alpha(al, **packed)
+        ((w * probe).sum() + (T * probe).sum()).backward()
+    print(f"volrend: d loss / d alphas with alpha == 1 samples: non-finite elements this build {int((~torch.isfinite(op_h.grad)).sum())}, "
+          f"nerfacc {int((~torch.isfinite(op_n.grad)).sum())} (expected: 0 and > 0; not counted)")
+    vis_h = volrend.render_visibility_from_density(ts_n, te_n, sig, early_stop_eps=1e-4, alpha_thre=1e-2, **packed)
+    vis_n = nerfacc.render_visibility_from_density(ts_n, te_n, sig, early_stop_eps=1e-4, alpha_thre=1e-2, **packed)
+    differ = int((vis_h != vis_n).sum())
+    print(f"volrend: render_visibility_from_density: {differ} of {vis_n.numel()} samples differ")
+    ok &= vis_h.shape == vis_n.shape and differ <= max(1, vis_n.numel() // 1000)
+    fn = lambda t0, t1, idx: (rgb, sig)
+    bkgd = torch.tensor([1.0, 0.5, 0.25], device=dev)
+    out_h = volrend.rendering(ts_n, te_n, ri_n, N, rgb_sigma_fn=fn, render_bkgd=bkgd)
+    out_n = nerfacc.rendering(ts_n, te_n, ri_n, N, rgb_sigma_fn=fn, render_bkgd=bkgd)
+    for name, a, b in zip(("rendering: colors", "rendering: opacities", "rendering: depths"), out_h[:3], out_n[:3]):
+        row(name, a, b)
+    print(f"volrend: rendering: extras keys this build {sorted(out_h[3])}, nerfacc {sorted(out_n[3])}")
+    ok &= set(out_n[3]) <= set(out_h[3])
     print("PINNED: nerfacc and this build agree" if ok else "DIFFERENCES FOUND (see above)")
     return 0 if ok else 1
 
