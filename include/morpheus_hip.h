@@ -1002,6 +1002,53 @@ int mh_accumulate_fwd(const float *weights, const float *values, int32_t D, cons
 int mh_accumulate_bwd(const float *weights, const float *values, int32_t D, const int32_t *ray_start, const int32_t *ray_cnt,
                       int32_t N, const float *g_out, float *d_weights, float *d_values, void *stream);
 
+/* ---- device-resident dataset (csrc/dataset.hip; morpheus_amd/dataset.py is its Python face) -------------------------------
+ * Stands where the reference's datasets/dataset.py:DeformDataset stands.  Frames stay on the device in their file precision:
+ * rgb uint8 [F,H,W,3], depth uint16 (depth_is_f32 = 0) or fp32 (1) [F,H,W], mask uint8 [F,H,W]; poses fp32 [F,4,4] row-major;
+ * theta, phi, radius fp32 [F].  Purely additive: MH_ABI_VERSION is unchanged.
+ * mh_dataset_sample: ONE launch per real-view batch (dataset.py:398-433).  frame_idx int64 [B], pix int32 [N] (NULL: the whole
+ *   frame, pixel n = n, N <= H W).  Ray (b, n) looks through pixel pix[n] of frame frame_idx[b], both CLAMPED into their
+ *   ranges -- no read leaves the tables whatever the arrays hold:
+ *     rays_o, rays_d [B,N,3]   the arithmetic of mh_generate_rays on the frame's device pose, the same bits
+ *     rays_t [B,N]             (float)f / (float)F;      rays_id int64 [B,N] = f
+ *     image [B,3,N]            (float)((double)u8 / 255.0)
+ *     depth_out [B,N]          (float)((double)raw / depth_scale)
+ *     mask_out int64 [B,N]     1 where the byte is 255, else 0 (`/ 255.0`, then the truncation of `.to(int64)`)
+ *     pose_out [B,4,4], theta_out, phi_out, radius_out [B]   the frame's row of each table
+ * mh_generate_rays_dev: rays of B DEVICE poses [B,4,4]: rays_o, rays_d [B,N,3] with the arithmetic of mh_generate_rays; pix
+ *   int32 [N] is shared by the poses and clamped (NULL: the whole image).  With frame_idx int64 [B] (clamped into [0, F)) it
+ *   also writes rays_t [B,N] = (float)f / (float)F and rays_id int64 [B,N] = f; either may be NULL.
+ * mh_dataset_virtual_pose: B virtual views (dataset.py:435-501, 268-330, 559-563) of the frames frame_idx (clamped).  mode:
+ *     0  a, b = theta, phi in radians, fp32 (the theta/phi box; phi < 0 is moved up by 2 pi, as the reference does)
+ *     1  a, b, c = the three normal draws of the uniform-sphere branch
+ *     2  a, b = theta, phi in DEGREES (is_train = False, get_c2w_from_polar); radians = deg / 180 * pi in fp32
+ *   radius = radius[f] * radius_factor in fp32.  The pose rule: the look-at chain (sin / cos or normalize, two
+ *   normalised cross products, safe_normalize with its 1e-20 clamp) is evaluated in DOUBLE from those fp32 inputs and rounded
+ *   to fp32 once -- not the bits of the reference's fp32 chain (torch's CPU sin is another program), judged against float64.
+ *   In mode 1 the fp32 angles restate the reference's fp32 chain: norm = sqrt(fma(z, z, fma(y, y, x * x))), unit = v /
+ *   max(norm, 1e-12), phi = the C library's atan2f (fdlibm) plus 2 pi where negative, theta = the double acos(unit_y) rounded once
+ *   (the reference's CPU acos, a vendor vector routine, is within one fp32 step of it and equal in about 92 % of draws).
+ *   Bit for bit the reference's, given the fp32 angles: dir_out int64 [B], the six-way label of datasets/utils.py:70-91
+ *   (phi % 2 pi and the six thresholds compared at fp32: front_half = front / 2, back_lo = pi - front / 2, left_lo = pi +
+ *   front / 2, wrap_lo = 2 pi - front / 2, overhead, bottom = pi - overhead, each rounded from the caller's float64 value);
+ *   deg_out [B,2] = (theta, phi) / pi * 180; polar_out = theta_deg - theta[f]; azimuth_out = phi_deg - phi[f], minus 360 where
+ *   it exceeds 180; dradius_out = radius - radius[f].  pose_out [B,4,4].
+ * Bad arguments return MH_ERR_ARG before any launch; B == 0 or N == 0 returns MH_OK without one. */
+int mh_dataset_sample(float fx, float fy, float cx, float cy, const float *poses, const uint8_t *rgb, const void *depth,
+                      int32_t depth_is_f32, double depth_scale, const uint8_t *mask, const float *theta, const float *phi,
+                      const float *radius, int32_t F, int32_t H, int32_t W, const int64_t *frame_idx, int32_t B,
+                      const int32_t *pix, int32_t N, float *rays_o, float *rays_d, float *rays_t, int64_t *rays_id, float *image,
+                      float *depth_out, int64_t *mask_out, float *pose_out, float *theta_out, float *phi_out, float *radius_out,
+                      void *stream);
+int mh_generate_rays_dev(float fx, float fy, float cx, float cy, const float *poses, int32_t B, int32_t H, int32_t W,
+                         const int32_t *pix, int32_t N, const int64_t *frame_idx, int32_t F, float *rays_o, float *rays_d,
+                         float *rays_t, int64_t *rays_id, void *stream);
+int mh_dataset_virtual_pose(int32_t mode, const float *a, const float *b, const float *c, const int64_t *frame_idx, int32_t B,
+                            const float *radius, const float *theta, const float *phi, int32_t F, float radius_factor,
+                            float front_half, float back_lo, float left_lo, float wrap_lo, float overhead, float bottom,
+                            float *pose_out, int64_t *dir_out, float *polar_out, float *azimuth_out, float *dradius_out,
+                            float *deg_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,24 +17,7 @@
 // plain operators are used instead.)
 #pragma clang fp contract(off)
 
-struct Pose {
-    float r[9];
-    float t[3];
-};
-
-// one pinhole ray: pixel idx = j*W + i -> camera direction ((i+.5-cx)/fx, -(j+.5-cy)/fy, -1) rotated by R
-__device__ __forceinline__ void pixel_ray(float fx, float fy, float cx, float cy, const Pose &pose, int W, int idx,
-                                          float *o, float *d) {
-    const int j = idx / W, i = idx - j * W;
-    const float d0 = (((float)i + 0.5f) - cx) / fx;
-    const float d1 = -((((float)j + 0.5f) - cy) / fy);
-    const float d2 = -1.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        d[a] = (d0 * pose.r[a * 3 + 0] + d1 * pose.r[a * 3 + 1]) + d2 * pose.r[a * 3 + 2];
-        o[a] = pose.t[a];
-    }
-}
+#include "rays.h"      // Pose, pixel_ray, pose_from_c2w: shared with dataset.hip
 
 __global__ __launch_bounds__(256) void generate_rays_kernel(float fx, float fy, float cx, float cy, Pose pose, int H,
                                                             int W, float *__restrict__ rays_o, float *__restrict__ rays_d) {
@@ -253,15 +236,6 @@ __global__ __launch_bounds__(256) void march_pack_kernel(const int32_t *__restri
         t_starts[base + i] = row_s[i];
         t_ends[base + i] = row_e[i];
     }
-}
-
-static Pose pose_from_c2w(const float *c2w_host) {
-    Pose p;
-    for (int a = 0; a < 3; a++) {
-        for (int b = 0; b < 3; b++) p.r[a * 3 + b] = c2w_host[a * 4 + b];
-        p.t[a] = c2w_host[a * 4 + 3];
-    }
-    return p;
 }
 
 extern "C" int mh_generate_rays(float fx, float fy, float cx, float cy, const float *c2w_host, int32_t H, int32_t W,

@@ -478,6 +478,102 @@ def generate_rays(fx, fy, cx, cy, c2w, H, W, device):
     return o, d
 
 
+def _intrinsics4(K):
+    """fx, fy, cx, cy of a 3x3 intrinsic matrix as Python floats (rounded to fp32 at the C boundary, as torch casts the
+    reference's float64 entries when they meet its fp32 pixel grid)"""
+    return float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+
+
+def _frame_pix(frame_idx, pix, n_views, HW):
+    """checked (frame_idx int64 [B] | None, pix int32 [N] | None, N) of the device-pose ray kernels"""
+    if frame_idx is not None:
+        require_gpu(frame_idx)
+        if frame_idx.dtype != torch.int64 or frame_idx.shape != (n_views,):
+            raise ValueError(f"frame indices must be int64 [{n_views}], got {frame_idx.dtype} {tuple(frame_idx.shape)}")
+        frame_idx = frame_idx.contiguous()
+    if pix is None:
+        return frame_idx, None, HW
+    require_gpu(pix)
+    if pix.dtype != torch.int32 or pix.dim() != 1:
+        raise ValueError(f"pix must be int32 [N], got {pix.dtype} {tuple(pix.shape)}")
+    return frame_idx, pix.contiguous(), pix.shape[0]
+
+
+def generate_rays_dev(K, poses_dev, H: int, W: int, pix=None, frame_idx=None, num_frames: int = 0):
+    """Rays of B camera poses that live on the device (`mh_generate_rays_dev`): fp32 [B,4,4] -> rays_o, rays_d [B,N,3] with the
+    arithmetic of `generate_rays`, bit for bit.  `pix`: int32 [N] pixel indices (j*W+i) on the device, shared by the poses and
+    clamped into the image; None = all H*W pixels.  With `frame_idx` (int64 [B] on the device, clamped into [0, num_frames))
+    -> rays_o, rays_d, rays_t [B,N,1] = f / num_frames, rays_id int64 [B,N,1]."""
+    require_gpu(poses_dev)
+    if poses_dev.dtype != torch.float32 or poses_dev.dim() != 3 or poses_dev.shape[1:] != (4, 4):
+        raise ValueError(f"poses must be float32 [B,4,4], got {poses_dev.dtype} {tuple(poses_dev.shape)}")
+    poses_dev, dev, B = poses_dev.contiguous(), poses_dev.device, poses_dev.shape[0]
+    frame_idx, pix, N = _frame_pix(frame_idx, pix, B, H * W)
+    o, d = torch.empty(B, N, 3, device=dev), torch.empty(B, N, 3, device=dev)
+    t = i = None
+    if frame_idx is not None:
+        t, i = torch.empty(B, N, 1, device=dev), torch.empty(B, N, 1, dtype=torch.int64, device=dev)
+    _timed("mh_generate_rays_dev", *_intrinsics4(K), ptr(poses_dev), B, H, W, ptr(pix), N, ptr(frame_idx), int(num_frames),
+           ptr(o), ptr(d), ptr(t), ptr(i))
+    return (o, d) if frame_idx is None else (o, d, t, i)
+
+
+def dataset_sample(K, poses, rgb, depth, mask, theta, phi, radius, depth_scale: float, frame_idx, pix=None):
+    """One real-view batch in one launch (`mh_dataset_sample`, datasets/dataset.py:398-433) from device-resident frames: rgb uint8
+    [F,H,W,3], depth uint16 / float32 [F,H,W], mask uint8 [F,H,W], poses fp32 [F,4,4], theta / phi / radius fp32 [F].
+    frame_idx int64 [B], pix int32 [N] | None (the whole frame); both on the device, clamped by the kernel.
+    -> dict(rays_o, rays_d [B,N,3], rays_t [B,N,1], rays_id int64 [B,N,1], image [B,3,N], depth [B,N], mask int64 [B,N],
+            pose [B,4,4], theta, phi, radius [B])"""
+    require_gpu(poses, rgb, depth, mask, theta, phi, radius, frame_idx)
+    F, H, W = rgb.shape[:3]
+    if rgb.dtype != torch.uint8 or rgb.shape != (F, H, W, 3) or mask.dtype != torch.uint8 or mask.shape != (F, H, W):
+        raise ValueError("rgb must be uint8 [F,H,W,3] and mask uint8 [F,H,W]")
+    if depth.dtype not in (torch.uint16, torch.float32) or depth.shape != (F, H, W):
+        raise ValueError("depth must be uint16 or float32 [F,H,W]")
+    if poses.dtype != torch.float32 or poses.shape != (F, 4, 4):
+        raise ValueError("poses must be float32 [F,4,4]")
+    for v in (theta, phi, radius):
+        if v.dtype != torch.float32 or v.shape != (F,):
+            raise ValueError("theta, phi and radius must be float32 [F]")
+    dev, B = rgb.device, frame_idx.shape[0]
+    frame_idx, pix, N = _frame_pix(frame_idx, pix, B, H * W)
+    f32 = dict(device=dev, dtype=torch.float32)
+    out = dict(rays_o=torch.empty(B, N, 3, **f32), rays_d=torch.empty(B, N, 3, **f32), rays_t=torch.empty(B, N, 1, **f32),
+               rays_id=torch.empty(B, N, 1, dtype=torch.int64, device=dev), image=torch.empty(B, 3, N, **f32),
+               depth=torch.empty(B, N, **f32), mask=torch.empty(B, N, dtype=torch.int64, device=dev),
+               pose=torch.empty(B, 4, 4, **f32), theta=torch.empty(B, **f32), phi=torch.empty(B, **f32),
+               radius=torch.empty(B, **f32))
+    _timed("mh_dataset_sample", *_intrinsics4(K), ptr(poses), ptr(rgb), ptr(depth), int(depth.dtype == torch.float32),
+           float(depth_scale), ptr(mask), ptr(theta), ptr(phi), ptr(radius), F, H, W, ptr(frame_idx), B, ptr(pix), N,
+           *(ptr(out[k]) for k in ("rays_o", "rays_d", "rays_t", "rays_id", "image", "depth", "mask", "pose", "theta", "phi",
+                                   "radius")))
+    return out
+
+
+VIRTUAL_ANGLES, VIRTUAL_SPHERE, VIRTUAL_POLAR = 0, 1, 2
+
+
+def dataset_virtual_pose(mode: int, a, b, c, frame_idx, radius, theta, phi, radius_factor: float, bounds):
+    """Look-at poses, view labels and deltas of B virtual views in one launch (`mh_dataset_virtual_pose`).  mode / a, b, c: see
+    include/morpheus_hip.h; `bounds`: the six label thresholds (front/2, pi - front/2, pi + front/2, 2 pi - front/2, overhead,
+    pi - overhead) as float64 Python numbers.  -> dict(pose [B,4,4], dir int64 [B], polar, azimuth, radius [B], deg [B,2])"""
+    require_gpu(a, b, c, frame_idx, radius, theta, phi)
+    B, dev, F = a.shape[0], a.device, radius.shape[0]
+    for v in (a, b) + ((c,) if c is not None else ()):
+        if v.dtype != torch.float32 or v.shape != (B,):
+            raise ValueError(f"draws must be float32 [{B}], got {v.dtype} {tuple(v.shape)}")
+    if mode == VIRTUAL_SPHERE and c is None:
+        raise ValueError("the sphere branch takes three normal draws")
+    frame_idx, _, _ = _frame_pix(frame_idx, None, B, 0)
+    a, b, c = a.contiguous(), b.contiguous(), None if c is None else c.contiguous()
+    f32 = dict(device=dev, dtype=torch.float32)
+    out = dict(pose=torch.empty(B, 4, 4, **f32), dir=torch.empty(B, dtype=torch.int64, device=dev), polar=torch.empty(B, **f32),
+               azimuth=torch.empty(B, **f32), radius=torch.empty(B, **f32), deg=torch.empty(B, 2, **f32))
+    _timed("mh_dataset_virtual_pose", int(mode), ptr(a), ptr(b), ptr(c), ptr(frame_idx), B, ptr(radius), ptr(theta), ptr(phi), F, float(radius_factor), *(float(x) for x in bounds),
+           *(ptr(out[k]) for k in ("pose", "dir", "polar", "azimuth", "radius", "deg")))
+    return out
+
+
 def sample_uniform(rays_o, rays_d, jitter, S: int, bound: float, with_xyz: bool = False):
     """-> ray_idx int32 [N*S], t_starts, t_ends, xyz|None, ray_start, ray_cnt (no_grad, like morpheus.py:628)."""
     require_gpu(rays_o, rays_d, jitter)
