@@ -1049,6 +1049,36 @@ int mh_dataset_virtual_pose(int32_t mode, const float *a, const float *b, const 
                             float *pose_out, int64_t *dir_out, float *polar_out, float *azimuth_out, float *dradius_out,
                             float *deg_out, void *stream);
 
+/* ---- preprocessing of a raw RGB-D sequence (csrc/preprocess.hip; morpheus_amd/preprocess.py is its Python face) -----------
+ * Stands where the reference's preprocess/preprocess.py:DataProcessor.rotate_and_crop_frames and its four imwrite lines stand.
+ * Purely additive: MH_ABI_VERSION is unchanged (the precedents are mh_subdiv_*, volrend and dataset).
+ * mh_prep_frames: ALL frames of a sequence in one launch.  In: rgb uint8 [F,H,W,3], depth uint16 [F,H,W] (raw), mask uint8
+ *   [F,H,W]; origin int32 [F,2] = (top, left) of each frame's window; inv_affine float64 [F,6], the inverse affine map of each
+ *   frame, formed on the host; rotated uint8 [F], 0 = the frame is not rotated (inv_affine of that frame is not read);
+ *   table_inside, table_padded uint16 [65536].  Out, DeviceDataset's storage layout: rgb_out uint8 [F,h,w,3], depth_out uint16
+ *   [F,h,w], mask_out uint8 [F,h,w], padding_out uint8 [F,h,w].
+ *   Window: output pixel (y, x) of frame f looks at canvas pixel (Y, X) = (top + y, left + x) (64-bit sums).  Outside [0,H) x
+ *   [0,W): rgb, depth and mask 0, padding 255; inside: padding 0.  This holds for EVERY position of the window.  The reference
+ *   raises a numpy shape error for a window that crosses two different sides of the frame, one wholly outside the frame and one
+ *   larger than the frame; this build defines those three kinds by the same rule.
+ *   Depth: depth_out = table_inside[raw] when the frame's window passes the reference's inside test, top >= 0 && left >= 0 &&
+ *   top + h < H && left + w < W (strict: touching the bottom or right edge is not inside), else table_padded[raw].  The caller
+ *   tabulates the reference's two write expressions (fp32 and float64 products; morpheus_amd.preprocess.depth_tables).
+ *   Unrotated frames: rgb and mask bytes are copied.
+ *   Rotated frames: this build's own definition, agreement with cv2 unverified (cv2.warpAffine's fixed-point coordinates are not
+ *   restated).  With a = inv_affine[f], canvas (X, Y) samples the source at u = (a0 X + a1 Y) + a2, v = (a3 X + a4 Y) + a5 in
+ *   float64 without contraction.  depth, mask: nearest, column floor(u + 0.5), row floor(v + 0.5), 0 outside the image (raw 0 ->
+ *   table[0]).  rgb: bilinear on byte / 255.0 in float64, taps outside the image 0, fu = floor(u), ax = u - fu (v alike),
+ *   val = ((p00 (1-ax)(1-ay) + p01 ax (1-ay)) + p10 (1-ax) ay) + p11 ax ay, byte = (uint8)(val * 255.0), a truncation.
+ *   tests/preprocess_oracle.py states the same order; equal bit for bit.
+ *   One lane writes 4 consecutive pixels of the flat output as whole dwords: the four outputs must be 4-byte aligned (depth_out
+ *   8), F h w < 2^31, H W < 2^31.  Every read is inside the frames and the tables whatever origin and inv_affine hold.
+ * Bad sizes, null pointers or misaligned outputs return MH_ERR_ARG before any launch; F == 0 returns MH_OK without one. */
+int mh_prep_frames(const uint8_t *rgb, const uint16_t *depth, const uint8_t *mask, int32_t F, int32_t H, int32_t W,
+                   const int32_t *origin, const double *inv_affine, const uint8_t *rotated, const uint16_t *table_inside,
+                   const uint16_t *table_padded, int32_t h, int32_t w, uint8_t *rgb_out, uint16_t *depth_out, uint8_t *mask_out,
+                   uint8_t *padding_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

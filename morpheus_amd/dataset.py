@@ -8,7 +8,8 @@ for pose, label and deltas, `ops.generate_rays_dev` for the rays), and the pose 
 on the device a call makes no device-to-host transfer.
 
 What is the reference's bit for bit and what is judged in float64 instead: the header comment of csrc/dataset.hip.
-The image decode stays on the host and happens once (`from_dir`, PIL and numpy).  Resized known views
+The image decode stays on the host and happens once (`from_dir`, PIL and numpy; `from_raw` reads a RAW sequence and cuts its frames
+on the device through morpheus_amd.preprocess, with no files in between).  Resized known views
 (`data.known_view_scale != 1.0`) are not implemented.  Sampling needs the frames on an MI355X: there is no CPU path.
 """
 from __future__ import annotations
@@ -155,6 +156,19 @@ class DeviceDataset:
         rtp = np.loadtxt(os.path.join(root, "r_theta_phi.txt")).reshape(-1, 3)
         poses = np.stack([np.loadtxt(p) for p in sorted(glob(os.path.join(root, "poses_virt", "*.txt")))])
         return cls(config, rgb, depth, mask, poses, K, rtp[:, 0], rtp[:, 1], rtp[:, 2], device=device, is_train=is_train)
+
+    @classmethod
+    def from_raw(cls, config, device="cuda", pre=None, is_train: bool = True):
+        """From a RAW sequence under data.data_dir (rgb/, depth/, mask/ and data.render_cameras_name): `preprocess.preprocess_dir`
+        forms the virtual cameras and cuts the frames on the device, and the device tensors go to the constructor as they are --
+        no files in between, no host round trip.  The preprocessing keys (size_h, size_w, rot_degree, depth_scale) are read from
+        config["data"]; `pre` overrides them, for a training YAML that lacks them or whose depth_scale describes the CUT frames
+        (the reference writes those with its constant 1000) rather than the raw ones.  The dataset itself keeps `config`."""
+        from . import preprocess
+        r = preprocess.preprocess_dir({**config, "data": {**config["data"], **(pre or {})}}, device)
+        ds = cls(config, r.rgb, r.depth, r.mask, r.poses_virt, r.K_virt, r.radius, r.theta, r.phi, device=device, is_train=is_train)
+        ds.preprocessed = r
+        return ds
 
     # ------------------------------------------------------------------------------- the reference's host-side attributes
     def _host_view(self, name, make):

@@ -574,6 +574,40 @@ def dataset_virtual_pose(mode: int, a, b, c, frame_idx, radius, theta, phi, radi
     return out
 
 
+def prep_frames(rgb, depth, mask, origin, inv_affine, rotated, table_inside, table_padded, size_h: int, size_w: int):
+    """Rotate, cut and mark the padding of every frame of a raw sequence in one launch (`mh_prep_frames`, the reference's
+    preprocess/preprocess.py:rotate_and_crop_frames and its write expressions): rgb uint8 [F,H,W,3], depth uint16 [F,H,W], mask
+    uint8 [F,H,W]; origin int32 [F,2] (top, left); inv_affine float64 [F,6]; rotated uint8 [F]; the two depth tables uint16
+    [65536]; all on the device.  -> dict(rgb uint8 [F,h,w,3], depth uint16 [F,h,w], mask uint8 [F,h,w], padding uint8 [F,h,w])"""
+    require_gpu(rgb, depth, mask, origin, inv_affine, rotated, table_inside, table_padded)
+    F, H, W = rgb.shape[:3]
+    if rgb.dtype != torch.uint8 or rgb.shape != (F, H, W, 3) or mask.dtype != torch.uint8 or mask.shape != (F, H, W):
+        raise ValueError("rgb must be uint8 [F,H,W,3] and mask uint8 [F,H,W]")
+    if depth.dtype != torch.uint16 or depth.shape != (F, H, W):
+        raise ValueError("depth must be uint16 [F,H,W]")
+    if origin.dtype != torch.int32 or origin.shape != (F, 2):
+        raise ValueError(f"origin must be int32 [{F},2], got {origin.dtype} {tuple(origin.shape)}")
+    if inv_affine.dtype != torch.float64 or inv_affine.shape != (F, 6):
+        raise ValueError(f"inv_affine must be float64 [{F},6], got {inv_affine.dtype} {tuple(inv_affine.shape)}")
+    if rotated.dtype != torch.uint8 or rotated.shape != (F,):
+        raise ValueError(f"rotated must be uint8 [{F}], got {rotated.dtype} {tuple(rotated.shape)}")
+    for t in (table_inside, table_padded):
+        if t.dtype != torch.uint16 or t.shape != (65536,):
+            raise ValueError("the depth tables must be uint16 [65536]")
+    h, w = int(size_h), int(size_w)
+    if h <= 0 or w <= 0 or F * h * w >= 2 ** 31 or H * W >= 2 ** 31:
+        raise ValueError(f"window {h} x {w} of {F} frames {H} x {W}: sizes must be positive, F h w and H W below 2^31")
+    dev = rgb.device
+    u8 = dict(device=dev, dtype=torch.uint8)
+    out = dict(rgb=torch.empty(F, h, w, 3, **u8), depth=torch.empty(F, h, w, device=dev, dtype=torch.uint16),
+               mask=torch.empty(F, h, w, **u8), padding=torch.empty(F, h, w, **u8))
+    rgb, depth, mask, origin, inv_affine, rotated, table_inside, table_padded = (
+        t.contiguous() for t in (rgb, depth, mask, origin, inv_affine, rotated, table_inside, table_padded))
+    _timed("mh_prep_frames", ptr(rgb), ptr(depth), ptr(mask), F, H, W, ptr(origin), ptr(inv_affine), ptr(rotated),
+           ptr(table_inside), ptr(table_padded), h, w, *(ptr(out[k]) for k in ("rgb", "depth", "mask", "padding")))
+    return out
+
+
 def sample_uniform(rays_o, rays_d, jitter, S: int, bound: float, with_xyz: bool = False):
     """-> ray_idx int32 [N*S], t_starts, t_ends, xyz|None, ray_start, ray_cnt (no_grad, like morpheus.py:628)."""
     require_gpu(rays_o, rays_d, jitter)
