@@ -1079,6 +1079,62 @@ int mh_prep_frames(const uint8_t *rgb, const uint16_t *depth, const uint8_t *mas
                    const uint16_t *table_padded, int32_t h, int32_t w, uint8_t *rgb_out, uint16_t *depth_out, uint8_t *mask_out,
                    uint8_t *padding_out, void *stream);
 
+/* ---- occupancy estimator in full (csrc/estimator.hip; morpheus_amd/estimator.py:OccGridEstimator is its Python face) -------
+ * Stands where nerfacc 0.5.x's OccGridEstimator stands for a render loop written against it: names, buffers and the update rule
+ * are RECALLED from its public source, agreement unverified; the interval placement is this build's definition.
+ * Purely additive: MH_ABI_VERSION is unchanged.  tests/estimator_oracle.py restates every rule below in fp32, one rounding per
+ * operation; the kernels are compiled without contraction and equal it bit for bit.
+ * Grid: L levels (1 .. 16) of Rx x Ry x Rz cells, L Rx Ry Rz < 2^31; aabbs fp32 [L,6] (lo xyz, hi xyz) on the DEVICE, level L - 1
+ * the coarsest; binary uint8 [L,Rx,Ry,Rz]; occs fp32 [L * cells], cells = Rx Ry Rz, cell index (i Ry + j) Rz + k.
+ *
+ * mh_est_march_slots: mh_march_slots (same slot rows, counts and overflow flag; mh_march_pack packs them) with
+ *   - the clip against the coarsest level's box, (lo - o) / d and (hi - o) / d per axis, and the MISS rule decided on it alone;
+ *   - then t_near = near_plane if near_plane > t_near, then t_min[r] alike; t_far = far_plane if far_plane < t_far, then
+ *     t_max[r] alike (t_min / t_max fp32 [N] or NULL; a NaN never passes a comparison and is ignored);
+ *   - t0 = t_near + u * step; cone_angle == 0: ts_k = t0 + k * step, te_k = min(ts_k + step, t_far); cone_angle > 0:
+ *     ts_0 = t0, dt_k = min(max(ts_k * cone_angle, step), 1e10f), te_k = min(ts_k + dt_k, t_far), ts_{k+1} = ts_k + dt_k;
+ *     kept while ts_k < t_far;
+ *   - a step is a sample iff the cell of its midpoint is occupied in the finest level whose box holds the midpoint (lo <= x <
+ *     hi on the three axes; none: the coarsest); cell = clamp(floor((x - lo) / (hi - lo) * R), 0, R - 1).
+ *   mh_est_march_cap, given the diagonal of the coarsest box, = (int)(min(diagonal, far_plane - near_plane) / step) + 4,
+ *   0 for bad arguments: the slot row a ray of unit-or-longer direction cannot overflow (every step is >= `step` long).
+ * The update, no device->host read:
+ *   mh_est_occ_count / mh_est_occ_pack: one wavefront per chunk of mh_est_occ_chunk cells; chunk_cnt int32 [L, n_chunks],
+ *     n_chunks = ceil(cells / chunk).  The caller scans each level's row into chunk_start (exclusive); pack writes the occupied
+ *     cells of level l, in index order, to occ_list [l * cells ...).
+ *   mh_est_select: ids int32 [L,n] and points fp32 [L,n,3] in one launch.  warmup != 0: n = cells, entry i is cell i.  Else
+ *     n = 2 k, k = cells / 4: entry i < k is uniform[l,i] (int32 [L,k]); entry k + j, with c = occ_cnt[l]: c > k -> the
+ *     min((int)(u_occ[l,j] * (float)c), c - 1)-th occupied cell, else the j-th while j < c and padding (-1) behind.
+ *     point = lo + ((ijk + u_point[l,i,:]) / R) * (hi - lo); padding gets cell 0's point.
+ *   mh_est_ema: occs[cell] = max over the entries naming it of max(old * decay, occ > 0 ? occ : 0) -- a reset pass, then an
+ *     integer atomic max; padding and cells with old < 0 (invisible) are skipped.  old_occs: the caller's copy of occs.
+ *   mh_est_threshold: *thre = mean < cap ? mean : cap, mean = the float64 sum of occs[occs >= 0] over their count, summed in a
+ *     fixed order and rounded to fp32 once (no such cell: cap); binaries (may be NULL) = occs > *thre.  partials: float64
+ *     [2 * mh_est_max_partials] scratch.
+ * mh_est_mark_invisible: K fp32 [C,3,3], c2w fp32 [C,3,4] (OpenCV convention).  Cell point x = lo + ijk / (R - 1) * (hi - lo);
+ *   x_c = R^T x - R^T t; uvd = K x_c (sums of three products are (p0 + p1) + p2); in the image iff d >= 0, 0 <= u / d < width,
+ *   0 <= v / d < height.  occs = 0 where some camera has the cell in the image with d >= near_plane and none has it in the image
+ *   with d < near_plane, -1 elsewhere.
+ * Bad arguments return MH_ERR_ARG before any launch. */
+int32_t mh_est_occ_chunk(void);
+int32_t mh_est_max_partials(void);
+int32_t mh_est_march_cap(float step, float diagonal, float near_plane, float far_plane);
+int mh_est_march_slots(const float *rays_o, const float *rays_d, const float *jitter, const float *t_min, const float *t_max,
+                       int32_t N, float step, float cone_angle, float near_plane, float far_plane, const float *aabbs,
+                       int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, const uint8_t *binary, int32_t cap, int32_t *ray_cnt,
+                       float *slot_ts, float *slot_te, int32_t *overflow, void *stream);
+int mh_est_occ_count(const uint8_t *binary, int32_t L, int64_t cells, int32_t *chunk_cnt, void *stream);
+int mh_est_occ_pack(const uint8_t *binary, int32_t L, int64_t cells, const int32_t *chunk_start, int32_t *occ_list,
+                    void *stream);
+int mh_est_select(int32_t warmup, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, int64_t n, const int32_t *uniform,
+                  const float *u_occ, const float *u_point, const int32_t *occ_list, const int32_t *occ_cnt,
+                  const float *aabbs, int32_t *ids, float *points, void *stream);
+int mh_est_ema(const int32_t *ids, const float *occ, int32_t L, int64_t n, int64_t cells, const float *old_occs, float decay,
+               float *occs, void *stream);
+int mh_est_threshold(const float *occs, int64_t n, float cap, double *partials, float *thre, uint8_t *binaries, void *stream);
+int mh_est_mark_invisible(const float *K, const float *c2w, int32_t C, float width, float height, float near_plane,
+                          const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, float *occs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -749,6 +749,159 @@ def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary:
     return ri, ts, te, start, cnt_c, n_valid, overflow
 
 
+# ------------------------------------------------------------------------------------ occupancy estimator (csrc/estimator.hip)
+def _est_grid(aabbs, binary):
+    """(L, Rx, Ry, Rz) of a level grid: aabbs fp32 [L,6] and binary uint8 [L,Rx,Ry,Rz], both contiguous on the device"""
+    require_gpu(aabbs, binary)
+    if binary.dtype != torch.uint8 or binary.dim() != 4 or not binary.is_contiguous():
+        raise ValueError(f"estimator grid: binary uint8 [L,Rx,Ry,Rz] contiguous expected, got {binary.dtype} {tuple(binary.shape)}")
+    L = binary.shape[0]
+    if aabbs.dtype != torch.float32 or tuple(aabbs.shape) != (L, 6) or not aabbs.is_contiguous():
+        raise ValueError(f"estimator grid: aabbs float32 [{L},6] contiguous expected, got {aabbs.dtype} {tuple(aabbs.shape)}")
+    return (L,) + tuple(int(r) for r in binary.shape[1:])
+
+
+def est_march_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal: float, cone_angle: float = 0.0,
+                   near_plane: float = 0.0, far_plane: float = 1e10, t_min=None, t_max=None, capacity: Optional[int] = None):
+    """The estimator's marcher (mh_est_march_slots + mh_march_pack; the definition is in include/morpheus_hip.h).
+    capacity None: march_rays' ragged result (ray_idx, t_starts, t_ends, ray_start, ray_cnt), one host read of M and the
+    doubling retry of an overflowing slot row.  With a capacity: march_rays_capped's seven results, no host read.
+    diagonal: of the coarsest box, a HOST number (the caller keeps it from construction)."""
+    require_gpu(rays_o, rays_d, jitter, t_min, t_max)
+    lib = _lib.load()
+    L, Rx, Ry, Rz = _est_grid(aabbs, binary)
+    o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
+    N, dev = o.shape[0], o.device
+    j = _ray_jitter(jitter, N)
+    tmn, tmx = _ray_jitter(t_min, N), _ray_jitter(t_max, N)
+    step, cone, near, far = float(step), float(cone_angle), float(near_plane), float(far_plane)
+    cap = int(lib.mh_est_march_cap(step, float(diagonal), near, far))
+    if cap <= 0:
+        raise ValueError(f"est_march_rays: step {step}, diagonal {diagonal}, planes [{near}, {far}] give no slot row")
+
+    def slots(cap):
+        cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)     # [ray_cnt | overflow flag]
+        rows = torch.empty(2, N, cap, device=dev)
+        _timed("mh_est_march_slots", ptr(o), ptr(d), ptr(j), ptr(tmn), ptr(tmx), N, step, cone, near, far, ptr(aabbs), L, Rx, Ry, Rz,
+               ptr(binary), cap, ptr(cnt_ovf), ptr(rows[0]), ptr(rows[1]), cnt_ovf.data_ptr() + 4 * N)
+        return cnt_ovf, rows
+
+    if capacity is not None:
+        assert N > 0 and capacity > 0
+        cnt_ovf, rows = slots(cap)
+        cnt = cnt_ovf[:N]
+        csum = torch.cumsum(cnt, 0, dtype=torch.int32)
+        start = (csum - cnt).clamp_(max=capacity)
+        total = csum[N - 1]
+        cnt_c = torch.minimum(cnt, capacity - start)
+        n_valid = total.clamp(max=capacity)
+        overflow = ((total > capacity) | (cnt_ovf[N] != 0)).to(torch.int32)
+        ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        ts, te = torch.zeros(capacity, device=dev), torch.zeros(capacity, device=dev)
+        _timed("mh_march_pack", ptr(start), ptr(cnt_c), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
+        return ri, ts, te, start, cnt_c, n_valid, overflow
+    if N == 0:
+        e = torch.empty(0, device=dev)
+        z = torch.empty(0, dtype=torch.int32, device=dev)
+        return z, e, e.clone(), z.clone(), z.clone()
+    while True:
+        cnt_ovf, rows = slots(cap)
+        cnt = cnt_ovf[:N]
+        csum = torch.cumsum(cnt_ovf, 0, dtype=torch.int32)              # last element = M + overflow flag
+        start = (csum[:N] - cnt).contiguous()
+        M, tot = csum[N - 1:].tolist()                                  # the one device->host sync
+        if tot == M:
+            break
+        if cap > (1 << 20):
+            raise _lib.MorpheusHipError("est_march_rays: a ray takes more than 2^20 steps (step size / direction scale?)")
+        cap *= 2
+    ri = torch.empty(M, dtype=torch.int32, device=dev)
+    ts, te = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    if M > 0:
+        _timed("mh_march_pack", ptr(start), ptr(cnt), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
+    return ri, ts, te, start, cnt.contiguous()
+
+
+def est_occupied_list(binary):
+    """-> (occ_list int32 [L, cells]: each level's occupied cells in index order, the rest of a row unspecified; occ_cnt int32
+    [L]) -- count, a cumsum of the chunk counts on the device, pack.  No host read."""
+    require_gpu(binary)
+    lib = _lib.load()
+    assert binary.dtype == torch.uint8 and binary.dim() == 4 and binary.is_contiguous()
+    L, dev = binary.shape[0], binary.device
+    cells = int(binary[0].numel())
+    n_chunks = -(-cells // int(lib.mh_est_occ_chunk()))
+    chunk_cnt = torch.zeros(L, n_chunks, dtype=torch.int32, device=dev)
+    _timed("mh_est_occ_count", ptr(binary), L, cells, ptr(chunk_cnt))
+    csum = torch.cumsum(chunk_cnt, 1, dtype=torch.int32)
+    start = (csum - chunk_cnt).contiguous()
+    occ_list = torch.empty(L, cells, dtype=torch.int32, device=dev)
+    _timed("mh_est_occ_pack", ptr(binary), L, cells, ptr(start), ptr(occ_list))
+    return occ_list, csum[:, -1].contiguous()
+
+
+def est_select(aabbs, binary, warmup: bool, u_point, uniform=None, u_occ=None, occ_list=None, occ_cnt=None):
+    """The cells of one update and the point to evaluate in each (mh_est_select, one launch) -> ids int32 [L,n] (-1: padding),
+    points fp32 [L,n,3]; n = cells in warm-up, else 2 (cells // 4)."""
+    L, Rx, Ry, Rz = _est_grid(aabbs, binary)
+    cells = Rx * Ry * Rz
+    k = cells // 4
+    n = cells if warmup else 2 * k
+    dev = binary.device
+    require_gpu(u_point, uniform, u_occ, occ_list, occ_cnt)
+
+    def want(t, shape, dtype, what):
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype:
+            raise ValueError(f"est_select: {what} {dtype} {list(shape)} expected, got "
+                             f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        return t.contiguous()
+
+    u_point = want(u_point, (L, n, 3), torch.float32, "u_point")
+    if not warmup:
+        uniform, u_occ = want(uniform, (L, k), torch.int32, "uniform"), want(u_occ, (L, k), torch.float32, "u_occ")
+        occ_list, occ_cnt = want(occ_list, (L, cells), torch.int32, "occ_list"), want(occ_cnt, (L,), torch.int32, "occ_cnt")
+    ids = torch.empty(L, n, dtype=torch.int32, device=dev)
+    pts = torch.empty(L, n, 3, device=dev)
+    if n > 0:
+        _timed("mh_est_select", 1 if warmup else 0, L, Rx, Ry, Rz, n, ptr(uniform), ptr(u_occ), ptr(u_point), ptr(occ_list),
+               ptr(occ_cnt), ptr(aabbs), ptr(ids), ptr(pts))
+    return ids, pts
+
+
+def est_ema(ids, occ, occs, decay: float):
+    """EMA-max of `occs` [L * cells] in place from the evaluations occ [L,n] of the cells ids [L,n] (mh_est_ema)."""
+    require_gpu(ids, occ, occs)
+    L, n = ids.shape
+    occ = occ.detach().reshape(-1).float().contiguous()
+    if occ.shape[0] != L * n or ids.dtype != torch.int32 or occs.dtype != torch.float32 or occs.numel() % L:
+        raise ValueError(f"est_ema: one evaluation per selected cell ({L * n}) expected, got {tuple(occ.shape)}")
+    if n > 0:
+        _timed("mh_est_ema", ptr(ids.contiguous()), ptr(occ), L, n, occs.numel() // L, ptr(occs.clone()), float(decay), ptr(occs))
+
+
+def est_threshold(occs, cap: float, thre=None, binaries=None):
+    """thre (fp32 0-dim, device; made when None) = min(mean(occs[occs >= 0]), cap); binaries (uint8 view, optional) = occs > thre."""
+    require_gpu(occs, thre, binaries)
+    lib = _lib.load()
+    if thre is None:
+        thre = torch.empty((), device=occs.device)
+    part = torch.empty(2 * int(lib.mh_est_max_partials()), dtype=torch.float64, device=occs.device)
+    _timed("mh_est_threshold", ptr(occs), occs.numel(), float(cap), ptr(part), ptr(thre), ptr(binaries))
+    return thre
+
+
+def est_mark_invisible(K, c2w, width: int, height: int, near_plane: float, aabbs, binary, occs):
+    """occs [L * cells] <- 0 where visible, -1 elsewhere (mh_est_mark_invisible); K [C,3,3], c2w [C,3,4], fp32 on the device."""
+    L, Rx, Ry, Rz = _est_grid(aabbs, binary)
+    require_gpu(K, c2w, occs)
+    K, c2w = K.detach().float().contiguous(), c2w.detach().float().contiguous()
+    C = c2w.shape[0]
+    if tuple(K.shape) != (C, 3, 3) or tuple(c2w.shape) != (C, 3, 4) or occs.numel() != L * Rx * Ry * Rz:
+        raise ValueError(f"est_mark_invisible: K [{C},3,3] and c2w [{C},3,4] expected, got {tuple(K.shape)}, {tuple(c2w.shape)}")
+    _timed("mh_est_mark_invisible", ptr(K), ptr(c2w), C, float(width), float(height), float(near_plane), ptr(aabbs), L, Rx, Ry, Rz,
+           ptr(occs))
+
+
 # ------------------------------------------------------------------------------------ visibility pruning (csrc/visibility.hip)
 def visibility_mask(values, t_starts, t_ends, ray_start, ray_cnt, early_stop_eps: float = 0.0, alpha_thre=None,
                     alpha_form: bool = False, padded: bool = False):

@@ -5,7 +5,8 @@
 lets a render loop written against nerfacc 0.5.x -- the reference's own `render_rays` (morpheus.py:675-685, :775), or a fork of
 it with one more accumulated channel, another background rule or an alpha-based field -- run on an MI355X with nothing from
 nerfacc installed.  `HotPathRenderer` does not go through here: it keeps the fused compositor (ops.composite), which does the
-reference's four calls in one launch.
+reference's four calls in one launch.  `OccGridEstimator` (morpheus_amd/estimator.py), the other half of such a loop, is exported
+here too, so that `nerfacc.OccGridEstimator` resolves.
 
 nerfacc is third-party, un-vendored and does not build on ROCm, so it is not on the machine this module was written on.  Names,
 argument names, argument order, defaults and result shapes below are nerfacc 0.5.x's AS RECALLED from its public documentation;
@@ -50,11 +51,12 @@ from torch import Tensor
 
 from . import ops
 from ._lib import MorpheusHipError, ptr, require_gpu
+from .estimator import OccGridEstimator      # the other half of a nerfacc render loop: `nerfacc.OccGridEstimator` resolves
 from .ops import _timed
 
 __all__ = ["pack_info", "render_transmittance_from_density", "render_transmittance_from_alpha", "render_weight_from_density",
            "render_weight_from_alpha", "accumulate_along_rays", "render_visibility_from_density", "render_visibility_from_alpha",
-           "rendering", "MorpheusHipError"]
+           "rendering", "MorpheusHipError", "OccGridEstimator"]
 
 MAX_CHANNELS = 256
 
