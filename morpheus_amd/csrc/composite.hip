@@ -9,43 +9,7 @@
 // accumulators are reduced across the wave once at the end -- no cross-ray running sum is ever
 // formed (a global cumsum loses ~1e-4 here), no atomics, no index_add.
 #include "common.h"
-
-__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        float n = __shfl_up(v, o);
-        if (lane >= o) v += n;
-    }
-    return v;
-}
-
-// Exclusive prefix from the inclusive one.  `incl - v` returns the prefix with an absolute error of ulp(incl) / 2, which the weight
-// takes as a relative error.  While the sample's own v = sigma*dt is below 1 that is at most 2^-24 x the transmittance-weighted
-// share of the sample (a prefix large enough to raise ulp(incl) has already taken the weight away), and the subtraction stays, so
-// that results for ordinary densities are bit for bit what they were.  For an opaque sample -- the first one of a ray carries most
-// of the ray's weight -- incl is rounded at ulp(v): 4e-6 of the weight at v = 100, 5e-4 at 1e4, and inf - inf = NaN at
-// sigma = +inf, where the definition gives w = T for the sample and 0 behind it.  There the exclusive value is the inclusive value
-// of the lane below, 0 at lane 0, which never contains the sample's own term.
-constexpr float COMPOSITE_OPAQUE_SD = 1.0f;
-__device__ __forceinline__ float wave_excl_from_incl(float incl, float v, int lane) {
-    const float below = __shfl_up(incl, 1);
-    return v >= COMPOSITE_OPAQUE_SD ? (lane ? below : 0.f) : incl - v;
-}
-
-__device__ __forceinline__ float wave_rev_incl_scan(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        float n = __shfl_down(v, o);
-        if (lane + o < 64) v += n;
-    }
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+#include "wave.h"      // scans, the exclusive-prefix rule for opaque samples, wave_sum, the wave-per-ray index
 
 __global__ __launch_bounds__(256) void composite_fwd_kernel(const float *__restrict__ sigma, const float *__restrict__ ts,
                                                             const float *__restrict__ te, const float *__restrict__ rgb,
@@ -54,10 +18,10 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float *__restr
                                                             float *__restrict__ opacity, float *__restrict__ depth,
                                                             float *__restrict__ color, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     float carry = 0.f, a_o = 0.f, a_d = 0.f, a_r = 0.f, a_g = 0.f, a_b = 0.f;
     for (int base = 0; base < cnt; base += 64) {
         const int k = base + lane;
@@ -111,10 +75,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float *__restrict__ g_depth, const float *__restrict__ g_color, float *__restrict__ d_sigma,
     float *__restrict__ d_rgb, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     const float gO = g_opacity ? g_opacity[ray] : 0.f;
     const float gD = g_depth ? g_depth[ray] : 0.f;
     float gC0 = 0.f, gC1 = 0.f, gC2 = 0.f;

@@ -3,7 +3,7 @@
 //
 // Stands where nerfacc 0.5.x's OccGridEstimator stands for a render loop written against it.  nerfacc is third-party and
 // un-vendored: names, buffers and the update rule are recalled from its public source, agreement unverified.  The interval
-// placement is this build's definition (csrc/sampler.hip:march_wave_kernel), extended here and restated in fp32, one
+// placement is this build's definition (csrc/march.h:march_slots, one body for this file and csrc/sampler.hip), restated in fp32, one
 // rounding per operation, by tests/estimator_oracle.py -- every kernel below is held to it bit for bit.
 //   1. clip the ray to the COARSEST level's stored box (slab_clip's operations and order, per-axis lo / hi);
 //   2. a MISS (empty clip, NaN quotient, non-finite t_far) is decided on that clip alone and has no interval;
@@ -14,70 +14,23 @@
 //      ts_{k+1} = ts_k + dt_k, kept while ts_k < t_far;
 //   7. a step is a sample iff the cell of its midpoint (ts + te) / 2 is occupied in the finest level whose stored box holds the
 //      midpoint (lo <= x < hi on the three axes; none: the coarsest), cell = clamp(floor((x - lo) / (hi - lo) * R), 0, R - 1).
-// With one level, a centred cubic box and default planes these are the operations of march_wave_kernel, bit for bit.
+// With one level, a centred cubic box and default planes these are the operations of march_wave_kernel (csrc/sampler.hip), bit
+// for bit: both kernels run csrc/march.h's march_slots, which says why the cube marched as a box rounds the same.
 #include "common.h"
 
 // no FMA contraction: every mul / add / div below is one IEEE round-to-nearest operation (see csrc/sampler.hip)
 #pragma clang fp contract(off)
 
-#define EST_MAX_LEVELS 16
+#include "march.h"      // slab_clip, march_occupied, march_slots: shared with sampler.hip
+#include "wave.h"
+
+#define EST_MAX_LEVELS MARCH_MAX_LEVELS
 #define EST_CHUNK 2048          // cells one wavefront scans in the occupied-list kernels
 #define EST_MAX_PARTIALS 1024   // blocks of the mean's first pass
 
-struct EstRes {
-    int x, y, z;
-};
+typedef GridRes EstRes;
 
-// slab_clip of csrc/sampler.hip for a box given as lo[3] hi[3]
-__device__ __forceinline__ void est_clip(const float *o, const float *d, const float *box, float *t_near, float *t_far) {
-    float tmin = -INFINITY, tmax = INFINITY;
-    bool nan = false;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float ta = (box[a] - o[a]) / d[a];
-        const float tb = (box[3 + a] - o[a]) / d[a];
-        nan = nan || ta != ta || tb != tb;
-        tmin = fmaxf(tmin, fminf(ta, tb));
-        tmax = fminf(tmax, fmaxf(ta, tb));
-    }
-    tmin = fmaxf(tmin, 0.0f);
-    if (nan || !(tmax > tmin) || !(tmax < INFINITY)) {
-        tmin = 0.f;
-        tmax = 0.f;
-    }
-    *t_near = tmin;
-    *t_far = tmax;
-}
-
-__device__ __forceinline__ bool est_occupied(const float *o, const float *d, float ts, float te, const float *boxes, int L,
-                                             EstRes R, const uint8_t *__restrict__ binary) {
-    const float tm = (ts + te) / 2.0f;
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) x[a] = o[a] + d[a] * tm;
-    int lvl = L - 1;
-    for (int l = 0; l < L - 1; l++) {
-        const float *b = boxes + l * 6;
-        if (b[0] <= x[0] && x[0] < b[3] && b[1] <= x[1] && x[1] < b[4] && b[2] <= x[2] && x[2] < b[5]) {
-            lvl = l;
-            break;
-        }
-    }
-    const float *b = boxes + lvl * 6;
-    const int res[3] = {R.x, R.y, R.z};
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float u = (x[a] - b[a]) / (b[3 + a] - b[a]);
-        c[a] = min(max((int)floorf(u * (float)res[a]), 0), res[a] - 1);
-    }
-    return binary[(((int64_t)lvl * R.x + c[0]) * R.y + c[1]) * R.z + c[2]] != 0;
-}
-
-// march_wave_kernel's shape: one wavefront per ray, 64 consecutive steps a trip, ballot + prefix popcount into the slot row.
-// Cone steps are a recurrence (each rounds on the one before), so a lane cannot jump to its step: every lane walks the 64
-// steps of the trip in lockstep -- three VALU operations a step, against the latency of the occupancy byte -- and keeps its
-// own; the value behind the 64th is the next trip's start.  Bit-exact against the sequential restatement.
+// march_slots with everything on: the boxes are copied to LDS once per block (the level search reads them per step)
 __global__ __launch_bounds__(256) void est_march_kernel(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                         const float *__restrict__ jitter, const float *__restrict__ t_min,
                                                         const float *__restrict__ t_max, int N, float step, float cone,
@@ -88,67 +41,8 @@ __global__ __launch_bounds__(256) void est_march_kernel(const float *__restrict_
     __shared__ float boxes[EST_MAX_LEVELS * 6];
     if ((int)threadIdx.x < L * 6) boxes[threadIdx.x] = aabbs[threadIdx.x];
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= N) return;
-    float o[3], d[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        o[a] = rays_o[r * 3 + a];
-        d[a] = rays_d[r * 3 + a];
-    }
-    float tn, tf;
-    est_clip(o, d, boxes + (L - 1) * 6, &tn, &tf);
-    if (near_plane > tn) tn = near_plane;
-    if (t_min) {
-        const float v = t_min[r];
-        if (v > tn) tn = v;
-    }
-    if (far_plane < tf) tf = far_plane;
-    if (t_max) {
-        const float v = t_max[r];
-        if (v < tf) tf = v;
-    }
-    const float t0 = tn + (jitter ? jitter[r] : 0.0f) * step;
-    float *row_s = slot_ts + (int64_t)r * cap, *row_e = slot_te + (int64_t)r * cap;
-    const bool coned = cone > 0.f;
-    float carry = t0;      // cone marching: ts of step k0, the same value in every lane
-    int n = 0, k0 = 0;
-    for (; k0 < cap; k0 += 64) {
-        float ts, dt = step;
-        if (coned) {
-            float t = carry;
-            ts = t;
-            for (int j = 0; j < 64; j++) {
-                const float dj = fminf(fmaxf(t * cone, step), 1e10f);
-                if (j == lane) {
-                    ts = t;
-                    dt = dj;
-                }
-                t = t + dj;
-            }
-            carry = t;
-        } else {
-            ts = t0 + (float)(k0 + lane) * step;
-        }
-        const bool in = ts < tf;
-        if (__ballot(in) == 0ull) break;
-        const float te = fminf(ts + dt, tf);
-        const bool occ = in && est_occupied(o, d, ts, te, boxes, L, R, binary);
-        const unsigned long long mask = __ballot(occ);
-        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-        if (occ && pos < cap) {
-            row_s[pos] = ts;
-            row_e[pos] = te;
-        }
-        n += __popcll(mask);
-    }
-    if (lane == 0) {
-        ray_cnt[r] = n < cap ? n : cap;
-        // more kept steps than the slot row holds, or steps left unwalked: the host marches again with a longer row
-        const float next = coned ? carry : t0 + (float)k0 * step;
-        if (n > cap || next < tf) atomicOr(overflow, 1);
-    }
+    march_slots<true>(rays_o, rays_d, jitter, N, step, MarchLimits{t_min, t_max, near_plane, far_plane, cone}, boxes, L, R, binary,
+                      cap, ray_cnt, slot_ts, slot_te, overflow);
 }
 
 // ---- occupied list: each level's occupied cells in index order, count on the device -------------------------------------
@@ -171,7 +65,7 @@ __global__ __launch_bounds__(256) void est_occ_list_kernel(const uint8_t *__rest
         const bool occ = idx < cells && row[idx] != 0;
         const unsigned long long mask = __ballot(occ);
         if (PACK) {
-            const int64_t dst = (int64_t)chunk_start[w] + n + __popcll(mask & ((1ull << lane) - 1ull));
+            const int64_t dst = (int64_t)chunk_start[w] + n + wave_rank(mask, lane);
             if (occ && dst >= 0 && dst < cells) occ_list[(int64_t)l * cells + dst] = (int32_t)idx;
         }
         n += __popcll(mask);
@@ -250,11 +144,10 @@ __global__ __launch_bounds__(256) void est_ema_kernel(const int32_t *__restrict_
 
 // ---- threshold and binaries: thre = min(mean(occs[occs >= 0]), cap), the mean summed in float64 in a fixed order --------
 __device__ __forceinline__ void est_block_sum(double &s, double &c, double *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o);
-        c += __shfl_down(c, o);
-    }
+    // only lane 0 is used: the down form this replaces gave lane 0 the butterfly's association (at every step lane 0 adds
+    // lane o, whose partner 2 o exists)
+    s = wave_sum(s);
+    c = wave_sum(c);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         sh[wave * 2] = s;

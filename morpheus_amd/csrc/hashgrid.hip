@@ -15,6 +15,7 @@
 //     row operations, embedding gradients go out as fp32 atomics (same as the reference).
 //   * both tables (3.2 MB each) are L2-resident per XCD; gathers are 8-byte float2 loads.
 #include "common.h"
+#include "wave.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -438,8 +439,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ g
         m = max(max(m, __float_as_uint(fabsf(v[2]))), __float_as_uint(fabsf(v[3])));
     }
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max(m, __float_as_uint(fabsf(g[i])));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 

@@ -13,6 +13,7 @@
 // so the result is the same from run to run whatever order the waves arrive in, which float atomics cannot give.
 // This is the plain path: no brick staging.  The default configuration keeps hashgrid.hip's kernels.
 #include "common.h"
+#include "wave.h"
 #include <algorithm>
 #include <cmath>
 
@@ -187,8 +188,7 @@ __global__ __launch_bounds__(256) void gg_absmax_kernel(const float *__restrict_
     uint32_t m = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max(m, __float_as_uint(fabsf(g[i])));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 

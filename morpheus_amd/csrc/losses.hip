@@ -7,6 +7,7 @@
 // Every function here is the same arithmetic in fp32, one launch forward (two for a mean: block partials, then one block that
 // adds them in a fixed order -- deterministic, no atomics, nothing to zero) and one backward.
 #include "common.h"
+#include "wave.h"
 
 #define MEAN_BLOCKS 512
 #define MEAN_THREADS 256
@@ -67,11 +68,8 @@ __global__ __launch_bounds__(MEAN_THREADS) void masked_mean_partial_kernel(int k
         }
     }
     __shared__ float red[2][MEAN_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sf += __shfl_xor(sf, o);
-        sw += __shfl_xor(sw, o);
-    }
+    sf = wave_sum(sf);
+    sw = wave_sum(sw);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = sf;
         red[1][threadIdx.x >> 6] = sw;
@@ -101,11 +99,8 @@ __global__ __launch_bounds__(MEAN_THREADS) void masked_mean_final_kernel(const f
         sw += ws[2 * k + 1];
     }
     __shared__ float red[2][MEAN_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sf += __shfl_xor(sf, o);
-        sw += __shfl_xor(sw, o);
-    }
+    sf = wave_sum(sf);
+    sw = wave_sum(sw);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = sf;
         red[1][threadIdx.x >> 6] = sw;
@@ -344,8 +339,7 @@ __global__ __launch_bounds__(256) void pose_bwd_partial_kernel(const float *__re
     __shared__ float red[4][12];
 #pragma unroll
     for (int k = 0; k < 12; k++) {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) acc[k] += __shfl_xor(acc[k], s);
+        acc[k] = wave_sum(acc[k]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = acc[k];
     }
     __syncthreads();
@@ -457,12 +451,9 @@ __global__ __launch_bounds__(1024) void render_loss_kernel(const float *__restri
         s_depth += dd * dd;
     }
     __shared__ float red[3][16];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s_rgb += __shfl_xor(s_rgb, o);
-        s_mask += __shfl_xor(s_mask, o);
-        s_depth += __shfl_xor(s_depth, o);
-    }
+    s_rgb = wave_sum(s_rgb);
+    s_mask = wave_sum(s_mask);
+    s_depth = wave_sum(s_depth);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = s_rgb;
         red[1][threadIdx.x >> 6] = s_mask;

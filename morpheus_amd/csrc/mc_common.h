@@ -2,6 +2,7 @@
 // the edge numbering, the workgroup scans and the vertex formula.  Conventions: include/morpheus_hip.h (marching cubes).
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 #define MC_THREADS 256
 #define MC_WAVES (MC_THREADS / MH_WAVE)
@@ -18,22 +19,15 @@ static __constant__ uint8_t kMcEdgeAxis[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 
 
 static inline int64_t mc_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
-__device__ __forceinline__ int mc_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // exclusive prefix of a small count (< 8) over the workgroup: three ballots per wave, wave totals through LDS.  Returns the
 // thread's offset; *total = the workgroup's sum.  `red` holds MC_WAVES ints; one barrier pair per call.
 __device__ __forceinline__ int mc_block_scan(int v, int *red, int *total) {
     const int lane = mh_lane(), wave = threadIdx.x >> 6;
-    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     int pre = 0, wsum = 0;
 #pragma unroll
     for (int b = 0; b < 3; b++) {
         const uint64_t bal = __ballot((v >> b) & 1);
-        pre += __popcll(bal & below) << b;
+        pre += wave_rank(bal, lane) << b;
         wsum += __popcll(bal) << b;
     }
     if (lane == 0) red[wave] = wsum;

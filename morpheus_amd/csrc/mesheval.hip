@@ -14,6 +14,7 @@
 //   nn_unpack_kernel  keys -> idx, d2
 // Every loop is bounded by Nr, Nq, T or count.  No float atomics anywhere in this file.
 #include "common.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -237,8 +238,7 @@ __global__ __launch_bounds__(ME_THREADS) void ss_area_kernel(const float *__rest
         areas[t] = a;
     }
     uint32_t m = __float_as_uint(a);               // bits of a float >= 0 order like it
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if (mh_lane() == 0 && m) atomicMax(gmax_bits, m);
 }
 
@@ -331,13 +331,6 @@ __global__ __launch_bounds__(ME_THREADS) void icp_transform_kernel(IcpPose T, co
         out[3 * i + r] = (float)(((T.m[4 * r] * x + T.m[4 * r + 1] * y) + T.m[4 * r + 2] * z) + T.m[4 * r + 3]);
 }
 
-// sum over the 64 lanes in the fixed order of the xor butterfly (every lane ends with the same value)
-__device__ __forceinline__ double icp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // partials [gridDim.x][17]: n, sum d2, sum p (3), sum q (3), sum p q^T (9, row-major: p_a q_b at 3a + b).  A lane adds its
 // points i = first, first + stride, ... in that order; lanes meet in the butterfly, the four waves in wave order.
 __global__ __launch_bounds__(ME_THREADS) void icp_partial_kernel(const float *__restrict__ p, int64_t N,
@@ -365,7 +358,7 @@ __global__ __launch_bounds__(ME_THREADS) void icp_partial_kernel(const float *__
     }
 #pragma unroll
     for (int k = 0; k < ICP_SUMS; k++) {
-        const double w = icp_wave_sum(s[k]);
+        const double w = wave_sum(s[k]);
         if (mh_lane() == 0) wave_sums[threadIdx.x >> 6][k] = w;
     }
     __syncthreads();

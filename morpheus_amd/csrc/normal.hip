@@ -11,6 +11,7 @@
 // FMA contraction in this file): taps and positions are bit-identical to the torch expressions, the normalisation differs
 // from torch only in the order of its three-term sum.
 #include "common.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -141,10 +142,10 @@ __global__ __launch_bounds__(256) void sample_positions_bwd_kernel(const float *
                                                                    const int32_t *__restrict__ ray_cnt, int N,
                                                                    float *__restrict__ g_o, float *__restrict__ g_d) {
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int r = wave_ray();
     if (r >= N) return;
-    const int64_t base = ray_start[r];
-    const int n = ray_cnt[r];
+    int64_t base;
+    const int n = ray_range(ray_start, ray_cnt, r, &base);
     float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
     for (int i = lane; i < n; i += 64) {
         const int64_t m = base + i;
@@ -157,12 +158,10 @@ __global__ __launch_bounds__(256) void sample_positions_bwd_kernel(const float *
         }
     }
 #pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            so[a] += __shfl_xor(so[a], o);
-            sd[a] += __shfl_xor(sd[a], o);
-        }
+    for (int a = 0; a < 3; a++) {
+        so[a] = wave_sum(so[a]);
+        sd[a] = wave_sum(sd[a]);
+    }
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; a++) {
@@ -262,12 +261,9 @@ __global__ __launch_bounds__(256) void sdf_losses_kernel(const float *__restrict
         sl += o.sl;
         nd += o.nz ? 1.0f : 0.0f;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        fs += __shfl_xor(fs, o);
-        sl += __shfl_xor(sl, o);
-        nd += __shfl_xor(nd, o);
-    }
+    fs = wave_sum(fs);
+    sl = wave_sum(sl);
+    nd = wave_sum(nd);
     __shared__ float red[3][4];
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = fs;

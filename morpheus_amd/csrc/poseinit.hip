@@ -11,6 +11,7 @@
 //   mh_icp_wsums                    mh_icp_sums' reduction, term for term and in its order, with a Welsch weight per term.
 // Every loop is bounded by H * W, N or the block count.  No float atomics anywhere in this file.
 #include "common.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(PI_THREADS) void dp_emit_kernel(DpCam cam, const fl
     if (!keep) return;
     int64_t at = tile_start[blockIdx.x];
     for (int w = 0; w < wave; w++) at += wave_count[w];
-    at += __popcll(kept & ((1ull << mh_lane()) - 1ull));           // the kept lanes below this one
+    at += wave_rank(kept, mh_lane());                              // the kept lanes below this one
     if (at < 0 || at >= n) return;                                 // starts that are not this image's prefix sum write nothing outside
     const int32_t v = i / W, u = i - v * W;
     const float d = depth[i];
@@ -162,13 +163,6 @@ extern "C" int mh_knn_d2(const float *points, int64_t N, int32_t k, float *out_d
 
 // ---- Welsch-weighted sums ------------------------------------------------------------------------------------------------
 
-// sum over the 64 lanes in the fixed order of the xor butterfly (every lane ends with the same value)
-__device__ __forceinline__ double ws_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // partials [gridDim.x][19].  The partition of the points over workgroups and lanes, the order of a lane's additions and the
 // meeting of lanes, wavefronts and workgroups are mh_icp_sums' (csrc/mesheval.hip): with w = 1 the first 17 are its bytes.
 __global__ __launch_bounds__(PI_THREADS) void ws_partial_kernel(const float *__restrict__ p, int64_t N,
@@ -201,7 +195,7 @@ __global__ __launch_bounds__(PI_THREADS) void ws_partial_kernel(const float *__r
     }
 #pragma unroll
     for (int k = 0; k < WS_SUMS; k++) {
-        const double w = ws_wave_sum(s[k]);
+        const double w = wave_sum(s[k]);
         if (mh_lane() == 0) wave_sums[threadIdx.x >> 6][k] = w;
     }
     __syncthreads();

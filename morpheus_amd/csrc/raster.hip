@@ -14,6 +14,7 @@
 // mh_raster_resolve: one lane per pixel.  mh_mesh_vertex_normals: max |cross component| (atomicMax on float bits), 64-bit
 // integer atomic sums on the grid that maximum fixes, one conversion per vertex.
 #include "common.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_small_kernel(RsCam cam, const f
         uint32_t base = 0u;
         if (lane == leader) base = atomicAdd(ws.qlen, (uint32_t)__popcll(appending));
         base = (uint32_t)__shfl((int)base, leader);
-        const uint32_t slot = base + (uint32_t)__popcll(appending & ((1ull << lane) - 1ull));
+        const uint32_t slot = base + (uint32_t)wave_rank(appending, lane);
         if (slot < T) ws.queue[slot] = (int32_t)t;             // each triangle is appended at most once: slot < T always
         return;
     }
@@ -345,8 +346,7 @@ __global__ __launch_bounds__(RS_THREADS) void vn_max_kernel(const float *__restr
     uint32_t m = 0u;
     if (t < T && vn_cross(vertices, V, triangles, t, idx, n))
         m = __float_as_uint(fmaxf(fabsf(n[0]), fmaxf(fabsf(n[1]), fabsf(n[2]))));      // bits of a float >= 0 order like it
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if (mh_lane() == 0 && m) atomicMax(gmax_bits, m);
 }
 

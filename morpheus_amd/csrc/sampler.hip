@@ -6,7 +6,7 @@
 // benchmark sampler of SURVEY 8(d); definition shared with oracle/field.py:uniform_samples:
 //   slab clip to [-bound,bound]^3 -> [t_near>=0, t_far];  dt = (t_far - t_near) / (S+1);
 //   ts_i = t_near + (i + u) * dt;  te_i = t_near + (i + 1 + u) * dt;   misses -> zero-width samples at t = 0.
-//   A miss: empty clip, a NaN slab quotient, or a non-finite clipped t_near / t_far (slab_clip below).
+//   A miss: empty clip, a NaN slab quotient, or a non-finite clipped t_near / t_far (slab_clip, csrc/march.h).
 // Arithmetic is un-contracted round-to-nearest mul/add/div (no FMA) so the packed
 // samples are bit-identical to the oracle's -- samples are *inputs* to every parity test.
 #include "common.h"
@@ -18,6 +18,7 @@
 #pragma clang fp contract(off)
 
 #include "rays.h"      // Pose, pixel_ray, pose_from_c2w: shared with dataset.hip
+#include "march.h"     // slab_clip, CubeBox, march_slots: shared with estimator.hip
 
 __global__ __launch_bounds__(256) void generate_rays_kernel(float fx, float fy, float cx, float cy, Pose pose, int H,
                                                             int W, float *__restrict__ rays_o, float *__restrict__ rays_d) {
@@ -32,37 +33,11 @@ __global__ __launch_bounds__(256) void generate_rays_kernel(float fx, float fy, 
     }
 }
 
-// Slab clip of one ray to the AABB [-bound,bound]^3 -> [*t_near >= 0, *t_far]; a MISS gives t_near = t_far = 0.
-// A ray is a miss when the clipped segment is empty, when one of its six slab quotients is NaN (fmaxf / fminf would drop
-// the NaN and clip on the remaining axes; the oracle's minimum / maximum propagate it) or when the clipped t_far is not
-// finite (d = 0 inside the box: nothing bounds the walk).  For every finite ray that hits, the operations and their order
-// are the ones this file always had.  Shared by the two uniform-sampler kernels and the marcher.
-__device__ __forceinline__ void slab_clip(const float *o, const float *d, float bound, float *t_near, float *t_far) {
-    float tmin = -INFINITY, tmax = INFINITY;
-    bool nan = false;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float ta = (-bound - o[a]) / d[a];
-        const float tb = (bound - o[a]) / d[a];
-        nan = nan || ta != ta || tb != tb;
-        tmin = fmaxf(tmin, fminf(ta, tb));
-        tmax = fminf(tmax, fmaxf(ta, tb));
-    }
-    tmin = fmaxf(tmin, 0.0f);
-    // tmax > tmin >= 0 leaves +inf as the only non-finite t_far; a non-finite t_near never passes tmax > tmin
-    if (nan || !(tmax > tmin) || !(tmax < INFINITY)) {
-        tmin = 0.f;
-        tmax = 0.f;
-    }
-    *t_near = tmin;
-    *t_far = tmax;
-}
-
 // the i-th stratified interval of one ray (shared by the two uniform-sampler kernels)
 __device__ __forceinline__ void uniform_interval(const float *o, const float *d, float bound, int S, int i, float u,
                                                  float *ts, float *te) {
     float tmin, tmax;
-    slab_clip(o, d, bound, &tmin, &tmax);
+    slab_clip(o, d, CubeBox(bound).b, &tmin, &tmax);
     const float dt = (tmax - tmin) / (float)(S + 1);
     *ts = tmin + ((float)i + u) * dt;
     *te = tmin + (((float)i + 1.0f) + u) * dt;
@@ -149,76 +124,16 @@ __global__ __launch_bounds__(256) void rays_sample_uniform_kernel(float fx, floa
 //   interval k: ts = t0 + k*step, te = min(ts + step, t_far), kept while ts < t_far and only if the grid cell
 //   containing the interval's midpoint is occupied.  A miss (slab_clip: empty clip, NaN quotient, non-finite t_far) has no interval.
 // The packed layout is ragged: march into per-ray slot rows, scan the counts, pack (march_wave_kernel, march_pack_kernel).
-struct MarchRay {
-    float o[3], d[3];
-    float t0, tfar;
-};
-
-__device__ __forceinline__ MarchRay march_setup(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
-                                                const float *__restrict__ jitter, int r, float step, float bound) {
-    MarchRay m;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        m.o[a] = rays_o[r * 3 + a];
-        m.d[a] = rays_d[r * 3 + a];
-    }
-    float tmin, tmax;
-    slab_clip(m.o, m.d, bound, &tmin, &tmax);
-    m.t0 = tmin + (jitter ? jitter[r] : 0.0f) * step;
-    m.tfar = tmax;
-    return m;
-}
-
-__device__ __forceinline__ bool march_occupied(const MarchRay &m, float ts, float te, float bound, int R,
-                                               const uint8_t *__restrict__ binary) {
-    const float tm = (ts + te) / 2.0f;
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float x = m.o[a] + m.d[a] * tm;
-        const float u = (x + bound) / (2.0f * bound);
-        c[a] = min(max((int)floorf(u * (float)R), 0), R - 1);
-    }
-    return binary[((int64_t)c[0] * R + c[1]) * R + c[2]] != 0;
-}
-
-// Wave-per-ray marcher: one wavefront walks one ray, 64 consecutive steps per iteration (a lane = one step: setup once,
-// one occupancy byte per lane in flight instead of a 350-iteration dependent-load loop per thread), ballot + prefix
-// popcount compacts the occupied steps into the ray's slot row [cap]; 2 048 rays fill 2 048 waves (8 per CU) where the
-// thread-per-ray form filled 32 workgroups.  A second launch copies the slot rows to their packed positions once the
-// exclusive scan of the counts is known -- the march itself runs ONCE (a count pass + a fill pass would run it twice).
+// The march is csrc/march.h's march_slots, here for one level, the cube from the scalar `bound` held in registers, no planes
+// and no cone steps: 2 048 rays fill 2 048 waves (8 per CU) where a thread-per-ray form filled 32 workgroups.
 __global__ __launch_bounds__(256) void march_wave_kernel(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                          const float *__restrict__ jitter, int N, float step, float bound,
                                                          int R, const uint8_t *__restrict__ binary, int cap,
                                                          int32_t *__restrict__ ray_cnt, float *__restrict__ slot_ts,
                                                          float *__restrict__ slot_te, int32_t *__restrict__ overflow) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= N) return;
-    const MarchRay m = march_setup(rays_o, rays_d, jitter, r, step, bound);
-    float *row_s = slot_ts + (int64_t)r * cap, *row_e = slot_te + (int64_t)r * cap;
-    int n = 0, k0 = 0;
-    for (; k0 < cap; k0 += 64) {
-        const int k = k0 + lane;
-        const float ts = m.t0 + (float)k * step;
-        const bool in = ts < m.tfar;
-        if (__ballot(in) == 0ull) break;
-        const float te = fminf(ts + step, m.tfar);
-        const bool occ = in && march_occupied(m, ts, te, bound, R, binary);
-        const unsigned long long mask = __ballot(occ);
-        const int pos = n + __popcll(mask & ((1ull << lane) - 1ull));
-        if (occ && pos < cap) {
-            row_s[pos] = ts;
-            row_e[pos] = te;
-        }
-        n += __popcll(mask);
-    }
-    if (lane == 0) {
-        ray_cnt[r] = n < cap ? n : cap;
-        // a ray with more steps than the slot row holds (directions much shorter than unit length): tell the host, which
-        // re-runs the batch with a longer slot row
-        if (n > cap || (m.t0 + (float)k0 * step) < m.tfar) atomicOr(overflow, 1);
-    }
+    const CubeBox box(bound);
+    march_slots<false>(rays_o, rays_d, jitter, N, step, MarchLimits{}, box.b, 1, GridRes{R, R, R}, binary, cap, ray_cnt, slot_ts,
+                       slot_te, overflow);
 }
 
 __global__ __launch_bounds__(256) void march_pack_kernel(const int32_t *__restrict__ ray_start, const int32_t *__restrict__ ray_cnt,
@@ -226,10 +141,10 @@ __global__ __launch_bounds__(256) void march_pack_kernel(const int32_t *__restri
                                                          int N, int cap, int32_t *__restrict__ ray_idx,
                                                          float *__restrict__ t_starts, float *__restrict__ t_ends) {
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int r = wave_ray();
     if (r >= N) return;
-    const int n = ray_cnt[r];
-    const int64_t base = ray_start[r];
+    int64_t base;
+    const int n = ray_range(ray_start, ray_cnt, r, &base);
     const float *row_s = slot_ts + (int64_t)r * cap, *row_e = slot_te + (int64_t)r * cap;
     for (int i = lane; i < n; i += 64) {
         ray_idx[base + i] = r;

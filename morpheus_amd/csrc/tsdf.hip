@@ -12,6 +12,7 @@
 //   tsdf_vertex_colors_kernel  a lane per marching-cubes vertex
 // Every loop is bounded by the box or the image; every index is formed from clamped integers.
 #include "tsdf_common.h"
+#include "wave.h"
 
 #define TSDF_GROUP 4                                    // blocks per workgroup along z: 32 voxels = one 128-byte line
 
@@ -40,11 +41,8 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_bounds_kernel(const float *
     }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = min(lo[a], __shfl_xor(lo[a], o));
-            hi[a] = max(hi[a], __shfl_xor(hi[a], o));
-        }
+        lo[a] = wave_min(lo[a]);
+        hi[a] = wave_max(hi[a]);
     }
     if (mh_lane() == 0 && lo[0] != INT32_MAX) {                // a wave with a usable pixel has all six
 #pragma unroll

@@ -277,8 +277,8 @@ __global__ __launch_bounds__(MC_THREADS) void sparse_mc_count_kernel(const float
         const int cube = sp_cube(h, iso, l);
         if (cube >= 0) nt += ntri[cube];
     }
-    nv = mc_wave_sum(nv);
-    nt = mc_wave_sum(nt);
+    nv = wave_sum(nv);
+    nt = wave_sum(nt);
     if (mh_lane() == 0) {
         red[0][threadIdx.x >> 6] = nv;
         red[1][threadIdx.x >> 6] = nt;

@@ -8,30 +8,14 @@
 // reading the ray and only zeroes the rest of its keep bytes.  The compaction is the marcher's: ballot + prefix popcount.
 // No atomics, no LDS, no cross-ray sum.
 #include "common.h"
+#include "wave.h"
 
-// exclusive wave scan that survives +inf terms (an opaque sample: alpha = 1, or sigma = inf): the compositor's `incl - v` would
-// form inf - inf there
+// exclusive wave scan that survives +inf terms (an opaque sample: alpha = 1, or sigma = inf): the "lane below" form, where the
+// compositor's `incl - v` would form inf - inf
 __device__ __forceinline__ float wave_excl_scan(float v, int lane, float *total) {
-    float incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        float n = __shfl_up(incl, o);
-        if (lane >= o) incl += n;
-    }
-    const float prev = __shfl_up(incl, 1);
+    const float incl = wave_incl_scan(v, lane);
     *total = __shfl(incl, 63);
-    return lane == 0 ? 0.f : prev;
-}
-
-// the ray's sample range, held inside the packed arrays whatever ray_start / ray_cnt say
-__device__ __forceinline__ int ray_range(const int32_t *__restrict__ ray_start, const int32_t *__restrict__ ray_cnt, int ray,
-                                         int64_t M, int64_t *start) {
-    const int64_t s = ray_start[ray];
-    int64_t c = ray_cnt[ray];
-    if (s < 0 || s >= M || c < 0) c = 0;
-    if (s + c > M) c = M - s;
-    *start = s;
-    return (int)c;
+    return wave_excl_below(incl, lane, 0.f);
 }
 
 template <bool ALPHA>
@@ -42,10 +26,10 @@ __global__ __launch_bounds__(256) void visibility_mask_kernel(const float *__res
                                                               const float *__restrict__ alpha_thre,
                                                               uint8_t *__restrict__ keep, int32_t *__restrict__ kept_cnt) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
     int64_t start;
-    const int cnt = ray_range(ray_start, ray_cnt, ray, M, &start);
+    const int cnt = ray_range_clamped(ray_start, ray_cnt, ray, M, &start);
     const float thre = alpha_thre ? *alpha_thre : 0.f;
     float carry = 0.f;       // optical depth of the samples before this chunk: T = exp(-carry - prefix inside the chunk)
     int n = 0, base = 0;
@@ -93,10 +77,10 @@ __global__ __launch_bounds__(256) void visibility_pack_kernel(const uint8_t *__r
                                                               float *__restrict__ out_ts, float *__restrict__ out_te,
                                                               int32_t *__restrict__ src_index) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
     int64_t start;
-    const int cnt = ray_range(ray_start, ray_cnt, ray, M, &start);
+    const int cnt = ray_range_clamped(ray_start, ray_cnt, ray, M, &start);
     const int64_t dst0 = new_start[ray];
     int n = 0;
     for (int base = 0; base < cnt; base += 64) {
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(256) void visibility_pack_kernel(const uint8_t *__r
         const int64_t i = start + k;
         const bool kp = k < cnt && keep[i] != 0;
         const unsigned long long mask = __ballot(kp);
-        const int64_t dst = dst0 + n + __popcll(mask & ((1ull << lane) - 1ull));
+        const int64_t dst = dst0 + n + wave_rank(mask, lane);
         if (kp && dst >= 0 && dst < M_out) {
             out_ray_idx[dst] = ray;
             out_ts[dst] = ts[i];

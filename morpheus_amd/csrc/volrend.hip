@@ -4,104 +4,29 @@
 //
 // The scans follow composite.hip: one wavefront per ray, four rays per 256-thread block, the ray's packed samples walked in chunks
 // of 64, a 6-step wave scan plus a scalar carry -- no running value ever crosses a ray boundary, no atomics, so a ray's result does
-// not depend on which rays lie beside it.  The scan helpers are copies of composite.hip's (that file is not touched).
-#include "common.h"
-
-namespace {
-
-__device__ __forceinline__ float vr_incl_sum(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        float n = __shfl_up(v, o);
-        if (lane >= o) v += n;
-    }
-    return v;
-}
-
+// not depend on which rays lie beside it.  The scans are wave.h's, the density form's exclusive sum is the compositor's rule
+// (wave_excl_from_incl): ordinary densities give the compositor's weights bit for bit.
+//
 // The alpha form's factors 1 - alpha and their running product are kept in DOUBLE.  1 - alpha is rounded in fp32 wherever alpha
 // < 1/2, and a product of n fp32 factors carries n - 1 more roundings whatever the order of the multiplications, a wave scan as
 // many as the sequential loop; the opaque sample behind a thin prefix takes the whole of that as the relative error of the ray's
 // one heavy weight.  In double the factor is exact, the roundings are 2^-29 of an fp32 one and T is rounded once, when it is
 // stored.  (12 more shuffles and 6 double multiplications per 64 samples, beside the memory traffic that bounds the kernel.)
-__device__ __forceinline__ double vr_shfl_up(double v, int o) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __shfl_up((int)(b & 0xffffffffLL), o), hi = __shfl_up((int)(b >> 32), o);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double vr_shfl(double v, int src) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __shfl((int)(b & 0xffffffffLL), src), hi = __shfl((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+//
+// The reverse sums of the backward kernels are EXCLUSIVE as the inclusive value of the lane above (wave_excl_above), never
+// `incl - v`: the alpha form divides the suffix by 1 - alpha_i, and a suffix that had the sample's own (1 / (1 - alpha_i) times
+// larger) term added and taken away again keeps that term's rounding.
+#include "common.h"
+#include "wave.h"
 
-__device__ __forceinline__ double vr_shfl_down(double v, int o) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __shfl_down((int)(b & 0xffffffffLL), o), hi = __shfl_down((int)(b >> 32), o);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+namespace {
 
-__device__ __forceinline__ double vr_incl_prod(double v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        double n = vr_shfl_up(v, o);
-        if (lane >= o) v *= n;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int vr_incl_count(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int n = __shfl_up(v, o);
-        if (lane >= o) v += n;
-    }
-    return v;
-}
-
-// the value of the lane below: an exclusive prefix that never contains the lane's own factor (1 at lane 0)
-__device__ __forceinline__ double vr_prod_below(double incl, int lane) {
-    const double below = vr_shfl_up(incl, 1);
-    return lane ? below : 1.0;
-}
-
-// Exclusive sum of sd from the inclusive one: composite.hip's rule and its reason (incl - v is rounded at ulp(incl), which an
-// opaque sample's weight takes as a relative error, and inf - inf = NaN): subtract while the sample's own term is below 1, take
-// the lane below from there on.  Ordinary densities give the compositor's weights bit for bit.
-constexpr float VR_OPAQUE_SD = 1.0f;
-__device__ __forceinline__ float vr_excl_sum(float incl, float v, int lane) {
-    const float below = __shfl_up(incl, 1);
-    return v >= VR_OPAQUE_SD ? (lane ? below : 0.f) : incl - v;
-}
-
-// reverse EXCLUSIVE sum over the wave (sum of the lanes above), and the wave's total in `total`.  The exclusive value is the
-// inclusive one of the lane above, never `incl - v`: the alpha form divides the suffix by 1 - alpha_i, and a suffix that had
-// the sample's own (1 / (1 - alpha_i) times larger) term added and taken away again keeps that term's rounding.
-__device__ __forceinline__ float vr_rev_excl_sum(float v, int lane, float &total) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        float n = __shfl_down(v, o);
-        if (lane + o < 64) v += n;
-    }
-    total = __shfl(v, 0);
-    const float above = __shfl_down(v, 1);
-    return lane < 63 ? above : 0.f;
-}
-
-__device__ __forceinline__ double vr_rev_excl_sum(double v, int lane, double &total) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        double n = vr_shfl_down(v, o);
-        if (lane + o < 64) v += n;
-    }
-    total = vr_shfl(v, 0);
-    const double above = vr_shfl_down(v, 1);
-    return lane < 63 ? above : 0.0;
-}
-
-__device__ __forceinline__ float vr_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
+// reverse exclusive sum over the wave (the lanes above), and the wave's total in `total`
+template <typename T>
+__device__ __forceinline__ T vr_rev_excl_sum(T v, int lane, T &total) {
+    const T rincl = wave_rev_incl_scan(v, lane);
+    total = __shfl(rincl, 0);
+    return wave_excl_above(rincl, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------ pack_info
@@ -139,10 +64,10 @@ __global__ __launch_bounds__(256) void ray_weights_fwd_kernel(const float *__res
                                                               const int32_t *__restrict__ ray_cnt, float *__restrict__ weights,
                                                               float *__restrict__ trans, float *__restrict__ alphas, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     float carry = 0.f;
     double carry_p = 1.0;
     for (int base = 0; base < cnt; base += 64) {
@@ -152,13 +77,13 @@ __global__ __launch_bounds__(256) void ray_weights_fwd_kernel(const float *__res
         float T, alpha;
         if (ALPHA) {
             alpha = on ? val[i] : 0.f;
-            const double incl = vr_incl_prod(1.0 - (double)alpha, lane);      // the factor itself is exact in double
-            T = (float)(carry_p * vr_prod_below(incl, lane));
-            carry_p *= vr_shfl(incl, 63);
+            const double incl = wave_incl_prod(1.0 - (double)alpha, lane);      // the factor itself is exact in double
+            T = (float)(carry_p * wave_excl_below(incl, lane, 1.0));
+            carry_p *= __shfl(incl, 63);
         } else {
             const float sd = on ? val[i] * (te[i] - ts[i]) : 0.f;
-            const float incl = vr_incl_sum(sd, lane);
-            T = expf(-(carry + vr_excl_sum(incl, sd, lane)));
+            const float incl = wave_incl_scan(sd, lane);
+            T = expf(-(carry + wave_excl_from_incl(incl, sd, lane)));
             alpha = -expm1f(-sd);
             carry += __shfl(incl, 63);
         }
@@ -179,10 +104,10 @@ __global__ __launch_bounds__(256) void ray_weights_bwd_density_kernel(
     const int32_t *__restrict__ ray_cnt, const float *__restrict__ trans, const float *__restrict__ g_w, const float *__restrict__ g_T,
     const float *__restrict__ g_a, float *__restrict__ d_sigma, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     float tail = 0.f;
     for (int c = (cnt + 63) / 64 - 1; c >= 0; c--) {
         const int k = c * 64 + lane;
@@ -218,10 +143,10 @@ __global__ __launch_bounds__(256) void ray_weights_bwd_alpha_kernel(const float 
                                                                     const int32_t *__restrict__ ray_cnt, const float *__restrict__ g_w,
                                                                     const float *__restrict__ g_T, float *__restrict__ d_alpha, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     double carry_p = 1.0;
     int carry_z = 0;
     for (int base = 0; base < cnt; base += 64) {
@@ -230,12 +155,12 @@ __global__ __launch_bounds__(256) void ray_weights_bwd_alpha_kernel(const float 
         const int64_t i = start + k;
         const double f = on ? 1.0 - (double)alphas[i] : 1.0;      // exact
         const bool zero = f == 0.0;
-        const double incl_p = vr_incl_prod(zero ? 1.0 : f, lane);
-        const int incl_z = vr_incl_count(zero ? 1 : 0, lane);
-        const float P = (float)(carry_p * vr_prod_below(incl_p, lane));
+        const double incl_p = wave_incl_prod(zero ? 1.0 : f, lane);
+        const int incl_z = wave_incl_scan(zero ? 1 : 0, lane);
+        const float P = (float)(carry_p * wave_excl_below(incl_p, lane, 1.0));
         const int Z = carry_z + incl_z - (zero ? 1 : 0);
         if (on) d_alpha[i] = Z == 0 ? P : (Z == 1 ? -P : 0.f);
-        carry_p *= vr_shfl(incl_p, 63);
+        carry_p *= __shfl(incl_p, 63);
         carry_z += __shfl(incl_z, 63);
     }
     // the suffix sums and the last line in double as well: what is left of fp32 is the rounding of the parked P and of the result
@@ -275,10 +200,10 @@ __global__ __launch_bounds__(256) void accumulate_fwd_small_kernel(const float *
                                                                    const int32_t *__restrict__ ray_start,
                                                                    const int32_t *__restrict__ ray_cnt, float *__restrict__ out, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     float acc[D];
 #pragma unroll
     for (int c = 0; c < D; c++) acc[c] = 0.f;
@@ -290,7 +215,7 @@ __global__ __launch_bounds__(256) void accumulate_fwd_small_kernel(const float *
     }
 #pragma unroll
     for (int c = 0; c < D; c++) {
-        const float s = vr_wave_sum(acc[c]);
+        const float s = wave_sum(acc[c]);
         if (lane == 0) out[(int64_t)ray * D + c] = s;
     }
 }
@@ -302,10 +227,10 @@ __global__ __launch_bounds__(256) void accumulate_fwd_wide_kernel(const float *_
                                                                   int G, const int32_t *__restrict__ ray_start,
                                                                   const int32_t *__restrict__ ray_cnt, float *__restrict__ out, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     const int sub = lane / G, ch = lane % G, step = 64 / G;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     // four steps' loads are issued before the first is used: with one load-use pair a step the D = 48 kernel ran at 0.41 of the
@@ -333,8 +258,7 @@ __global__ __launch_bounds__(256) void accumulate_fwd_wide_kernel(const float *_
     }
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-        float v = acc[s];
-        for (int o = G; o < 64; o <<= 1) v += __shfl_xor(v, o);
+        const float v = wave_sum_across(acc[s], G);
         const int c = ch + s * 64;
         if (sub == 0 && c < D) out[(int64_t)ray * D + c] = v;
     }
@@ -348,10 +272,10 @@ __global__ __launch_bounds__(256) void accumulate_bwd_small_kernel(const float *
                                                                    const int32_t *__restrict__ ray_cnt, const float *__restrict__ g_out,
                                                                    float *__restrict__ d_weights, float *__restrict__ d_values, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     float g[D];
 #pragma unroll
     for (int c = 0; c < D; c++) g[c] = g_out[(int64_t)ray * D + c];
@@ -378,10 +302,10 @@ __global__ __launch_bounds__(256) void accumulate_bwd_wide_kernel(const float *_
                                                                   const int32_t *__restrict__ ray_cnt, const float *__restrict__ g_out,
                                                                   float *__restrict__ d_weights, float *__restrict__ d_values, int N) {
     const int lane = threadIdx.x & 63;
-    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ray = wave_ray();
     if (ray >= N) return;
-    const int64_t start = ray_start[ray];
-    const int cnt = ray_cnt[ray];
+    int64_t start;
+    const int cnt = ray_range(ray_start, ray_cnt, ray, &start);
     const int sub = lane / G, ch = lane % G, step = 64 / G;
     float g[4];
 #pragma unroll
@@ -405,7 +329,7 @@ __global__ __launch_bounds__(256) void accumulate_bwd_wide_kernel(const float *_
             }
         }
         if (d_weights) {
-            for (int o = 1; o < G; o <<= 1) s_gv += __shfl_xor(s_gv, o);
+            s_gv = wave_sum_within(s_gv, G);
             if (on && ch == 0) d_weights[i] = s_gv;
         }
     }

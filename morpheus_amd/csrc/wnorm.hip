@@ -9,6 +9,7 @@
 //         dv[r,:] = (g[r] / ||v[r,:]||) * (dW[r,:] - v[r,:] * <dW[r,:], v[r,:]> / ||v[r,:]||^2)
 // (the formulas of torch's _weight_norm_interface / _backward).  Layer descriptors travel by value.
 #include "common.h"
+#include "wave.h"
 
 #define WN_MAX_LAYERS 32
 struct WnLayers {
@@ -22,16 +23,10 @@ struct WnLayers {
     float *out1[WN_MAX_LAYERS];      // fwd: unused bwd: dg
 };
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 template <bool BWD>
 __global__ __launch_bounds__(256) void wn_kernel(WnLayers L) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int row = wave_ray();
     if (row >= L.row_end[L.n - 1]) return;
     int l = 0;
     while (row >= L.row_end[l]) l++;

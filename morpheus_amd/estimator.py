@@ -10,8 +10,8 @@ nerfacc is third-party, un-vendored and not on any machine this project uses.  T
 [3], `aabbs` [levels,6], `occs` [levels * cells_per_lvl], `binaries` bool [levels,Rx,Ry,Rz]), the signatures and defaults of
 `sampling`, `update_every_n_steps` and `mark_invisible_cells`, and the update rule are nerfacc 0.5.x's as RECALLED from its public
 source: recalled, agreement unverified.  The interval placement is NOT nerfacc's DDA cell traversal: it stays this build's
-fixed-lattice definition (csrc/sampler.hip), extended by levels, planes and cone steps -- include/morpheus_hip.h states it,
-tests/estimator_oracle.py restates it in fp32 and the kernels equal that bit for bit.
+fixed-lattice definition (csrc/march.h, the one march behind both classes), extended by levels, planes and cone steps --
+include/morpheus_hip.h states it, tests/estimator_oracle.py restates it in fp32 and the kernels equal that bit for bit.
 
 `occgrid.OccupancyGrid` stays what the reference's own call uses.  Differences from it:
   * without a density function (`sigma_fn` / `alpha_fn`) `alpha_thre` and `early_stop_eps` are IGNORED, as nerfacc does --
@@ -36,6 +36,7 @@ import torch
 
 from . import ops
 from ._lib import MorpheusHipError
+from .occgrid import PackedSampling
 
 __all__ = ["OccGridEstimator", "level_aabbs"]
 
@@ -55,7 +56,7 @@ def level_aabbs(roi_aabb, levels: int) -> np.ndarray:
     return out
 
 
-class OccGridEstimator(torch.nn.Module):
+class OccGridEstimator(PackedSampling, torch.nn.Module):
     def __init__(self, roi_aabb, resolution=128, levels: int = 1):
         super().__init__()
         if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not (1 <= levels <= MAX_LEVELS):
@@ -75,12 +76,7 @@ class OccGridEstimator(torch.nn.Module):
         self._res = tuple(res)
         self._set_diagonal(aabbs)
         self.thre: Optional[torch.Tensor] = None     # device scalar: the threshold of the last update
-        self.packed = None
-        self.src_index = None
-        self.fixed_jitter = None
-        self.sample_capacity: Optional[int] = None
-        self.n_valid: Optional[torch.Tensor] = None
-        self.overflow: Optional[torch.Tensor] = None
+        self._init_sampling_state()
 
     def _set_diagonal(self, aabbs):
         # the slot-row bound needs the coarsest diagonal on the HOST: kept from construction / loading, never read back
@@ -113,38 +109,14 @@ class OccGridEstimator(torch.nn.Module):
         if not rays_o.is_cuda or not self.occs.is_cuda:
             raise MorpheusHipError("OccGridEstimator.sampling runs on an MI355X only (rays on %s, estimator on %s); there is "
                                    "no CPU path" % (rays_o.device, self.occs.device))
-        n, dev = rays_o.shape[0], rays_o.device
-        if isinstance(self.fixed_jitter, float):
-            u = torch.full((n,), self.fixed_jitter, device=dev)
-        elif self.fixed_jitter is not None:
-            u = self.fixed_jitter
-        elif stratified:
-            u = torch.rand(n, device=dev)
-        else:
-            u = None
-        capped = self.sample_capacity is not None
-        out = ops.est_march_rays(rays_o, rays_d, u, float(render_step_size), self.aabbs, self.binaries.view(torch.uint8),
-                                 self._diagonal, float(cone_angle), float(near_plane), float(far_plane), t_min, t_max,
-                                 capacity=int(self.sample_capacity) if capped else None)
-        ri, ts, te, rs, rc = out[:5]
-        if capped:
-            self.n_valid = out[5]
-            if self.overflow is None:
-                self.overflow = torch.zeros((), dtype=torch.int32, device=dev)
-            self.overflow.copy_(torch.maximum(self.overflow, out[6]))
-        else:
-            self.n_valid = None
-        self.packed, self.src_index = (rs, rc), None
-        fn = sigma_fn if sigma_fn is not None else alpha_fn
-        if fn is not None and ts.shape[0] > 0:
-            thre = ops.est_threshold(self.occs, float(alpha_thre)) if alpha_thre > 0 else None      # on the device
-            out = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps), thre, alpha_form=sigma_fn is None,
-                                       padded=capped)
-            ri, ts, te, rs, rc, self.src_index = out[:6]
-            if capped:
-                self.n_valid = out[6]
-            self.packed = (rs, rc)
-        return ri, ts, te
+
+        def march(u, capacity):
+            return ops.est_march_rays(rays_o, rays_d, u, float(render_step_size), self.aabbs, self.binaries.view(torch.uint8),
+                                      self._diagonal, float(cone_angle), float(near_plane), float(far_plane), t_min, t_max,
+                                      capacity=capacity)
+
+        return self._sample(rays_o.shape[0], rays_o.device, stratified, march, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
+                            lambda cap: ops.est_threshold(self.occs, cap))
 
     # -- occupancy update -------------------------------------------------------------------------
     def make_draws(self, warmup: bool):

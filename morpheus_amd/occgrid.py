@@ -9,8 +9,8 @@ here follow its published 0.5.x behaviour as summarised in SURVEY.md C.9 and are
     uniformly at random plus a quarter of the occupied ones), occs = max(occs*decay, new),
     binaries = occs > min(mean(occs), occ_thre);
   * sampling(...): fixed-step marching of the occupied cells with one stratified near-plane jitter per ray
-    (csrc/sampler.hip:march_wave_kernel).  With a sigma_fn or alpha_fn the marched samples are then pruned by visibility
-    (csrc/visibility.hip: T >= early_stop_eps and alpha >= min(alpha_thre, mean(occs)), include/morpheus_hip.h; recalled
+    (csrc/sampler.hip:march_wave_kernel, the march of csrc/march.h).  With a sigma_fn or alpha_fn the marched samples are then
+    pruned by visibility (csrc/visibility.hip: T >= early_stop_eps and alpha >= min(alpha_thre, mean(occs)), include/morpheus_hip.h; recalled
     from nerfacc 0.5.x, NOT verified).  The reference passes sigma_fn=None, alpha_thre=0, early_stop_eps=0: no pruning,
     the marcher's samples as they are.  Cone marching (cone_angle != 0) is not implemented.
 The heavy part of an update is occ_eval_fn = model.density on up to resolution^3 points, which runs on the HIP kernels.
@@ -35,7 +35,62 @@ def check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps):
         raise ValueError(f"sampling: alpha_thre ({alpha_thre}) and early_stop_eps ({early_stop_eps}) lie in [0, 1]")
 
 
-class OccupancyGrid(torch.nn.Module):
+class PackedSampling:
+    """What `OccupancyGrid.sampling` and `estimator.OccGridEstimator.sampling` share; the class keeps its own argument rules, its
+    march and its threshold.  State, with the same meaning in both classes:
+      packed    (ray_start, ray_cnt) of the last sampling() call, consumed by the compositor
+      src_index pruned sampling: the marched position of every returned sample (None: nothing was pruned)
+      fixed_jitter  parity runs pin the per-ray jitter (a float: one value for every ray, chunk-invariant; a tensor: per ray)
+      sample_capacity  None = off: ragged packed samples sized by one device->host sync, as nerfacc does.  With a capacity the
+                packed arrays always have that length, the first `n_valid` (a device int) entries are the samples and the rest is
+                padding no ray owns: constant shapes and no sync, so a whole training step can be captured in a HIP graph
+                (trainstep.GraphedRealViewStep).  `overflow` (device int, sticky) is set when a batch had more samples than the
+                capacity -- its tail rays were truncated -- and is the caller's cue to raise the capacity."""
+
+    def _init_sampling_state(self):
+        self.packed = None
+        self.src_index = None
+        self.fixed_jitter: Optional[torch.Tensor] = None
+        self.sample_capacity: Optional[int] = None
+        self.n_valid: Optional[torch.Tensor] = None
+        self.overflow: Optional[torch.Tensor] = None
+
+    def _sample(self, n: int, dev, stratified: bool, march: Callable, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
+                threshold: Callable):
+        """march(u, capacity) -> the ragged five results (capacity None) or the fixed-capacity seven (ops.march_rays /
+        ops.march_rays_capped and ops.est_march_rays); threshold(alpha_thre) -> the pruning threshold as a device scalar."""
+        if isinstance(self.fixed_jitter, float):
+            u = torch.full((n,), self.fixed_jitter, device=dev)
+        elif self.fixed_jitter is not None:
+            u = self.fixed_jitter
+        elif stratified:
+            u = torch.rand(n, device=dev)
+        else:
+            u = None
+        capped = self.sample_capacity is not None
+        out = march(u, int(self.sample_capacity) if capped else None)
+        ri, ts, te, rs, rc = out[:5]
+        if capped:
+            self.n_valid = out[5]
+            if self.overflow is None:
+                self.overflow = torch.zeros((), dtype=torch.int32, device=dev)
+            self.overflow.copy_(torch.maximum(self.overflow, out[6]))
+        else:
+            self.n_valid = None
+        self.packed, self.src_index = (rs, rc), None
+        fn = sigma_fn if sigma_fn is not None else alpha_fn
+        if fn is not None and ts.shape[0] > 0:
+            thre = threshold(float(alpha_thre)) if alpha_thre > 0 else None      # formed on the device
+            out = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps), thre, alpha_form=sigma_fn is None,
+                                       padded=capped)
+            ri, ts, te, rs, rc, self.src_index = out[:6]
+            if capped:
+                self.n_valid = out[6]
+            self.packed = (rs, rc)
+        return ri, ts, te
+
+
+class OccupancyGrid(PackedSampling, torch.nn.Module):
     def __init__(self, roi_aabb, resolution: int = 128):
         super().__init__()
         aabb = torch.as_tensor(roi_aabb, dtype=torch.float32).reshape(-1)
@@ -53,17 +108,7 @@ class OccupancyGrid(torch.nn.Module):
         self.register_buffer("occs", torch.zeros(R ** 3))
         self.register_buffer("binaries", torch.zeros(1, R, R, R, dtype=torch.bool))
         self._R = R
-        self.packed = None       # (ray_start, ray_cnt) of the last sampling() call, consumed by the compositor
-        self.src_index = None    # pruned sampling: the marched position of every returned sample (None: nothing was pruned)
-        self.fixed_jitter: Optional[torch.Tensor] = None   # parity runs pin the per-ray jitter
-        # Fixed-capacity sampling (None = off: ragged packed samples sized by one device->host sync, as nerfacc does).
-        # With a capacity the packed arrays always have that length, the first `n_valid` (a device int) entries are the
-        # samples and the rest is padding no ray owns: constant shapes and no sync, so a whole training step can be captured
-        # in a HIP graph (trainstep.GraphedRealViewStep).  `overflow` (device int, sticky) is set when a batch had more
-        # samples than the capacity -- its tail rays were truncated -- and is the caller's cue to raise the capacity.
-        self.sample_capacity: Optional[int] = None
-        self.n_valid: Optional[torch.Tensor] = None
-        self.overflow: Optional[torch.Tensor] = None
+        self._init_sampling_state()
 
     # -- sampling --------------------------------------------------------------------------------
     @torch.no_grad()
@@ -79,38 +124,17 @@ class OccupancyGrid(torch.nn.Module):
             raise NotImplementedError("cone marching (cone_angle != 0) is not used by the reference's call "
                                       "(morpheus.py:629-638) and is not implemented")
         check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps)
-        n = rays_o.shape[0]
-        if isinstance(self.fixed_jitter, float):
-            u = torch.full((n,), self.fixed_jitter, device=rays_o.device)     # one value for every ray (chunk-invariant)
-        elif self.fixed_jitter is not None:
-            u = self.fixed_jitter
-        elif stratified:
-            u = torch.rand(n, device=rays_o.device)
-        else:
-            u = None
         # a bool tensor is one byte per cell holding 0/1: the marcher reads it as uint8 without a copy
-        binary = self.binaries[0].view(torch.uint8)
-        if self.sample_capacity is not None:
-            ri, ts, te, rs, rc, self.n_valid, ovf = ops.march_rays_capped(rays_o, rays_d, u, float(render_step_size), self.bound,
-                                                                          binary, int(self.sample_capacity))
-            if self.overflow is None:
-                self.overflow = torch.zeros((), dtype=torch.int32, device=rays_o.device)
-            self.overflow.copy_(torch.maximum(self.overflow, ovf))
-        else:
-            ri, ts, te, rs, rc = ops.march_rays(rays_o, rays_d, u, float(render_step_size), self.bound, binary)
-            self.n_valid = None
-        self.packed, self.src_index = (rs, rc), None
-        fn = sigma_fn if sigma_fn is not None else alpha_fn
-        if fn is not None and ts.shape[0] > 0:
-            # nerfacc's rule: the opacity threshold never exceeds the grid's mean occupancy value; formed on the device
-            thre = torch.clamp(self.occs.mean(), max=float(alpha_thre)) if alpha_thre > 0 else None
-            out = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps), thre, alpha_form=sigma_fn is None,
-                                       padded=self.sample_capacity is not None)
-            ri, ts, te, rs, rc, self.src_index = out[:6]
-            if self.sample_capacity is not None:
-                self.n_valid = out[6]
-            self.packed = (rs, rc)
-        return ri, ts, te
+        binary, step = self.binaries[0].view(torch.uint8), float(render_step_size)
+
+        def march(u, capacity):
+            if capacity is None:
+                return ops.march_rays(rays_o, rays_d, u, step, self.bound, binary)
+            return ops.march_rays_capped(rays_o, rays_d, u, step, self.bound, binary, capacity)
+
+        # nerfacc's rule: the opacity threshold never exceeds the grid's mean occupancy value
+        return self._sample(rays_o.shape[0], rays_o.device, stratified, march, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
+                            lambda cap: torch.clamp(self.occs.mean(), max=cap))
 
     # -- occupancy update -------------------------------------------------------------------------
     def _cell_points(self, idx: torch.Tensor) -> torch.Tensor:

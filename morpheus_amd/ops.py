@@ -657,41 +657,89 @@ def _ray_jitter(jitter, n_rays: int):
     return jitter.reshape(-1).contiguous()
 
 
-def march_rays(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor):
-    """Occupancy-grid marcher -> (ray_idx int32 [M], t_starts [M], t_ends [M], ray_start [N], ray_cnt [N]).
-    One host sync on the path: M = total sample count sizes the packed arrays (nerfacc synchronises at the same point).
-    Single pass, one wavefront per ray (mh_march_slots + mh_march_pack); a batch with rays that overflow the per-ray slot
-    row (directions much shorter than unit length) is marched again with a slot row twice as long."""
-    require_gpu(rays_o, rays_d, jitter, binary)
-    lib = _lib.load()
-    o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
-    j = _ray_jitter(jitter, rays_o.shape[0])
-    assert binary.dtype == torch.uint8 and binary.is_contiguous() and binary.dim() == 3
-    N, R, dev = o.shape[0], binary.shape[0], o.device
+# ---- the march: slot rows, a scan of the counts, pack (csrc/march.h behind both slots entries) ---------------------------
+def _march_slots(entry, head, N: int, tail, cap: int, dev, call=None):
+    """One launch of a slots entry (mh_march_slots / mh_est_march_slots: the arguments are head, N, tail, cap and the four
+    outputs) -> (cnt_ovf int32 [N + 1] = [ray_cnt | slot-row overflow flag], rows fp32 [2, N, cap])."""
+    cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+    rows = torch.empty(2, N, cap, device=dev)
+    (call or _timed)(entry, *head, N, *tail, cap, ptr(cnt_ovf), ptr(rows[0]), ptr(rows[1]), cnt_ovf.data_ptr() + 4 * N)
+    return cnt_ovf, rows
+
+
+def _march_ragged(who: str, entry, head, N: int, tail, cap: int, dev):
+    """The ragged result (ray_idx int32 [M], t_starts [M], t_ends [M], ray_start [N], ray_cnt [N]).  One host sync: M = total
+    sample count sizes the packed arrays (nerfacc synchronises at the same point); the same read brings the overflow flag, and
+    a batch with a ray that overflows its slot row is marched again with a slot row twice as long."""
     if N == 0:
         e = torch.empty(0, device=dev)
         z = torch.empty(0, dtype=torch.int32, device=dev)
         return z, e, e.clone(), z.clone(), z.clone()
-    cap = int(lib.mh_march_cap(float(step), float(bound)))
     while True:
-        cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)     # [ray_cnt | overflow flag]
+        cnt_ovf, rows = _march_slots(entry, head, N, tail, cap, dev)
         cnt = cnt_ovf[:N]
-        slots = torch.empty(2, N, cap, device=dev)
-        _timed("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt),
-               ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
         csum = torch.cumsum(cnt_ovf, 0, dtype=torch.int32)              # last element = M + overflow flag
         start = (csum[:N] - cnt).contiguous()
         M, tot = csum[N - 1:].tolist()                                  # the one device->host sync
         if tot == M:                                                    # no overflow
             break
         if cap > (1 << 20):
-            raise _lib.MorpheusHipError("march_rays: a ray takes more than 2^20 steps inside the box (step size / direction scale?)")
+            raise _lib.MorpheusHipError(f"{who}: a ray takes more than 2^20 steps inside the box (step size / direction scale?)")
         cap *= 2
     ri = torch.empty(M, dtype=torch.int32, device=dev)
     ts, te = torch.empty(M, device=dev), torch.empty(M, device=dev)
     if M > 0:
-        _timed("mh_march_pack", ptr(start), ptr(cnt), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
+        _timed("mh_march_pack", ptr(start), ptr(cnt), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
     return ri, ts, te, start, cnt.contiguous()
+
+
+def capped_ranges(cnt: torch.Tensor, slot_overflow: torch.Tensor, capacity: int):
+    """The fixed-capacity bookkeeping, on whatever device `cnt` lives (no host read): per-ray counts int32 [N], N > 0, the slot-row
+    overflow flag (0-dim) and the packed length -> (start [N], cnt_c [N], n_valid 0-dim, overflow int32 0-dim).
+    start is the exclusive scan of cnt clamped to capacity and cnt_c = min(cnt, capacity - start), so start + cnt_c never passes
+    capacity, a ray behind the cut has start = capacity, cnt_c = 0, and start stays the exclusive scan of cnt_c.
+    n_valid = min(total, capacity); overflow != 0: more samples than capacity, or a ray overflowed its slot row."""
+    csum = torch.cumsum(cnt, 0, dtype=torch.int32)
+    start = (csum - cnt).clamp_(max=capacity)
+    total = csum[-1]
+    cnt_c = torch.minimum(cnt, capacity - start)
+    n_valid = total.clamp(max=capacity)
+    overflow = ((total > capacity) | (slot_overflow != 0)).to(torch.int32)
+    return start, cnt_c, n_valid, overflow
+
+
+def _march_capped(entry, head, N: int, tail, cap: int, dev, capacity: int):
+    """The fixed-capacity seven-tuple (ray_idx int32 [capacity], t_starts, t_ends [capacity], ray_start [N], ray_cnt [N], n_valid
+    int32 0-dim, overflow int32 0-dim): constant shapes and no device->host sync, so that a training step can be captured in a
+    HIP graph.  The first n_valid entries are the packed samples (identical to the ragged ones); the rest is padding (ray 0,
+    t = 0) that no ray owns (capped_ranges).  overflow != 0: the caller re-captures with a larger capacity."""
+    assert N > 0 and capacity > 0
+    cnt_ovf, rows = _march_slots(entry, head, N, tail, cap, dev)
+    start, cnt_c, n_valid, overflow = capped_ranges(cnt_ovf[:N], cnt_ovf[N], capacity)
+    ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
+    ts, te = torch.zeros(capacity, device=dev), torch.zeros(capacity, device=dev)
+    _timed("mh_march_pack", ptr(start), ptr(cnt_c), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
+    return ri, ts, te, start, cnt_c, n_valid, overflow
+
+
+def _grid_march_args(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor):
+    """-> (head, N, tail, cap, device, keep): mh_march_slots' arguments before N and between N and cap, the slot-row length
+    mh_march_cap gives, and the contiguous tensors the pointers in `head` name, which the caller holds while it launches"""
+    require_gpu(rays_o, rays_d, jitter, binary)
+    lib = _lib.load()
+    o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
+    j = _ray_jitter(jitter, rays_o.shape[0])
+    assert binary.dtype == torch.uint8 and binary.is_contiguous() and binary.dim() == 3
+    head, tail = (ptr(o), ptr(d), ptr(j)), (float(step), float(bound), binary.shape[0], ptr(binary))
+    return head, o.shape[0], tail, int(lib.mh_march_cap(float(step), float(bound))), o.device, (o, d, j)
+
+
+def march_rays(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor):
+    """Occupancy-grid marcher -> (ray_idx int32 [M], t_starts [M], t_ends [M], ray_start [N], ray_cnt [N]).
+    Single pass, one wavefront per ray (mh_march_slots + mh_march_pack); one host sync and the doubling retry of an overflowing
+    slot row (directions much shorter than unit length) as _march_ragged states them."""
+    head, N, tail, cap, dev, _keep = _grid_march_args(rays_o, rays_d, jitter, step, bound, binary)
+    return _march_ragged("march_rays", "mh_march_slots", head, N, tail, cap, dev)
 
 
 def march_count(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor) -> torch.Tensor:
@@ -700,53 +748,18 @@ def march_count(rays_o, rays_d, jitter, step: float, bound: float, binary: torch
     One march at the slot-row length mh_march_cap gives and no retry: the overflow flag is not read, so for a batch with a ray
     that overflows its slot row (directions much shorter than unit length -- march_rays marches such a batch again) the result
     is a LOWER BOUND of march_rays' total, each overflowing ray counted at the slot-row length at most."""
-    require_gpu(rays_o, rays_d, jitter, binary)
-    lib = _lib.load()
-    o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
-    j = _ray_jitter(jitter, rays_o.shape[0])
-    assert binary.dtype == torch.uint8 and binary.is_contiguous() and binary.dim() == 3
-    N, R, dev = o.shape[0], binary.shape[0], o.device
+    head, N, tail, cap, dev, _keep = _grid_march_args(rays_o, rays_d, jitter, step, bound, binary)
     if N == 0:
         return torch.zeros((), dtype=torch.int32, device=dev)
-    cap = int(lib.mh_march_cap(float(step), float(bound)))
-    cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-    slots = torch.empty(2, N, cap, device=dev)
-    launch("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt_ovf),
-           ptr(slots[0]), ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
+    cnt_ovf, _rows = _march_slots("mh_march_slots", head, N, tail, cap, dev, call=launch)
     return cnt_ovf[:N].sum(dtype=torch.int32)
 
 
 def march_rays_capped(rays_o, rays_d, jitter, step: float, bound: float, binary: torch.Tensor, capacity: int):
-    """The same marcher with a FIXED packed length and no device->host sync, so that a training step has constant shapes and
-    can be captured in a HIP graph: -> (ray_idx int32 [capacity], t_starts, t_ends [capacity], ray_start [N], ray_cnt [N],
-    n_valid int32 0-dim, overflow int32 0-dim).  The first n_valid entries are the packed samples (identical to march_rays');
-    the rest is padding (ray 0, t = 0) that no ray owns: ray_cnt and ray_start are clamped so that start + cnt never passes
-    `capacity` (a ray behind the cut has start = capacity, cnt = 0: ray_start stays the exclusive scan of ray_cnt).
-    overflow != 0: the batch had more samples than `capacity` (the tail rays were truncated) or a ray overflowed its slot
-    row -- the caller re-captures with a larger capacity."""
-    require_gpu(rays_o, rays_d, jitter, binary)
-    lib = _lib.load()
-    o, d = rays_o.detach().contiguous(), rays_d.detach().contiguous()
-    j = _ray_jitter(jitter, rays_o.shape[0])
-    assert binary.dtype == torch.uint8 and binary.is_contiguous() and binary.dim() == 3
-    N, R, dev = o.shape[0], binary.shape[0], o.device
-    assert N > 0 and capacity > 0
-    cap = int(lib.mh_march_cap(float(step), float(bound)))
-    cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-    cnt = cnt_ovf[:N]
-    slots = torch.empty(2, N, cap, device=dev)
-    _timed("mh_march_slots", ptr(o), ptr(d), ptr(j), N, float(step), float(bound), R, ptr(binary), cap, ptr(cnt), ptr(slots[0]),
-           ptr(slots[1]), cnt_ovf.data_ptr() + 4 * N)
-    csum = torch.cumsum(cnt, 0, dtype=torch.int32)
-    start = (csum - cnt).clamp_(max=capacity)
-    total = csum[N - 1]
-    cnt_c = torch.minimum(cnt, capacity - start)
-    n_valid = total.clamp(max=capacity)
-    overflow = ((total > capacity) | (cnt_ovf[N] != 0)).to(torch.int32)
-    ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
-    ts, te = torch.zeros(capacity, device=dev), torch.zeros(capacity, device=dev)
-    _timed("mh_march_pack", ptr(start), ptr(cnt_c), ptr(slots[0]), ptr(slots[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
-    return ri, ts, te, start, cnt_c, n_valid, overflow
+    """The same marcher with a FIXED packed length and no device->host sync (_march_capped): -> (ray_idx int32 [capacity],
+    t_starts, t_ends [capacity], ray_start [N], ray_cnt [N], n_valid int32 0-dim, overflow int32 0-dim)."""
+    head, N, tail, cap, dev, _keep = _grid_march_args(rays_o, rays_d, jitter, step, bound, binary)
+    return _march_capped("mh_march_slots", head, N, tail, cap, dev, capacity)
 
 
 # ------------------------------------------------------------------------------------ occupancy estimator (csrc/estimator.hip)
@@ -778,48 +791,11 @@ def est_march_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal:
     cap = int(lib.mh_est_march_cap(step, float(diagonal), near, far))
     if cap <= 0:
         raise ValueError(f"est_march_rays: step {step}, diagonal {diagonal}, planes [{near}, {far}] give no slot row")
-
-    def slots(cap):
-        cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)     # [ray_cnt | overflow flag]
-        rows = torch.empty(2, N, cap, device=dev)
-        _timed("mh_est_march_slots", ptr(o), ptr(d), ptr(j), ptr(tmn), ptr(tmx), N, step, cone, near, far, ptr(aabbs), L, Rx, Ry, Rz,
-               ptr(binary), cap, ptr(cnt_ovf), ptr(rows[0]), ptr(rows[1]), cnt_ovf.data_ptr() + 4 * N)
-        return cnt_ovf, rows
-
+    head = (ptr(o), ptr(d), ptr(j), ptr(tmn), ptr(tmx))
+    tail = (step, cone, near, far, ptr(aabbs), L, Rx, Ry, Rz, ptr(binary))
     if capacity is not None:
-        assert N > 0 and capacity > 0
-        cnt_ovf, rows = slots(cap)
-        cnt = cnt_ovf[:N]
-        csum = torch.cumsum(cnt, 0, dtype=torch.int32)
-        start = (csum - cnt).clamp_(max=capacity)
-        total = csum[N - 1]
-        cnt_c = torch.minimum(cnt, capacity - start)
-        n_valid = total.clamp(max=capacity)
-        overflow = ((total > capacity) | (cnt_ovf[N] != 0)).to(torch.int32)
-        ri = torch.zeros(capacity, dtype=torch.int32, device=dev)
-        ts, te = torch.zeros(capacity, device=dev), torch.zeros(capacity, device=dev)
-        _timed("mh_march_pack", ptr(start), ptr(cnt_c), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
-        return ri, ts, te, start, cnt_c, n_valid, overflow
-    if N == 0:
-        e = torch.empty(0, device=dev)
-        z = torch.empty(0, dtype=torch.int32, device=dev)
-        return z, e, e.clone(), z.clone(), z.clone()
-    while True:
-        cnt_ovf, rows = slots(cap)
-        cnt = cnt_ovf[:N]
-        csum = torch.cumsum(cnt_ovf, 0, dtype=torch.int32)              # last element = M + overflow flag
-        start = (csum[:N] - cnt).contiguous()
-        M, tot = csum[N - 1:].tolist()                                  # the one device->host sync
-        if tot == M:
-            break
-        if cap > (1 << 20):
-            raise _lib.MorpheusHipError("est_march_rays: a ray takes more than 2^20 steps (step size / direction scale?)")
-        cap *= 2
-    ri = torch.empty(M, dtype=torch.int32, device=dev)
-    ts, te = torch.empty(M, device=dev), torch.empty(M, device=dev)
-    if M > 0:
-        _timed("mh_march_pack", ptr(start), ptr(cnt), ptr(rows[0]), ptr(rows[1]), N, cap, ptr(ri), ptr(ts), ptr(te))
-    return ri, ts, te, start, cnt.contiguous()
+        return _march_capped("mh_est_march_slots", head, N, tail, cap, dev, capacity)
+    return _march_ragged("est_march_rays", "mh_est_march_slots", head, N, tail, cap, dev)
 
 
 def est_occupied_list(binary):

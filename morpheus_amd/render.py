@@ -25,7 +25,7 @@ from .occgrid import check_prune_args
 
 class UniformSampler:
     """Benchmark sampler of SURVEY 8(d) behind nerfacc's `.sampling` call shape: S equal bins per
-    ray inside the AABB with one stratified jitter per ray (csrc/sampler.hip)."""
+    ray inside the AABB with one stratified jitter per ray (csrc/sampler.hip; the box clip is csrc/march.h's)."""
 
     def __init__(self, n_samples: int, bound: float, jitter: Optional[torch.Tensor] = None):
         self.n_samples, self.bound, self.jitter = n_samples, float(bound), jitter

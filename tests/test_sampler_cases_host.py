@@ -244,3 +244,43 @@ def test_pixel_ray_restatement_and_pixel_sets():
         o, d = sets[name]
         ri, ts, te = of.uniform_samples(o, d, sc.jitter_tensor(0.0, o.shape[0]), 2, sc.BOUND)
         assert (te > ts).all()
+
+
+# capacity -> (start, cnt_c) for the counts [3, 0, 5, 2] (exclusive scan [0, 3, 3, 8], total 10), written out from the
+# definition: start = min(exclusive scan, capacity), cnt_c = min(cnt, capacity - start)
+CAPPED_WANT = {
+    1: ([0, 1, 1, 1], [1, 0, 0, 0]),        # the cut falls inside the first ray
+    3: ([0, 3, 3, 3], [3, 0, 0, 0]),        # on a ray boundary, an empty ray behind it
+    4: ([0, 3, 3, 4], [3, 0, 1, 0]),        # inside the third ray
+    10: ([0, 3, 3, 8], [3, 0, 5, 2]),       # exactly the total
+    11: ([0, 3, 3, 8], [3, 0, 5, 2]),       # above the total
+}
+
+
+@pytest.mark.parametrize("capacity", sorted(CAPPED_WANT))
+def test_fixed_capacity_bookkeeping(capacity):
+    """ops.capped_ranges, the one place the fixed-capacity marches (march_rays_capped, est_march_rays with a capacity) clamp the
+    ray ranges: on CPU tensors, against values written out above"""
+    from morpheus_amd import ops
+    cnt, total = torch.tensor([3, 0, 5, 2], dtype=torch.int32), 10
+    excl = [0, 3, 3, 8]
+    want_start, want_cnt = CAPPED_WANT[capacity]
+    assert want_start == [min(e, capacity) for e in excl]
+    start, cnt_c, n_valid, overflow = ops.capped_ranges(cnt, torch.tensor(0, dtype=torch.int32), capacity)
+    assert start.dtype == cnt_c.dtype == overflow.dtype == torch.int32
+    assert start.tolist() == want_start and cnt_c.tolist() == want_cnt
+    assert all(s + c <= capacity for s, c in zip(start.tolist(), cnt_c.tolist()))
+    for r, e in enumerate(excl):
+        if e >= capacity:                                          # a ray behind the cut
+            assert start[r] == capacity and cnt_c[r] == 0
+    assert int(n_valid) == min(total, capacity) and n_valid.dim() == 0
+    assert int(overflow) == int(total > capacity) and overflow.dim() == 0
+    assert cnt.tolist() == [3, 0, 5, 2]                            # the counts are not written
+
+
+def test_fixed_capacity_overflow_carries_the_slot_row_flag():
+    from morpheus_amd import ops
+    cnt = torch.tensor([3, 0, 5, 2], dtype=torch.int32)
+    start, cnt_c, n_valid, overflow = ops.capped_ranges(cnt, torch.tensor(1, dtype=torch.int32), 11)
+    assert int(overflow) == 1 and int(n_valid) == 10
+    assert start.tolist() == CAPPED_WANT[11][0] and cnt_c.tolist() == CAPPED_WANT[11][1]
