@@ -111,6 +111,15 @@ int mh_grid_encode_fwd_binned(const float *x, const float *emb, const int32_t *o
  * global memory; smaller calls (the ~0.1 ms calls of a training step) are faster gathering.  Results are bit-identical either
  * way.  set < 0: query only.  Returns the value in force (default 2^20). */
 int64_t mh_grid_stage_min_points(int64_t set);
+/* Host only: where the staged d/dx forms of mh_grid_encode_bwd_binned keep a brick's sums in LDS, for the resolutions res_host
+ * [L] (L must be 16; a geometry the binned calls refuse returns MH_ERR_ARG).  cbase int32[3*16]: the 8-byte word k (sum x,
+ * sum y, staged table row) of vertex li of level l is at byte cbase[16 k + l] + li * stride.  Where it fits, the layout is
+ * COLUMNS: rows of 128 bytes = 16 words, stride 128, for every k the 16 levels on 16 different columns (byte / 8 mod 16),
+ * so that the 16 levels of a point -- one lane group of an 8-byte LDS atomic -- never share a bank pair; *rows is the number of
+ * 128-byte rows the accumulator takes.  A geometry whose columns would need more rows than the kernel's accumulator has gets the
+ * LINEAR layout instead (stride 24, cbase = 8 (3 first_vertex(l) + k)), the same kernel and the same results.  Purely additive:
+ * MH_ABI_VERSION is unchanged. */
+int mh_grid_bwd_layout(const int32_t *res_host, int32_t L, int32_t *cbase, int32_t *stride, int32_t *rows);
 
 /* ---- the grid encoder in full (csrc/hashgrid_general.hip) ------------------------------------
  * Every switch of the reference operator (gridencoder.cu:61-378): C = 1, 2, 4 or 8 channels per level, gridtype 0 hash /

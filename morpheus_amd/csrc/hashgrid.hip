@@ -310,9 +310,15 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float2 *__restrict_
 #define NBRK (BRK * BRK * BRK)
 #define BRK_NODES_MAX 4608   // >= sum_l (ceil(res_l/16)+2)^3 for the 16-level 16..128 pyramid (4558)
 
+#define BRK_ACC_ROWS 1152    // the staged backward's accumulator: rows of 128 bytes = 16 words of 8 (144 KB; with flush_par and item < 160 KB)
+
 struct BrickMeta {
     int32_t n[MH_MAX_LEVELS];        // LDS vertices per axis at level l
     int32_t lds_off[MH_MAX_LEVELS];  // first LDS vertex of level l
+    // the staged backward's accumulator (brick_layout): word k {sum x, sum y, table row} of vertex li of level l is at byte
+    // cbase[k][l] + li * stride
+    int32_t cbase[3][16];
+    int32_t stride;
 };
 
 __device__ __forceinline__ int brick_of(const float *__restrict__ x, int64_t p, float bound, float two_bound) {
@@ -472,9 +478,10 @@ __device__ __forceinline__ void fx_scales(uint32_t maxbits, float &to_fx, float 
 // the bound: a third of the kernel was the texture-address path working through 8 gathers x 64 distinct cache lines per wave
 // and iteration -- the same 2.1 GB of L2 gathers per table the forward does.  But a brick's points only ever read the brick's own
 // vertices, the very ones the accumulator has a slot for: the d/dx forms now STAGE the brick's table rows in LDS once per work
-// item (4558 rows, against 1024 points x 16 levels x 8 corners = 131 k gathers), one 24-byte slot per vertex {sum x, sum y, row},
-// and the loop reads a corner's row at the address it adds the corner's gradient to.  109 KB per workgroup: ONE workgroup per
-// CU (4 waves per SIMD, 128 registers), which pays for requesting the next point's operands an iteration ahead.
+// item (4558 rows, against 1024 points x 16 levels x 8 corners = 131 k gathers), three 8-byte words per vertex {sum x, sum y, row},
+// and the loop reads a corner's row beside the sums it adds the corner's gradient to.  ONE workgroup per CU (4 waves per SIMD,
+// 128 registers), which pays for requesting the next point's operands an iteration ahead -- at 109 KB when the words were
+// 24-byte slots, at 145 KB now that every level has its own LDS column per word (brick_layout; comment at `acc` in the kernel).
 // (DESIGN.md section 3 "The hash grid" has the whole table; profiles/r05_ab_hashgrid.txt the final kernels' run of it.)
 #define BRK_THREADS 1024
 constexpr int BRK_PIPE = 2;             // 0 = every operand requested in the iteration that uses it, 2 = the index two iterations ahead, x / grad one
@@ -539,11 +546,12 @@ __device__ __forceinline__ BrickLevel brk_level(const GridMeta &meta, const Bric
 }
 
 // Stage the table rows of the lane's level of the brick in LDS: vertex j of the level's block goes to the 8-byte word
-// lds8[STRIDE * (base + j) + OFF].  The lane's level, vertices sub, sub + 64, ...: BRK_STAGE_UNROLL independent gathers in flight.
+// at byte row0 + j * stride of lds.  The lane's level, vertices sub, sub + 64, ...: BRK_STAGE_UNROLL independent gathers in flight.
 // A slot past the grid's last vertex (the brick at the upper border) is never read by a point; it gets the border row.
 // (Branch-free row index as in grid_rows8: the 16 level-lanes of a wave mix dense and hashed levels.)
-template <int STRIDE, int OFF>
-__device__ __forceinline__ void brk_stage_rows(const BrickLevel &v, int sub, long long *lds8) {
+// ZERO (the backward): the vertex's two sums, at bytes z0 + j * stride and z1 + j * stride, are zeroed on the same walk.
+template <bool ZERO>
+__device__ __forceinline__ void brk_stage_rows(const BrickLevel &v, int sub, char *lds, int row0, int stride, int z0 = 0, int z1 = 0) {
     const int n3 = v.nn * v.nn * v.nn, m = (65536 + v.nn - 1) / v.nn;
     for (int j0 = sub; j0 < n3; j0 += 64 * BRK_STAGE_UNROLL) {
         float2 r[BRK_STAGE_UNROLL];
@@ -561,9 +569,18 @@ __device__ __forceinline__ void brk_stage_rows(const BrickLevel &v, int sub, lon
 #pragma unroll
         for (int u = 0; u < BRK_STAGE_UNROLL; u++) {
             const int j = j0 + 64 * u;
-            if (j < n3) *reinterpret_cast<float2 *>(&lds8[STRIDE * (v.base + j) + OFF]) = r[u];
+            if (j < n3) {
+                *reinterpret_cast<float2 *>(lds + row0 + j * stride) = r[u];
+                if (ZERO) *reinterpret_cast<long long *>(lds + z0 + j * stride) = 0, *reinterpret_cast<long long *>(lds + z1 + j * stride) = 0;
+            }
         }
     }
+}
+
+// the lane's level's sums zeroed without the rows (a work item too small to stage them): the same walk
+__device__ __forceinline__ void brk_zero_sums(int n3, int sub, char *lds, int stride, int z0, int z1) {
+    for (int j = sub; j < n3; j += 64)
+        *reinterpret_cast<long long *>(lds + z0 + j * stride) = 0, *reinterpret_cast<long long *>(lds + z1 + j * stride) = 0;
 }
 
 // Brick-binned FORWARD.  The ungrouped forward is the texture-address path working through 8 gathers x 64 distinct cache lines
@@ -591,7 +608,7 @@ __global__ __launch_bounds__(BRK_THREADS, 8) void grid_fwd_brick_kernel(const fl
     const int brick = item[0], start = item[1], end = item[2];
     const bool lev_on = l < n_levels;
     const BrickLevel lv = brk_level(meta, bm, emb, l, brick);
-    if (lev_on) brk_stage_rows<1, 0>(lv, sub, val);
+    if (lev_on) brk_stage_rows<false>(lv, sub, reinterpret_cast<char *>(val), 8 * lv.base, 8);
     __syncthreads();
     const int last = end - 1;
     // operands of the next point requested an iteration ahead, its index two ahead (as in the backward)
@@ -639,19 +656,28 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     const int32_t *__restrict__ perm, const int32_t *__restrict__ brick_start, long long *__restrict__ emb_acc, int acc_shift,
     float *__restrict__ grad_x, int L, int n_levels, float bound, float two_bound, const uint32_t *__restrict__ gmax_bits) {
     // per vertex: fixed-point sum of the x channel, of the y channel, and (d/dx forms) the vertex's table row -- 8-byte words.
-    // (Interleaved or channel-major made no difference in a round-5 A/B.  The bank-conflict replays the counters show are NOT
-    //  same-vertex collisions of the points a wave carries -- SQ_LDS_ADDR_CONFLICT is ~0, and walking the corners in a different
-    //  order per point measured the same time (comment at the atomics below): they are the 64-bit atomics of the 16 levels' regions
-    //  landing on random banks.)
-    constexpr int W = STAGED ? 3 : 2;
-    __shared__ long long acc[W * BRK_NODES_MAX];
+    // Word k of vertex li of the lane's level is at byte cb_k + li * stride (BrickMeta, brick_layout).  An 8-byte LDS write or
+    // atomic is served in four groups of 16 contiguous lanes, its bank pair is (byte / 8) mod 16 -- and a lane group here is the
+    // 16 LEVELS of one point.  With the levels' regions laid end to end (24-byte slots) the 16 addresses of a group fall on bank
+    // pairs at random and the pass is replayed: 127 M of the launch's 179 M SQ_LDS_IDX_ACTIVE cycles were SQ_LDS_BANK_CONFLICT,
+    // a ds_add_u64 on random slots costs 13.3 cycles per wave and CU against 7.3 on consecutive words (tools/micro/lds_atomics.hip).
+    // (Not same-vertex collisions of the points a wave carries: SQ_LDS_ADDR_CONFLICT is ~0, and walking the corners in a
+    // different order per point measured the same time.)  The staged form therefore views the accumulator as rows of 16 words
+    // and gives every level its OWN COLUMN for each of the three words: a group's 16 atomics are on 16 different bank pairs
+    // whatever the vertices are (8.7 cycles in the micro-benchmark; the launch 18 M conflict cycles of 74 M, cfg3's two launches
+    // 1.05 -> 0.89 ms; profiles/r20_grid_bwd_columns.txt).  The direct forms keep the end-to-end layout, 16-byte slots: two
+    // words in columns need 1027 rows = 131 KB, which would cost them their second workgroup per CU.
+    constexpr int ACC_WORDS = STAGED ? 16 * BRK_ACC_ROWS : 2 * BRK_NODES_MAX;
+    __shared__ long long acc[ACC_WORDS];
+    char *accb = reinterpret_cast<char *>(acc);
     // work item -> (brick, chunk of <= 1024 / 2048 points): hot bricks (all rays converge near the camera)
     // are split over several workgroups, each with its own LDS accumulation and flush
     __shared__ int item[3];
     if (!brk_find_item(brick_start, blockIdx.x, item)) return;
     const int brick = item[0], start = item[1], end = item[2];
     const bool staged = STAGED && end - start >= BRK_STAGE_MIN;     // uniform over the workgroup
-    for (int i = threadIdx.x; i < BRK_NODES_MAX; i += BRK_THREADS) acc[W * i] = 0, acc[W * i + 1] = 0;
+    if (!STAGED)        // every word is a sum; the staged form zeroes its sums level by level, beside the rows (below)
+        for (int i = threadIdx.x; i < BRK_NODES_MAX; i += BRK_THREADS) acc[2 * i] = 0, acc[2 * i + 1] = 0;
     float to_fx, from_fx;
     fx_scales(*gmax_bits, to_fx, from_fx);
     // the call's headroom (acc_shift) goes into the scale every term is quantized with: each term is rounded once, on the same grid
@@ -667,7 +693,14 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     const int nn = lv.nn, base = lv.base;
     const int lo[3] = {lv.lo[0], lv.lo[1], lv.lo[2]};
     const float2 *tab = lv.tab;
-    if (staged && lev_on) brk_stage_rows<W, 2>(lv, sub, acc);
+    // the direct forms' layout is fixed here, linear with two words per vertex (16-byte slots): its terms fold into the instructions
+    const int stride = STAGED ? bm.stride : 16;
+    const int cb0 = STAGED ? bm.cbase[0][l] : 16 * base, cb1 = STAGED ? bm.cbase[1][l] : cb0 + 8, cb2 = STAGED ? bm.cbase[2][l] : 0;
+    const int d1 = cb1 - cb0, d2 = cb2 - cb0;
+    if (STAGED && lev_on) {
+        if (staged) brk_stage_rows<true>(lv, sub, accb, cb2, stride, cb0, cb1);
+        else brk_zero_sums(nn * nn * nn, sub, accb, stride, cb0, cb1);
+    }
     // per-level parameters of the flush (below), from the sixteen lanes that hold one level each: the flush walks the brick's 4558
     // vertex slots in ONE flat loop, every lane looking its slot's level up here
     static_assert(MH_MAX_LEVELS >= 16, "the brick kernels run on 16-level grids (L == 16 is checked by the launchers)");
@@ -676,7 +709,7 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
         int *fp = flush_par[l];
         fp[0] = nn, fp[1] = (65536 + nn - 1) / nn, fp[2] = base, fp[3] = lo[0], fp[4] = lo[1], fp[5] = lo[2];
         fp[6] = (int)(res - 1), fp[7] = (int)lv.my, fp[8] = (int)lv.mz, fp[9] = (int)lv.mask, fp[10] = (int)lv.sel, fp[11] = (int)T;
-        fp[12] = (int)(!dense && !pow2), fp[13] = meta.offsets[l];
+        fp[12] = (int)(!dense && !pow2), fp[13] = meta.offsets[l], fp[14] = cb0, fp[15] = cb1;
     }
     __syncthreads();
     constexpr int PPI = BRK_THREADS / 16;  // points per iteration
@@ -745,25 +778,26 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
                          gyd = (double)__builtin_amdgcn_fmed3f(gr.y * to_fx, -fx_lim, fx_lim);
             // (Same-vertex collisions of the four points a wave carries are NOT what the atomics cost: with row k of the wave
             //  walking the corners in the order c ^ k -- four different vertices per instruction -- the kernel ran the same
-            //  1.16 ms; without the atomics 0.77 ms.  It is the 64-bit atomic rate itself.)
-            int slot[8];
+            //  1.16 ms; without the atomics 0.77 ms.  It was the 16 levels of a lane group sharing bank pairs: the layout's
+            //  columns, comment at `acc` above.)
+            int slot[8];    // byte address of the corner's sum x; sum y and the row are d1 and d2 behind it
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const float w = ((c & 1) ? f[0] : 1.f - f[0]) * ((c & 2) ? f[1] : 1.f - f[1]) * ((c & 4) ? f[2] : 1.f - f[2]);
                 // (24-bit multiplies: a brick has < 2^12 vertices per level, v_mul_lo_u32 is a quarter-rate instruction)
                 const int li = ((c & 1) ? lx1 : lx0) + __mul24(nn, ((c & 2) ? ly1 : ly0) + __mul24(nn, (c & 4) ? lz1 : lz0));
-                slot[c] = W * (base + li);
+                slot[c] = cb0 + __mul24(li, stride);
                 const double wd = (double)w;
                 const unsigned long long qx = (unsigned long long)__double_as_longlong(__builtin_fma(wd, gxd, magic)) - FX_MAGIC_BITS;
                 const unsigned long long qy = (unsigned long long)__double_as_longlong(__builtin_fma(wd, gyd, magic)) - FX_MAGIC_BITS;
-                atomicAdd(reinterpret_cast<unsigned long long *>(&acc[slot[c]]), qx);
-                atomicAdd(reinterpret_cast<unsigned long long *>(&acc[slot[c] + 1]), qy);
+                atomicAdd(reinterpret_cast<unsigned long long *>(accb + slot[c]), qx);
+                atomicAdd(reinterpret_cast<unsigned long long *>(accb + slot[c] + d1), qy);
             }
             if (NEED_DX) {
                 float2 v[8];
                 if (staged) {
 #pragma unroll
-                    for (int c = 0; c < 8; c++) v[c] = *reinterpret_cast<const float2 *>(&acc[slot[c] + 2]);
+                    for (int c = 0; c < 8; c++) v[c] = *reinterpret_cast<const float2 *>(accb + slot[c] + d2);
                 } else {
                     // (requesting the rows before the sixteen LDS atomics, to cover their round trip, needs 16 more live registers
                     //  than the 64 that keep two workgroups on a CU: 18 spills -- the rows are asked for here)
@@ -805,11 +839,21 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
             total = bm.lds_off[n_levels - 1] + n_last * n_last * n_last;
         }
         for (int j = threadIdx.x; j < total; j += BRK_THREADS) {
-            const long long qx = acc[W * j], qy = acc[W * j + 1];
-            if (qx == 0 && qy == 0) continue;
+            // (the staged form's slot address goes through its level's column; the direct forms look at the sums first and
+            //  find the level only for a touched vertex)
             int lev = 0;
+            if (STAGED) {
 #pragma unroll
-            for (int k = 1; k < 16; k++) lev += (k < n_levels && j >= bm.lds_off[k]) ? 1 : 0;
+                for (int k = 1; k < 16; k++) lev += (k < n_levels && j >= bm.lds_off[k]) ? 1 : 0;
+            }
+            const int a0 = STAGED ? flush_par[lev][14] + (j - flush_par[lev][2]) * stride : 16 * j;
+            const int a1 = STAGED ? flush_par[lev][15] + (j - flush_par[lev][2]) * stride : 16 * j + 8;
+            const long long qx = *reinterpret_cast<const long long *>(accb + a0), qy = *reinterpret_cast<const long long *>(accb + a1);
+            if (qx == 0 && qy == 0) continue;
+            if (!STAGED) {
+#pragma unroll
+                for (int k = 1; k < 16; k++) lev += (k < n_levels && j >= bm.lds_off[k]) ? 1 : 0;
+            }
             const int *fp = flush_par[lev];
             const int n = fp[0], m = fp[1], jl = j - fp[2];
             const int t = brk_div(jl, m), jz = brk_div(t, m);
@@ -941,6 +985,7 @@ extern "C" int mh_grid_bin_points(const float *x, int64_t M, float bound, int32_
 }
 
 static int fill_brick_meta(BrickMeta &bm, const int32_t *res_host, int L) {
+    bm = BrickMeta{};       // (cbase / stride: brick_layout, for the staged backward alone)
     int off = 0;
     for (int l = 0; l < L; l++) {
         const int n = (res_host[l] + BRK - 1) / BRK + 2;
@@ -949,6 +994,71 @@ static int fill_brick_meta(BrickMeta &bm, const int32_t *res_host, int L) {
         off += n * n * n;
     }
     return off > BRK_NODES_MAX ? MH_ERR_ARG : MH_OK;
+}
+
+// The linear layout: the levels end to end, a vertex's three 8-byte words side by side (24-byte slots).
+static int brick_layout_linear(BrickMeta &bm) {
+    for (int k = 0; k < 3; k++)
+        for (int l = 0; l < 16; l++) bm.cbase[k][l] = 8 * (3 * bm.lds_off[l] + k);
+    bm.stride = 24;
+    return (24 * (bm.lds_off[15] + bm.n[15] * bm.n[15] * bm.n[15]) + 127) / 128;
+}
+
+// The staged backward's accumulator layout for a 16-level geometry that passed fill_brick_meta; returns its rows of 128 bytes.
+// COLUMNS: the accumulator is rows of 16 words; for each of a vertex's three words the 16 levels get 16 different columns, a
+// column stacks its three segments (one of each word): word k of vertex li of level l at byte 128 (row0 + li) + 8 column.  The 16
+// levels of a point -- one lane group of an 8-byte LDS access -- are then always on 16 different bank pairs.  The packing: the
+// 48 segments, largest first, each onto the lowest column its word has not used; then two levels of a word change columns
+// whenever that lowers the taller of the two (every exchange lowers the sorted heights lexicographically: it ends).  The shipped
+// pyramid (27, 64 x 5, 125 x 2, 216 x 3, 343, 512, 729 x 2, 1000 vertices) reaches 1091 rows, the bound 1000 + 64 + 27.
+// A geometry whose packing is taller than BRK_ACC_ROWS gets the linear layout of three words (110 KB at most): same kernel.
+static int brick_layout(BrickMeta &bm) {
+    int sz[16], col[3][16], h[16] = {}, order[48];
+    bool used[3][16] = {};
+    for (int l = 0; l < 16; l++) sz[l] = bm.n[l] * bm.n[l] * bm.n[l];
+    for (int i = 0; i < 48; i++) order[i] = i;      // segment i = word i / 16 of level i % 16
+    std::stable_sort(order, order + 48, [&](int a, int b) { return sz[a % 16] > sz[b % 16]; });
+    for (int i = 0; i < 48; i++) {
+        const int k = order[i] / 16, l = order[i] % 16;
+        int best = -1;
+        for (int c = 0; c < 16; c++)
+            if (!used[k][c] && (best < 0 || h[c] < h[best])) best = c;
+        used[k][best] = true, col[k][l] = best, h[best] += sz[l];
+    }
+    for (bool moved = true; moved;) {
+        moved = false;
+        for (int k = 0; k < 3; k++)
+            for (int a = 0; a < 16; a++)
+                for (int b = a + 1; b < 16; b++) {
+                    const int ca = col[k][a], cb = col[k][b], d = sz[a] - sz[b];
+                    if (std::max(h[ca] - d, h[cb] + d) < std::max(h[ca], h[cb]))
+                        h[ca] -= d, h[cb] += d, col[k][a] = cb, col[k][b] = ca, moved = true;
+                }
+    }
+    const int rows = *std::max_element(h, h + 16);
+    if (rows > BRK_ACC_ROWS) return brick_layout_linear(bm);
+    int top[16] = {};
+    for (int k = 0; k < 3; k++)
+        for (int l = 0; l < 16; l++) {
+            const int c = col[k][l];
+            bm.cbase[k][l] = 128 * top[c] + 8 * c;
+            top[c] += sz[l];
+        }
+    bm.stride = 128;
+    return rows;
+}
+
+extern "C" int mh_grid_bwd_layout(const int32_t *res_host, int32_t L, int32_t *cbase, int32_t *stride, int32_t *rows) {
+    if (!res_host || !cbase || !stride || !rows || L != 16) return MH_ERR_ARG;
+    for (int l = 0; l < L; l++)
+        if (res_host[l] < 2) return MH_ERR_ARG;
+    BrickMeta bm;
+    if (int st = fill_brick_meta(bm, res_host, L)) return st;
+    *rows = brick_layout(bm);
+    *stride = bm.stride;
+    for (int k = 0; k < 3; k++)
+        for (int l = 0; l < 16; l++) cbase[16 * k + l] = bm.cbase[k][l];
+    return MH_OK;
 }
 
 extern "C" int mh_grid_encode_fwd_binned(const float *x, const float *emb, const int32_t *offsets_host,
@@ -986,6 +1096,8 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
     if (st) return st;
     BrickMeta bm;
     if ((st = fill_brick_meta(bm, res_host, L))) return st;
+    const bool staged = BRK_STAGE && grad_x && M >= g_stage_min_points.load(std::memory_order_relaxed);
+    if (staged) brick_layout(bm);       // (the direct forms' layout is fixed in the kernel: linear, two words)
     // upper bound on sum_b ceil(cnt_b / chunk) for either chunk size; surplus workgroups exit at once
     const unsigned work_items = (unsigned)(NBRK + M / BRK_CHUNK_SMALL + 1);
     // max|grad| (float bits): supplied by the producer of `grad` (mh_field_bwd_data computes it on the fly), else
@@ -1008,7 +1120,6 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
                        reinterpret_cast<const float2 *>(grad), x, reinterpret_cast<const float2 *>(emb), meta, bm, perm,     \
                        brick_start, reinterpret_cast<long long *>(emb_acc), acc_shift, grad_x, (int)L, (int)n_levels, bound,          \
                        2.0f * bound, gmax)
-    const bool staged = BRK_STAGE && M >= g_stage_min_points.load(std::memory_order_relaxed);
     if (grad_x && accumulate_dx) {
         // grad_x already holds a gradient of the same points (the field nets' d/dx): each visited point adds to its own row
         if (staged) BRK_LAUNCH(2, true); else BRK_LAUNCH(2, false);
