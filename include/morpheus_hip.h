@@ -1144,6 +1144,39 @@ int mh_est_threshold(const float *occs, int64_t n, float cap, double *partials, 
 int mh_est_mark_invisible(const float *K, const float *c2w, int32_t C, float width, float height, float near_plane,
                           const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, float *occs, void *stream);
 
+/* ---- importance resampling (csrc/resample.hip; morpheus_amd/resample.py is its Python face) -------------------------------
+ * Purely additive: MH_ABI_VERSION is unchanged.  One wavefront per ray; csrc/resample.hip's header states every operation, how
+ * the searched CDF is kept non-decreasing and why the cut is a merge by rank; tests/resample_oracle.py restates it.
+ * mh_sample_pdf: the reference's utils.sample_pdf (utils.py:10-44), dense: bins fp32 [B,T], weights fp32 [B,T-1], u fp32 [B,n]
+ *   -> samples fp32 [B,n] in the order of u.  T >= 2, n >= 1.  scratch: fp32 [B*T], read and written only when
+ *   T - 1 > mh_resample_stage() (may be NULL otherwise).
+ * mh_resample_packed: packed ragged samples (ray_start, ray_cnt int32 [N]; t_starts, t_ends, weights fp32 [M]; ranges are
+ *   clipped to [0, M)).  A ray with c >= 1 intervals draws n points from the piecewise-constant pdf (w_i + eps) / sum over its c
+ *   intervals (gaps between intervals carry none) at u_k = ((float)k + j_k) / (float)n, jitter j fp32 [N,n] in [0,1), NULL:
+ *   j_k = 0.5; every draw lies inside its interval [ts_i, te_i]; u at or above the last CDF value is the last interval's end.
+ *   Output: the coarse intervals cut at the draws -- c + n intervals in order from new_start[r], every coarse ts / te unchanged,
+ *   a cut point the same bits as the end of one interval and the start of the next, zero-width intervals where draws coincide
+ *   with an edge or each other; out_ray_idx = r.  A ray without samples writes nothing.  xyz (NULL: skipped) fp32 [M_out,3] =
+ *   rays_o[r] + rays_d[r] * ((ts + te) / 2) for EVERY entry of the output arrays, read through out_ray_idx.
+ *   Writes past M_out are suppressed.  scratch_cdf fp32 [M + N] and scratch_cnt int32 [M] stage the rays longer than
+ *   mh_resample_stage() intervals and are required when M exceeds it.
+ * mh_resample_ranges: new_cnt[r] = c_r + n (0 for an empty ray), new_start = its exclusive scan, *total = its sum, all held to
+ *   `limit` (start <= limit, start + cnt <= limit).  One launch, no host read.
+ * Two forms, as for the marcher: ragged -- the host reads *total once and sizes the outputs by it; fixed capacity -- the outputs
+ *   have length M + n N (M the input capacity), *total is n_valid and stays on the device, the caller zeroes the outputs (ray 0,
+ *   t = 0: the marcher's padding), nothing is synchronised and the calls may be captured in a graph.
+ * Bad arguments return MH_ERR_ARG before any launch; N == 0, M == 0 or M_out == 0 launch nothing. */
+int32_t mh_resample_stage(void);
+int mh_sample_pdf(const float *bins, const float *weights, const float *u, int32_t B, int32_t T, int32_t n, float *scratch,
+                  float *samples, void *stream);
+int mh_resample_ranges(const int32_t *ray_start, const int32_t *ray_cnt, int32_t N, int64_t M, int32_t n, int64_t limit,
+                       int32_t *new_start, int32_t *new_cnt, int32_t *total, void *stream);
+int mh_resample_packed(const float *weights, const float *t_starts, const float *t_ends, const int32_t *ray_start,
+                       const int32_t *ray_cnt, const int32_t *new_start, int32_t N, int64_t M, int32_t n, const float *jitter,
+                       float eps, float *scratch_cdf, int32_t *scratch_cnt, int64_t M_out, const float *rays_o,
+                       const float *rays_d, int32_t *out_ray_idx, float *out_t_starts, float *out_t_ends, float *xyz,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 SO = os.path.join(OUT_DIR, "libmorpheus_hip.so")
 SOURCES = ["hashgrid.hip", "hashgrid_general.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_b3.hip", "optim.hip", "wnorm.hip", "normal.hip", "graph.hip", "losses.hip",
-           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip", "volrend.hip", "dataset.hip", "preprocess.hip", "estimator.hip"]
+           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip", "volrend.hip", "dataset.hip", "preprocess.hip", "estimator.hip", "resample.hip"]
 HEADER = os.path.join(HERE, "..", "include", "morpheus_hip.h")      # the C ABI; _lib.py binds the library from this text
 HEADERS = [os.path.join(CSRC, "common.h"), HEADER]
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar fp32 adds / muls of the epilogues into v_pk_* instructions, which
@@ -39,6 +39,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # dataset.hip: rays, conversions, view labels and degree values are pinned bit for bit by tests/dataset_oracle.py, the same reason as sampler.hip's pragma
 # preprocess.hip: the float64 source coordinates and the bilinear sums of rotated frames are pinned bit for bit by tests/preprocess_oracle.py, the same reason
 # estimator.hip: un-contracted by its own pragma, like sampler.hip (tests/estimator_oracle.py states the operations)
+# resample.hip: un-contracted by its own pragma, the same way (tests/resample_oracle.py states the operations)
 FILE_FLAGS = {"adan.hip": ["-ffp-contract=off"], "losses.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"], "raster.hip": ["-ffp-contract=off"],
               "mesheval.hip": ["-ffp-contract=off"], "subdivide.hip": ["-ffp-contract=off"], "tsdf.hip": ["-ffp-contract=off"],
               "tsdf_sparse.hip": ["-ffp-contract=off"], "poseinit.hip": ["-ffp-contract=off"], "encoders.hip": ["-ffp-contract=off"],

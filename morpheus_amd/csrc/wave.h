@@ -74,6 +74,23 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
     }
     return v;
 }
+__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        double n = __shfl_up(v, o);
+        if (lane >= o) v += n;
+    }
+    return v;
+}
+// running maximum: exact, so lane i's value is >= lane i - 1's whatever the terms are (fmaxf drops a NaN term)
+__device__ __forceinline__ float wave_incl_max(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        float n = __shfl_up(v, o);
+        if (lane >= o) v = fmaxf(v, n);
+    }
+    return v;
+}
 // running product in double (the alpha form of volrend.hip, which says why it is double)
 __device__ __forceinline__ double wave_incl_prod(double v, int lane) {
 #pragma unroll

@@ -940,6 +940,82 @@ def visibility_prune(values, t_starts, t_ends, ray_start, ray_cnt, early_stop_ep
     return visibility_pack(keep, kept, t_starts, t_ends, ray_start, ray_cnt, padded)
 
 
+# ------------------------------------------------------------------------------------ importance resampling (csrc/resample.hip)
+def sample_pdf(bins, weights, u):
+    """The reference's utils.sample_pdf with the draws given (mh_sample_pdf): bins fp32 [B,T], weights fp32 [B,T-1], u fp32 [B,n]
+    -> samples fp32 [B,n] in the order of u."""
+    require_gpu(bins, weights, u)
+    lib = _lib.load()
+    b, w, uu = (t.detach().contiguous() for t in (bins, weights, u))
+    if b.dim() != 2 or w.dim() != 2 or uu.dim() != 2 or any(t.dtype != torch.float32 for t in (b, w, uu)):
+        raise ValueError(f"sample_pdf: float32 bins [B,T], weights [B,T-1] and u [B,n] expected, got {tuple(bins.shape)}, "
+                         f"{tuple(weights.shape)}, {tuple(u.shape)}")
+    B, T = b.shape
+    n = uu.shape[1]
+    if T < 2 or n < 1 or tuple(w.shape) != (B, T - 1) or uu.shape[0] != B:
+        raise ValueError(f"sample_pdf: T >= 2, n >= 1, weights [B,T-1] and u [B,n] expected, got bins {tuple(b.shape)}, weights "
+                         f"{tuple(w.shape)}, u {tuple(uu.shape)}")
+    out = torch.empty(B, n, device=b.device)
+    scratch = torch.empty(B * T, device=b.device) if T - 1 > int(lib.mh_resample_stage()) else None
+    if B > 0:
+        _timed("mh_sample_pdf", ptr(b), ptr(w), ptr(uu), B, T, n, ptr(scratch), ptr(out))
+    return out
+
+
+def resample_packed(weights, t_starts, t_ends, ray_start, ray_cnt, n: int, jitter=None, eps: float = 1e-5, padded: bool = False,
+                    rays_o=None, rays_d=None):
+    """The packed samples cut at n inverse-CDF draws per ray (mh_resample_ranges + mh_resample_packed, include/morpheus_hip.h)
+    -> (ray_idx int32 [M'], t_starts [M'], t_ends [M'], ray_start [N], ray_cnt [N], xyz [M',3] | None[, n_valid]).
+    jitter: fp32 [N,n] in [0,1), None = 0.5 (the reference's det grid).  xyz: the midpoints' positions, with rays_o / rays_d.
+    Ragged (padded=False): M' = the new total, ONE device->host read, where the marcher has one too.  padded=True: the inputs
+    have the marcher's fixed capacity M, M' = M + n N, a seventh result n_valid (int32 0-dim, device) counts the samples, the rest
+    is the marcher's padding (ray 0, t = 0); no host synchronisation."""
+    require_gpu(weights, t_starts, t_ends, ray_start, ray_cnt, jitter, rays_o, rays_d)
+    lib = _lib.load()
+    w = weights.detach().reshape(-1).float().contiguous()
+    ts, te = t_starts.detach().contiguous(), t_ends.detach().contiguous()
+    rs, rc = ray_start.contiguous(), ray_cnt.contiguous()
+    M, N, dev, n = ts.shape[0], rs.shape[0], ts.device, int(n)
+    if n < 1:
+        raise ValueError(f"resample_packed: n = {n} draws (at least one)")
+    if w.shape[0] != M or te.shape[0] != M or rc.shape[0] != N or rs.dtype != torch.int32 or rc.dtype != torch.int32 or \
+            ts.dtype != torch.float32 or te.dtype != torch.float32:
+        raise ValueError(f"resample_packed: one weight per packed sample ({M}), float32 t_starts / t_ends and int32 ray_start / "
+                         f"ray_cnt of one length, got {tuple(weights.shape)}, {rs.dtype} [{N}], {rc.dtype} [{rc.shape[0]}]")
+    if jitter is not None:
+        if jitter.dtype != torch.float32 or tuple(jitter.shape) != (N, n):
+            raise ValueError(f"resample_packed: jitter float32 [{N},{n}] expected, got {jitter.dtype} {tuple(jitter.shape)}")
+        jitter = jitter.detach().contiguous()
+    if (rays_o is None) != (rays_d is None):
+        raise ValueError("resample_packed: rays_o and rays_d together (the midpoints' positions), or neither")
+    limit = M + n * N
+    if limit > 0x7fffffff:
+        raise ValueError(f"resample_packed: {M} + {n} x {N} output samples do not fit int32 positions")
+    new_rs, new_rc = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+    total = torch.empty((), dtype=torch.int32, device=dev)
+    _timed("mh_resample_ranges", ptr(rs), ptr(rc), N, M, n, limit, ptr(new_rs), ptr(new_rc), ptr(total))
+    M_out = limit if padded else int(total)                           # ragged: the one device->host sync
+    new = (lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)) if padded else \
+        (lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=dev))
+    ri, ots, ote = new(M_out, dtype=torch.int32), new(M_out), new(M_out)
+    xyz = None
+    if rays_o is not None:
+        o, d = rays_o.detach().float().contiguous(), rays_d.detach().float().contiguous()
+        if tuple(o.shape) != (N, 3) or tuple(d.shape) != (N, 3):
+            raise ValueError(f"resample_packed: rays_o / rays_d [{N},3] expected, got {tuple(o.shape)}, {tuple(d.shape)}")
+        xyz = new(M_out, 3)
+    else:
+        o = d = None
+    if N > 0 and M > 0 and M_out > 0:
+        long_rays = M > int(lib.mh_resample_stage())                  # only then can a ray be longer than the LDS staging
+        s_cdf = torch.empty(M + N, device=dev) if long_rays else None
+        s_cnt = torch.empty(M, dtype=torch.int32, device=dev) if long_rays else None
+        _timed("mh_resample_packed", ptr(w), ptr(ts), ptr(te), ptr(rs), ptr(rc), ptr(new_rs), N, M, n, ptr(jitter), float(eps),
+               ptr(s_cdf), ptr(s_cnt), M_out, ptr(o), ptr(d), ptr(ri), ptr(ots), ptr(ote), ptr(xyz))
+    out = (ri, ots, ote, new_rs, new_rc, xyz)
+    return out + (total,) if padded else out
+
+
 # ------------------------------------------------------------------------------------ field-query glue (csrc/normal.hip)
 class _FdTaps(torch.autograd.Function):
     @staticmethod

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import chunking, ops
+from . import chunking, ops, resample
 from .model import safe_normalize, scene_representation
 from .occgrid import check_prune_args
 
@@ -79,6 +79,13 @@ class HotPathRenderer:
         # render_rays (and so eval_step) hands the sampler a sigma_fn of its own -- a density-only pass of the model under no_grad
         # -- and queries, composites and differentiates the samples that pass leaves visible only (_density_fn).
         self.prune: Optional[dict] = None
+        # Opt-in importance resampling: None (off, the call as it is without it), or dict(n_importance=, det=False, jitter=None,
+        # eps=1e-5).  When set, one density-only pass (_density_fn; the pruning pass's own when `prune` is set too) weighs the
+        # sampler's intervals and resample.importance_sampling cuts them at n_importance draws per ray; the render then carries
+        # on with the refined samples as if the sampler had returned them.  config['render']['n_importance'] seeds it (absent
+        # from the shipped configs).
+        n_imp = int((config.get("render") or {}).get("n_importance", 0) or 0)
+        self.importance: Optional[dict] = dict(n_importance=n_imp) if n_imp > 0 else None
 
     # -- helpers of morpheus.py:518-556
     def _const(self, key, build, device):
@@ -189,6 +196,39 @@ class HotPathRenderer:
 
         return sigma_fn
 
+    _IMPORTANCE_KEYS = ("n_importance", "det", "jitter", "eps")
+
+    def _importance_args(self) -> Optional[dict]:
+        """self.importance checked: None when resampling is off (None, or n_importance = 0), else the dict with its defaults"""
+        if not self.importance:
+            return None
+        unknown = set(self.importance) - set(self._IMPORTANCE_KEYS)
+        if unknown:
+            raise ValueError(f"HotPathRenderer.importance: unknown keys {sorted(unknown)} ({', '.join(self._IMPORTANCE_KEYS)})")
+        args = dict(n_importance=0, det=False, jitter=None, eps=1e-5)
+        args.update(self.importance)
+        if int(args["n_importance"]) < 0:
+            raise ValueError(f"HotPathRenderer.importance: n_importance = {args['n_importance']}")
+        return args if int(args["n_importance"]) > 0 else None
+
+    def _importance_resample(self, args, density, seen, ray_indices, t_starts, t_ends, n_rays):
+        """The sampler's samples refined (resample.importance_sampling) -> (ray_indices, t_starts, t_ends, (ray_start, ray_cnt),
+        n_valid).  `seen`: the densities a pruning pass computed on the marched samples, if there was one; the survivors take
+        theirs through the sampler's src_index, so a render has one density pass."""
+        grid = self.occupancy_grid
+        packed = getattr(grid, "packed", None)
+        rs, rc = packed if packed is not None else ops.packed_info(ray_indices.long(), n_rays)
+        if seen:
+            src = getattr(grid, "src_index", None)
+            sigma = seen[0] if src is None else seen[0].index_select(0, src.long())
+        else:
+            sigma = density(t_starts, t_ends, ray_indices)
+        n_valid = getattr(grid, "n_valid", None)
+        out = resample.importance_sampling(rs.contiguous(), rc.contiguous(), t_starts.contiguous(), t_ends.contiguous(),
+                                           int(args["n_importance"]), sigmas=sigma, det=bool(args["det"]), jitter=args["jitter"],
+                                           eps=float(args["eps"]), n_valid=n_valid)
+        return out[0], out[1], out[2], (out[3], out[4]), (out[5] if n_valid is not None else None)
+
     # -- the hot path
     def render_rays(self, rays_o, rays_d, rays_t, rays_id, H, W, perturb=True, bg_color=None, ambient_ratio=1.0,
                     light_d=None, shading="albedo", real_view=True, cano=False, rays_depth=None, rays_mask=None,
@@ -217,22 +257,37 @@ class HotPathRenderer:
 
         single_frame = (not cano) and self.frame_batched and len(prefix) == 2 and prefix[0] == 1
         with torch.no_grad():
-            if self.prune:
-                unknown = set(self.prune) - {"alpha_thre", "early_stop_eps"}
-                if unknown:
-                    raise ValueError(f"HotPathRenderer.prune: unknown keys {sorted(unknown)} (alpha_thre, early_stop_eps)")
+            importance = self._importance_args()
+            density, seen = None, []
+            if self.prune or importance:
                 pre_slots = None
                 if not single_frame and not cano and self.frame_batched and len(prefix) == 2:      # one slot per batch row
                     pre_slots = (rays_t.view(*prefix)[:, 0].contiguous(),
                                  torch.arange(prefix[0], device=rays_o.device, dtype=torch.int32).repeat_interleave(prefix[1]))
+                density = self._density_fn(rays_o, rays_d, rays_t, cano, single_frame, pre_slots)
+            if self.prune:
+                unknown = set(self.prune) - {"alpha_thre", "early_stop_eps"}
+                if unknown:
+                    raise ValueError(f"HotPathRenderer.prune: unknown keys {sorted(unknown)} (alpha_thre, early_stop_eps)")
+                sigma_fn = density
+                if importance:          # the resampling below weighs the survivors with the densities of this pass
+
+                    def sigma_fn(t_starts, t_ends, ray_indices):
+                        seen.append(density(t_starts, t_ends, ray_indices))
+                        return seen[0]
+
                 ray_indices, t_starts_, t_ends_ = self.occupancy_grid.sampling(
-                    rays_o, rays_d, sigma_fn=self._density_fn(rays_o, rays_d, rays_t, cano, single_frame, pre_slots),
+                    rays_o, rays_d, sigma_fn=sigma_fn,
                     render_step_size=cfg["render"]["step_size"], alpha_thre=float(self.prune.get("alpha_thre", 0.0)),
                     stratified=True, cone_angle=0.0, early_stop_eps=float(self.prune.get("early_stop_eps", 0.0)))
             else:
                 ray_indices, t_starts_, t_ends_ = self.occupancy_grid.sampling(
                     rays_o, rays_d, sigma_fn=None, render_step_size=cfg["render"]["step_size"], alpha_thre=0,
                     stratified=True, cone_angle=0.0, early_stop_eps=0)
+            refined = None
+            if importance and ray_indices.shape[0] > 0:
+                refined = self._importance_resample(importance, density, seen, ray_indices, t_starts_, t_ends_, N)
+                ray_indices, t_starts_, t_ends_ = refined[:3]
         # per-sample light directions are only read by the shaded modes (model.py:515-531), and not at ambient_ratio = 1
         # (real-view steps), where the lambertian factor is exactly 1
         lit = shading != "albedo" and (ambient_ratio != 1 or shading in ("textureless", "normal"))
@@ -240,7 +295,7 @@ class HotPathRenderer:
             light_d = safe_normalize(rays_o + torch.randn(3, device=rays_o.device))      # morpheus.py:641
         M_samples = ray_indices.shape[0]
         # fixed-capacity sampling (occgrid.OccupancyGrid.sample_capacity): only the first n_valid packed entries are samples
-        n_valid = getattr(self.occupancy_grid, "n_valid", None)
+        n_valid = getattr(self.occupancy_grid, "n_valid", None) if refined is None else refined[4]
         valid = None if n_valid is None else (torch.arange(M_samples, device=rays_o.device) < n_valid)
 
         def l1_mean(a, b):
@@ -267,6 +322,8 @@ class HotPathRenderer:
         if xyzs is not None:
             self.occupancy_grid.xyz = None             # one use: it belongs to the sampling call above
         packed = getattr(self.occupancy_grid, "packed", None)    # (ray_start, ray_cnt) of the sampling call above
+        if refined is not None:                        # the refined samples stand where the sampler's stood
+            xyzs, packed = None, refined[3]
         ray_start, ray_cnt = packed if packed is not None else ops.packed_info(ri_long(), N)
         if xyzs is None or rays_o.requires_grad or rays_d.requires_grad:   # pose optimisation: positions carry gradients
             # xyz = o[ri] + d[ri] * (ts + te) / 2 (morpheus.py:644-647) as one launch; its backward is a per-ray segment sum
