@@ -1107,6 +1107,37 @@ int mh_prep_frames(const uint8_t *rgb, const uint16_t *depth, const uint8_t *mas
  *     hi on the three axes; none: the coarsest); cell = clamp(floor((x - lo) / (hi - lo) * R), 0, R - 1).
  *   mh_est_march_cap, given the diagonal of the coarsest box, = (int)(min(diagonal, far_plane - near_plane) / step) + 4,
  *   0 for bad arguments: the slot row a ray of unit-or-longer direction cannot overflow (every step is >= `step` long).
+ *
+ * mh_est_traverse_slots: the second, opt-in placement (OccGridEstimator(traversal = "dda")): the grid is walked cell by cell, an
+ *   empty cell is jumped to its exit and stepping starts again where the next occupied cell is entered.  Same arguments, argument
+ *   rules, slot rows, counts and overflow flag as mh_est_march_slots; mh_march_pack packs the rows.  This is this build's statement
+ *   of nerfacc 0.5.x's traverse_grids as RECALLED, agreement unverified, with the one departure named in point 5.  fp32, one
+ *   IEEE rounding per operation, no contraction; tests/traverse_oracle.py restates it and the kernel equals that bit for bit.
+ *   1. Clip, miss rule, planes, per-ray limits: slab_clip against the coarsest box, the first two points of mh_est_march_slots.
+ *      Then t_near = t_near + u * step: the jitter shifts the near end only; later runs start at cell entries, unjittered.
+ *   2. Level segments.  For every finer level l, coarse to fine: (a_l, b_l) = slab_clip(o, d, box_l), then
+ *      a_l = min(max(a_l, a_{l+1}), b_{l+1}) and b_l = max(min(b_l, b_{l+1}), a_l); a level that is a miss has a_l = b_l =
+ *      b_{l+1}; a_{L-1}, b_{L-1} = t_near, t_far.  The ray is the segments [a_{L-1}, a_{L-2}] at level L - 1, ..., [a_0, b_0] at
+ *      level 0, [b_0, b_1] at level 1, ..., [b_{L-2}, b_{L-1}] at level L - 1; a segment with e <= s is skipped.
+ *   3. Cell spans of a segment [s, e] at level l.  Start cell c_a = clamp(floor(((o_a + d_a s) - lo_a) / (hi_a - lo_a) * R_a), 0,
+ *      R_a - 1).  Plane k of axis a = lo_a + ((float)k / (float)R_a) * (hi_a - lo_a): closed form from the integer index, never an
+ *      accumulated increment.  Exit of the current cell on axis a = (plane(c_a + (d_a > 0)) - o_a) / d_a, +inf when d_a == 0.  The
+ *      span ends at x = max(min(min(min(exit_x, exit_y), exit_z), e), start).  x >= e: the segment is done.  Otherwise the first
+ *      axis (x, y, z order) whose exit is the minimum is stepped; an index outside [0, R_a - 1] ends the segment.  A segment has
+ *      at most Rx + Ry + Rz + 3 spans: the walk is bounded by that count, not by a comparison of times alone.
+ *   4. Runs.  A span with end <= start is ignored: it neither extends nor breaks a run.  A run is a maximal sequence of
+ *      consecutive occupied spans (binary[l, c] != 0), across segment and level changes, from the first span's start A to the
+ *      last span's end B.
+ *   5. Samples of a run start at A' = max(A, te of the last sample of this ray).  cone_angle == 0: ts_k = A' + (float)k * step,
+ *      te_k = A' + (float)(k + 1) * step (te_k and ts_{k+1} are the same bits).  cone_angle > 0: ts_0 = A', dt_k = min(max(ts_k *
+ *      cone_angle, step), 1e10f), te_k = ts_k + dt_k, ts_{k+1} = te_k.  A sample is kept while (ts_k + te_k) / 2.0f < B.  te is NOT
+ *      clamped to B or t_far: a run's last sample may reach up to half a step past its end.
+ *      max(A, last te) is a deliberate departure from the recalled rule, which restarts at the cell entry A: behind an empty gap
+ *      shorter than half a step that rule lets two samples overlap, and mh_sample_pdf / mh_resample_packed and the compositor
+ *      assume t_starts[k] >= t_ends[k-1] inside a ray.
+ *   Slot row: every sample is at least `step` long, the samples are disjoint and every ts lies in [t_near, t_far), so
+ *   mh_est_march_cap bounds the row exactly as it does for the lattice; ray_cnt = min(n, cap), nothing is written past cap and
+ *   the flag is set when a ray has more than cap samples.
  * The update, no device->host read:
  *   mh_est_occ_count / mh_est_occ_pack: one wavefront per chunk of mh_est_occ_chunk cells; chunk_cnt int32 [L, n_chunks],
  *     n_chunks = ceil(cells / chunk).  The caller scans each level's row into chunk_start (exclusive); pack writes the occupied
@@ -1132,6 +1163,10 @@ int mh_est_march_slots(const float *rays_o, const float *rays_d, const float *ji
                        int32_t N, float step, float cone_angle, float near_plane, float far_plane, const float *aabbs,
                        int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, const uint8_t *binary, int32_t cap, int32_t *ray_cnt,
                        float *slot_ts, float *slot_te, int32_t *overflow, void *stream);
+int mh_est_traverse_slots(const float *rays_o, const float *rays_d, const float *jitter, const float *t_min, const float *t_max,
+                          int32_t N, float step, float cone_angle, float near_plane, float far_plane, const float *aabbs,
+                          int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, const uint8_t *binary, int32_t cap, int32_t *ray_cnt,
+                          float *slot_ts, float *slot_te, int32_t *overflow, void *stream);
 int mh_est_occ_count(const uint8_t *binary, int32_t L, int64_t cells, int32_t *chunk_cnt, void *stream);
 int mh_est_occ_pack(const uint8_t *binary, int32_t L, int64_t cells, const int32_t *chunk_start, int32_t *occ_list,
                     void *stream);

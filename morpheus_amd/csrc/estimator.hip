@@ -16,6 +16,7 @@
 //      midpoint (lo <= x < hi on the three axes; none: the coarsest), cell = clamp(floor((x - lo) / (hi - lo) * R), 0, R - 1).
 // With one level, a centred cubic box and default planes these are the operations of march_wave_kernel (csrc/sampler.hip), bit
 // for bit: both kernels run csrc/march.h's march_slots, which says why the cube marched as a box rounds the same.
+// The opt-in second placement, the cell-by-cell traversal, shares points 1 - 3 and is stated above est_traverse_kernel.
 #include "common.h"
 
 // no FMA contraction: every mul / add / div below is one IEEE round-to-nearest operation (see csrc/sampler.hip)
@@ -43,6 +44,238 @@ __global__ __launch_bounds__(256) void est_march_kernel(const float *__restrict_
     __syncthreads();
     march_slots<true>(rays_o, rays_d, jitter, N, step, MarchLimits{t_min, t_max, near_plane, far_plane, cone}, boxes, L, R, binary,
                       cap, ray_cnt, slot_ts, slot_te, overflow);
+}
+
+// ---- cell-by-cell traversal: the opt-in second placement (OccGridEstimator(traversal = "dda")) ---------------------------
+// The definition is points 1 - 5 under mh_est_traverse_slots in include/morpheus_hip.h, restated in fp32 by
+// tests/traverse_oracle.py; this build's statement of nerfacc 0.5.x's traverse_grids as recalled, agreement unverified, with one
+// deliberate departure (a run's samples start at max(run start, the ray's last te), so that samples never overlap).
+// One wavefront per ray, the slot-row contract of march_slots.  A trip is 64 cell spans.  The walk from span to span is a
+// recurrence (which axis steps depends on the exits before), so -- as march_slots does for cone steps -- every lane walks the
+// trip's 64 spans in lockstep and keeps its own: the walk's state is wave-uniform (the ray is read through readfirstlane, the
+// segment boundaries through wave_read).  A step needs one new exit, of the stepped axis; exits are closed form in the cell
+// index, so once a trip and segment lane i forms the exit of the i-th next cell of every axis and the walk only reads them: no
+// division sits in the chain.  The 64 occupancy bytes of a trip are then in flight at once, one a lane, not a dependent-load
+// chain.  Two ballots (spans wider than zero, occupied spans) give the runs; a run is closed by the first empty span behind it,
+// in this trip or a later one (the open run's start and end, the last te, the segment and the cell carry over).  A closed run's
+// samples are written a lane a sample, 64 a round: the closed form for cone_angle == 0, march_slots' lockstep recurrence
+// otherwise; the kept ones are a prefix (midpoints do not decrease), compacted by ballot + rank behind the n samples the ray
+// already has.
+__device__ __forceinline__ float trav_exit(int c, float o, float d, float lo, float ext, int res) {
+    if (d == 0.f) return INFINITY;
+    const int k = c + (d > 0.f ? 1 : 0);
+    const float plane = lo + ((float)k / (float)res) * ext;      // closed form from the integer index
+    return (plane - o) / d;
+}
+
+__global__ __launch_bounds__(256) void est_traverse_kernel(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                                           const float *__restrict__ jitter, const float *__restrict__ t_min,
+                                                           const float *__restrict__ t_max, int N, float step, float cone,
+                                                           float near_plane, float far_plane, const float *__restrict__ aabbs,
+                                                           int L, EstRes R, const uint8_t *__restrict__ binary, int cap,
+                                                           int32_t *__restrict__ ray_cnt, float *__restrict__ slot_ts,
+                                                           float *__restrict__ slot_te, int32_t *__restrict__ overflow) {
+    __shared__ float boxes[EST_MAX_LEVELS * 6];
+    if ((int)threadIdx.x < L * 6) boxes[threadIdx.x] = aabbs[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int r = __builtin_amdgcn_readfirstlane(wave_ray());
+    if (r >= N) return;
+    float o[3], d[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        o[a] = rays_o[r * 3 + a];
+        d[a] = rays_d[r * 3 + a];
+    }
+    // 1. clip, miss rule, planes, per-ray limits: march_slots' statements; the jitter moves the near end only
+    float tn, tf;
+    slab_clip(o, d, boxes + (L - 1) * 6, &tn, &tf);
+    if (near_plane > tn) tn = near_plane;
+    if (t_min) {
+        const float v = t_min[r];
+        if (v > tn) tn = v;
+    }
+    if (far_plane < tf) tf = far_plane;
+    if (t_max) {
+        const float v = t_max[r];
+        if (v < tf) tf = v;
+    }
+    tn = tn + (jitter ? jitter[r] : 0.0f) * step;
+    // 2. level segments: lane i holds boundary T_i of (a_{L-1}, ..., a_0, b_0, ..., b_{L-1}); segment j = [T_j, T_{j+1}] at level
+    // |L - 1 - j|
+    const int nseg = 2 * L - 1;
+    float T = 0.f;
+    {
+        float a_up = tn, b_up = tf;
+        if (lane == 0) T = tn;
+        if (lane == nseg) T = tf;
+        for (int l = L - 2; l >= 0; l--) {
+            float ca, cb;
+            slab_clip(o, d, boxes + l * 6, &ca, &cb);
+            float al = b_up, bl = b_up;                              // a miss (a hit has t_far > t_near >= 0)
+            if (cb != 0.f) {
+                al = fminf(fmaxf(ca, a_up), b_up);
+                bl = fmaxf(fminf(cb, b_up), al);
+            }
+            if (lane == L - 1 - l) T = al;
+            if (lane == L + l) T = bl;
+            a_up = al;
+            b_up = bl;
+        }
+    }
+    const int res[3] = {R.x, R.y, R.z};
+    const int span_max = R.x + R.y + R.z + 3;
+    float *row_s = slot_ts + (int64_t)r * cap, *row_e = slot_te + (int64_t)r * cap;
+    const bool coned = cone > 0.f;
+    // the walk (wave-uniform): segment j, `fresh`: its first span is still to be set up; cell c, exits t, span start cur, segment
+    // end e, spans the segment may still take
+    int j = 0, lvl = 0, left = 0, c[3] = {0, 0, 0};
+    bool fresh = true;
+    float t[3] = {INFINITY, INFINITY, INFINITY}, lo[3] = {0.f, 0.f, 0.f}, ext[3] = {0.f, 0.f, 0.f}, cur = 0.f, e = 0.f;
+    // The exit of a cell is closed form in its index, so the two divisions need not sit in the walk's chain: lane i holds, per
+    // axis, the exit of the i-th next cell from the table's base cell (the same statement on the same integer index, so the same
+    // bits), `ahead` counts the steps taken on the axis since, and the walk reads its next exit with wave_read.  A trip takes at
+    // most 64 steps; the tables are formed again at every trip and at every segment.
+    const int dir[3] = {d[0] > 0.f ? 1 : -1, d[1] > 0.f ? 1 : -1, d[2] > 0.f ? 1 : -1};
+    float tab[3] = {INFINITY, INFINITY, INFINITY};
+    int ahead[3] = {0, 0, 0};
+    auto exits_from_here = [&]() {
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            tab[a] = trav_exit(c[a] + lane * dir[a], o[a], d[a], lo[a], ext[a], res[a]);
+            ahead[a] = 0;
+            t[a] = wave_read(tab[a], 0);
+        }
+    };
+    // the samples (wave-uniform): n so far, the last te, the open run [run_a, run_b]
+    int n = 0;
+    bool open = false, over = false;
+    float last_te = -INFINITY, run_a = 0.f, run_b = 0.f;
+
+    // 5. the samples of the closed run [run_a, run_b]
+    auto emit = [&]() {
+        const float a1 = fmaxf(run_a, last_te);
+        float carry = a1;                                            // cone steps: ts of the round's first sample
+        for (int k0 = 0;; k0 += 64) {
+            float ts, te;
+            if (coned) {
+                float tt = carry, dt = step;
+                ts = tt;
+                for (int i = 0; i < 64; i++) {
+                    const float di = fminf(fmaxf(tt * cone, step), 1e10f);
+                    if (i == lane) {
+                        ts = tt;
+                        dt = di;
+                    }
+                    tt = tt + di;
+                }
+                carry = tt;
+                te = ts + dt;
+            } else {
+                ts = a1 + (float)(k0 + lane) * step;
+                te = a1 + (float)(k0 + lane + 1) * step;
+            }
+            const bool keep = (ts + te) / 2.0f < run_b;
+            const unsigned long long mask = __ballot(keep);
+            const int pos = n + wave_rank(mask, lane), kept = __popcll(mask);
+            if (keep && pos < cap) {
+                row_s[pos] = ts;
+                row_e[pos] = te;
+            }
+            if (kept) last_te = wave_read(te, kept - 1);             // the kept ones are lanes 0 .. kept - 1
+            n += kept;
+            if (n > cap) over = true;                                // the slot row is full: the host marches again
+            if (over || mask != ~0ull) break;
+        }
+    };
+
+    while (j < nseg && !over) {
+        // 3. the trip's 64 spans in lockstep; a lane keeps span `lane` (sp_e <= sp_s: no span, or one of no width)
+        float sp_s = 0.f, sp_e = 0.f;
+        int sp_cell = 0;
+        if (!fresh) exits_from_here();
+        for (int i = 0; i < 64; i++) {
+            if (fresh) {
+                float s = 0.f;
+                for (; j < nseg; j++) {                              // a segment with e <= s is skipped
+                    s = wave_read(T, j);
+                    e = wave_read(T, j + 1);
+                    if (e > s) break;
+                }
+                if (j >= nseg) break;
+                lvl = j < L - 1 ? L - 1 - j : j - (L - 1);
+                const float *b = boxes + lvl * 6;
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    lo[a] = b[a];
+                    ext[a] = b[3 + a] - b[a];
+                    const float x = o[a] + d[a] * s;
+                    const float u = (x - lo[a]) / ext[a];
+                    c[a] = min(max((int)floorf(u * (float)res[a]), 0), res[a] - 1);
+                }
+                exits_from_here();
+                cur = s;
+                left = span_max;
+                fresh = false;
+            }
+            const float m = fminf(fminf(t[0], t[1]), t[2]);
+            const float x = fmaxf(fminf(m, e), cur);
+            if (i == lane) {
+                sp_s = cur;
+                sp_e = x;
+                sp_cell = ((lvl * R.x + c[0]) * R.y + c[1]) * R.z + c[2];
+            }
+            left--;
+            if (x >= e) {
+                fresh = true;
+            } else {
+                const int ax = t[0] == m ? 0 : (t[1] == m ? 1 : 2);  // the first axis whose exit is the minimum
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+                    if (a == ax) {
+                        c[a] += dir[a];
+                        ahead[a]++;
+                        if (c[a] < 0 || c[a] >= res[a] || left == 0)
+                            fresh = true;
+                        else
+                            t[a] = wave_read(tab[a], ahead[a] & 63);     // 64 only behind the trip's last span: formed again
+                    }
+            }
+            if (fresh) j++;
+            cur = x;
+        }
+        // 4. runs: the occupied spans among those wider than zero
+        const bool wide = sp_e > sp_s;
+        const bool occ = wide && binary[sp_cell] != 0;
+        unsigned long long v = __ballot(wide), oc = __ballot(occ);
+        while (v && !over) {
+            if (!open) {
+                if (!oc) break;
+                const int i = __builtin_ctzll(oc);
+                run_a = wave_read(sp_s, i);
+                run_b = wave_read(sp_e, i);
+                open = true;
+                const unsigned long long upto = (2ull << i) - 1ull;  // lanes 0 .. i
+                v &= ~upto;
+                oc &= ~upto;
+            } else {
+                const unsigned long long empty = v & ~oc;
+                const unsigned long long more = empty ? v & ((1ull << __builtin_ctzll(empty)) - 1ull) : v;
+                if (more) run_b = wave_read(sp_e, 63 - __builtin_clzll(more));
+                if (!empty) break;                                   // still open behind the trip's last span
+                emit();
+                open = false;
+                const unsigned long long upto = (2ull << __builtin_ctzll(empty)) - 1ull;
+                v &= ~upto;
+                oc &= ~upto;
+            }
+        }
+    }
+    if (open && !over) emit();
+    if (lane == 0) {
+        ray_cnt[r] = n < cap ? n : cap;
+        if (n > cap) atomicOr(overflow, 1);
+    }
 }
 
 // ---- occupied list: each level's occupied cells in index order, count on the device -------------------------------------
@@ -250,7 +483,10 @@ extern "C" int32_t mh_est_occ_chunk(void) { return EST_CHUNK; }
 extern "C" int32_t mh_est_max_partials(void) { return EST_MAX_PARTIALS; }
 
 // steps a ray of unit-or-longer direction can take: every step is at least `step` long and lies inside both the coarsest
-// box (its longest chord is the diagonal) and [near_plane, far_plane]
+// box (its longest chord is the diagonal) and [near_plane, far_plane].
+// The same bound holds the traversal's slot row (mh_est_traverse_slots): its samples are at least `step` long as well, they are
+// disjoint (a run starts at max(run start, the last te)), every ts >= t_near and every ts < t_far (a kept sample's midpoint lies
+// before its run's end <= t_far), so at most (t_far - t_near) / step + 1 of them fit -- inside the + 4.
 extern "C" int32_t mh_est_march_cap(float step, float diagonal, float near_plane, float far_plane) {
     if (!(step > 0.f) || !(diagonal > 0.f)) return 0;
     double len = (double)diagonal;
@@ -261,22 +497,41 @@ extern "C" int32_t mh_est_march_cap(float step, float diagonal, float near_plane
     return (int32_t)n + 4;
 }
 
-extern "C" int mh_est_march_slots(const float *rays_o, const float *rays_d, const float *jitter, const float *t_min,
-                                  const float *t_max, int32_t N, float step, float cone_angle, float near_plane,
-                                  float far_plane, const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz,
-                                  const uint8_t *binary, int32_t cap, int32_t *ray_cnt, float *slot_ts, float *slot_te,
-                                  int32_t *overflow, void *stream) {
+// the two placements share the argument list, the argument rules and the launch shape
+template <typename Kernel>
+static inline int est_slots_launch(Kernel kernel, const float *rays_o, const float *rays_d, const float *jitter, const float *t_min,
+                                   const float *t_max, int32_t N, float step, float cone_angle, float near_plane, float far_plane,
+                                   const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz, const uint8_t *binary,
+                                   int32_t cap, int32_t *ray_cnt, float *slot_ts, float *slot_te, int32_t *overflow, void *stream) {
     if (N == 0) return MH_OK;
     if (!rays_o || !rays_d || !aabbs || !binary || !ray_cnt || !slot_ts || !slot_te || !overflow || N < 0 ||
         !est_grid_ok(L, Rx, Ry, Rz) || !(step > 0.f) || !(cone_angle >= 0.f) || cap <= 0 || near_plane != near_plane ||
         far_plane != far_plane)
         return MH_ERR_ARG;
     const EstRes R = {Rx, Ry, Rz};
-    hipLaunchKernelGGL(est_march_kernel, dim3((N + 3) / 4), dim3(256), 0, mh_stream(stream), rays_o, rays_d, jitter, t_min,
-                       t_max, (int)N, step, cone_angle, near_plane, far_plane, aabbs, (int)L, R, binary, (int)cap, ray_cnt,
-                       slot_ts, slot_te, overflow);
+    hipLaunchKernelGGL(kernel, dim3((N + 3) / 4), dim3(256), 0, mh_stream(stream), rays_o, rays_d, jitter, t_min, t_max, (int)N,
+                       step, cone_angle, near_plane, far_plane, aabbs, (int)L, R, binary, (int)cap, ray_cnt, slot_ts, slot_te,
+                       overflow);
     MH_CHECK_LAUNCH();
     return MH_OK;
+}
+
+extern "C" int mh_est_march_slots(const float *rays_o, const float *rays_d, const float *jitter, const float *t_min,
+                                  const float *t_max, int32_t N, float step, float cone_angle, float near_plane,
+                                  float far_plane, const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz,
+                                  const uint8_t *binary, int32_t cap, int32_t *ray_cnt, float *slot_ts, float *slot_te,
+                                  int32_t *overflow, void *stream) {
+    return est_slots_launch(est_march_kernel, rays_o, rays_d, jitter, t_min, t_max, N, step, cone_angle, near_plane, far_plane,
+                            aabbs, L, Rx, Ry, Rz, binary, cap, ray_cnt, slot_ts, slot_te, overflow, stream);
+}
+
+extern "C" int mh_est_traverse_slots(const float *rays_o, const float *rays_d, const float *jitter, const float *t_min,
+                                     const float *t_max, int32_t N, float step, float cone_angle, float near_plane,
+                                     float far_plane, const float *aabbs, int32_t L, int32_t Rx, int32_t Ry, int32_t Rz,
+                                     const uint8_t *binary, int32_t cap, int32_t *ray_cnt, float *slot_ts, float *slot_te,
+                                     int32_t *overflow, void *stream) {
+    return est_slots_launch(est_traverse_kernel, rays_o, rays_d, jitter, t_min, t_max, N, step, cone_angle, near_plane, far_plane,
+                            aabbs, L, Rx, Ry, Rz, binary, cap, ray_cnt, slot_ts, slot_te, overflow, stream);
 }
 
 static inline unsigned est_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }

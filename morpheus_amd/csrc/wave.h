@@ -158,6 +158,12 @@ __device__ __forceinline__ int wave_rank(unsigned long long mask, int lane) {
     return __popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// ---- broadcast: lane `src`'s value in every lane; `src` (0 .. 63) must be the same in every lane ------------------------
+// a v_readlane, not a shuffle: the result is wave-uniform to the compiler as well, so what is computed from it stays scalar
+__device__ __forceinline__ float wave_read(float v, int src) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
 // ---- one wavefront per ray, four rays per 256-thread block --------------------------------------------------------------
 // the ray (row, chunk) of this wavefront; the caller returns when it is past the end, the whole wavefront together
 __device__ __forceinline__ int wave_ray() { return blockIdx.x * 4 + (threadIdx.x >> 6); }

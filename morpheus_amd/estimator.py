@@ -9,9 +9,21 @@ never reads the device from the host.
 nerfacc is third-party, un-vendored and not on any machine this project uses.  The class name, the buffers (`resolution` int32
 [3], `aabbs` [levels,6], `occs` [levels * cells_per_lvl], `binaries` bool [levels,Rx,Ry,Rz]), the signatures and defaults of
 `sampling`, `update_every_n_steps` and `mark_invisible_cells`, and the update rule are nerfacc 0.5.x's as RECALLED from its public
-source: recalled, agreement unverified.  The interval placement is NOT nerfacc's DDA cell traversal: it stays this build's
-fixed-lattice definition (csrc/march.h, the one march behind both classes), extended by levels, planes and cone steps --
-include/morpheus_hip.h states it, tests/estimator_oracle.py restates it in fp32 and the kernels equal that bit for bit.
+source: recalled, agreement unverified.
+
+Two interval placements, chosen by the attribute `traversal` (not a buffer: `state_dict()` does not carry it):
+  * "lattice" (the default): this build's fixed-lattice definition (csrc/march.h, the one march behind both classes), extended by
+    levels, planes and cone steps: every ray walks t0 + k * step from clip entry to clip exit and keeps the steps whose midpoint
+    lies in an occupied cell -- tests/estimator_oracle.py restates it in fp32;
+  * "dda": the grid is walked cell by cell (mh_est_traverse_slots), empty cells are jumped to their exit and stepping starts
+    again at the entry of the next occupied cell, so where a sample lies inside an occupied region depends on where the ray
+    entered the REGION, not the clip box.  The rule is this build's statement of nerfacc's traverse_grids as recalled, agreement
+    unverified, with one deliberate departure: a run of occupied cells starts its samples at max(its entry, the end of the ray's
+    last sample), where the recalled rule restarts at the entry and lets two samples overlap behind an empty gap shorter than
+    half a step -- `resample` and the compositor assume t_starts[k] >= t_ends[k-1] inside a ray.  tests/traverse_oracle.py
+    restates it in fp32.
+include/morpheus_hip.h states both and the kernels equal the restatements bit for bit.  `sampling`'s signature is nerfacc's and
+stays so: `sampling_as(traversal, ...)` is `sampling` with the placement of that one call given.
 
 `occgrid.OccupancyGrid` stays what the reference's own call uses.  Differences from it:
   * without a density function (`sigma_fn` / `alpha_fn`) `alpha_thre` and `early_stop_eps` are IGNORED, as nerfacc does --
@@ -41,6 +53,13 @@ from .occgrid import PackedSampling
 __all__ = ["OccGridEstimator", "level_aabbs"]
 
 MAX_LEVELS = 16
+TRAVERSALS = ("lattice", "dda")
+
+
+def _traversal(value) -> str:
+    if value not in TRAVERSALS:
+        raise ValueError(f"OccGridEstimator: traversal is one of {TRAVERSALS}, got {value!r}")
+    return value
 
 
 def level_aabbs(roi_aabb, levels: int) -> np.ndarray:
@@ -76,7 +95,17 @@ class OccGridEstimator(PackedSampling, torch.nn.Module):
         self._res = tuple(res)
         self._set_diagonal(aabbs)
         self.thre: Optional[torch.Tensor] = None     # device scalar: the threshold of the last update
+        self._traversal = "lattice"
         self._init_sampling_state()
+
+    @property
+    def traversal(self) -> str:
+        """the interval placement of `sampling`: "lattice" (the default) or "dda"; any other value raises ValueError"""
+        return self._traversal
+
+    @traversal.setter
+    def traversal(self, value):
+        self._traversal = _traversal(value)
 
     def _set_diagonal(self, aabbs):
         # the slot-row bound needs the coarsest diagonal on the HOST: kept from construction / loading, never read back
@@ -99,7 +128,8 @@ class OccGridEstimator(PackedSampling, torch.nn.Module):
         with transmittance under early_stop_eps or opacity under min(alpha_thre, mean of the non-negative occs) are dropped
         (ops.visibility_prune) and `self.src_index` holds the marched position of every returned sample.
         Without a density function the two thresholds are ignored, as nerfacc does -- `OccupancyGrid.sampling` raises there.
-        t_min / t_max: float32 [n_rays] on the device.  `sample_capacity` set: fixed-length results and no host read."""
+        t_min / t_max: float32 [n_rays] on the device.  `sample_capacity` set: fixed-length results and no host read.
+        The placement is `self.traversal`; everything else here works alike on both."""
         if sigma_fn is not None and alpha_fn is not None:
             raise ValueError("sampling: give sigma_fn or alpha_fn, not both")
         if not (0.0 <= alpha_thre <= 1.0) or not (0.0 <= early_stop_eps <= 1.0):
@@ -110,13 +140,22 @@ class OccGridEstimator(PackedSampling, torch.nn.Module):
             raise MorpheusHipError("OccGridEstimator.sampling runs on an MI355X only (rays on %s, estimator on %s); there is "
                                    "no CPU path" % (rays_o.device, self.occs.device))
 
+        rays = ops.est_traverse_rays if self._traversal == "dda" else ops.est_march_rays
+
         def march(u, capacity):
-            return ops.est_march_rays(rays_o, rays_d, u, float(render_step_size), self.aabbs, self.binaries.view(torch.uint8),
-                                      self._diagonal, float(cone_angle), float(near_plane), float(far_plane), t_min, t_max,
-                                      capacity=capacity)
+            return rays(rays_o, rays_d, u, float(render_step_size), self.aabbs, self.binaries.view(torch.uint8), self._diagonal,
+                        float(cone_angle), float(near_plane), float(far_plane), t_min, t_max, capacity=capacity)
 
         return self._sample(rays_o.shape[0], rays_o.device, stratified, march, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
                             lambda cap: ops.est_threshold(self.occs, cap))
+
+    def sampling_as(self, traversal: str, rays_o, rays_d, **kw):
+        """`sampling(rays_o, rays_d, **kw)` with the placement `traversal` for this one call; the attribute is left as it was"""
+        keep, self._traversal = self._traversal, _traversal(traversal)
+        try:
+            return self.sampling(rays_o, rays_d, **kw)
+        finally:
+            self._traversal = keep
 
     # -- occupancy update -------------------------------------------------------------------------
     def make_draws(self, warmup: bool):

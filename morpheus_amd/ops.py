@@ -659,8 +659,8 @@ def _ray_jitter(jitter, n_rays: int):
 
 # ---- the march: slot rows, a scan of the counts, pack (csrc/march.h behind both slots entries) ---------------------------
 def _march_slots(entry, head, N: int, tail, cap: int, dev, call=None):
-    """One launch of a slots entry (mh_march_slots / mh_est_march_slots: the arguments are head, N, tail, cap and the four
-    outputs) -> (cnt_ovf int32 [N + 1] = [ray_cnt | slot-row overflow flag], rows fp32 [2, N, cap])."""
+    """One launch of a slots entry (mh_march_slots / mh_est_march_slots / mh_est_traverse_slots: the arguments are head, N, tail,
+    cap and the four outputs) -> (cnt_ovf int32 [N + 1] = [ray_cnt | slot-row overflow flag], rows fp32 [2, N, cap])."""
     cnt_ovf = torch.zeros(N + 1, dtype=torch.int32, device=dev)
     rows = torch.empty(2, N, cap, device=dev)
     (call or _timed)(entry, *head, N, *tail, cap, ptr(cnt_ovf), ptr(rows[0]), ptr(rows[1]), cnt_ovf.data_ptr() + 4 * N)
@@ -774,12 +774,9 @@ def _est_grid(aabbs, binary):
     return (L,) + tuple(int(r) for r in binary.shape[1:])
 
 
-def est_march_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal: float, cone_angle: float = 0.0,
-                   near_plane: float = 0.0, far_plane: float = 1e10, t_min=None, t_max=None, capacity: Optional[int] = None):
-    """The estimator's marcher (mh_est_march_slots + mh_march_pack; the definition is in include/morpheus_hip.h).
-    capacity None: march_rays' ragged result (ray_idx, t_starts, t_ends, ray_start, ray_cnt), one host read of M and the
-    doubling retry of an overflowing slot row.  With a capacity: march_rays_capped's seven results, no host read.
-    diagonal: of the coarsest box, a HOST number (the caller keeps it from construction)."""
+def _est_slots_rays(who: str, entry: str, rays_o, rays_d, jitter, step, aabbs, binary, diagonal, cone_angle, near_plane, far_plane,
+                    t_min, t_max, capacity):
+    """the estimator's two placements behind one argument list: `entry` fills the slot rows, mh_march_pack packs them"""
     require_gpu(rays_o, rays_d, jitter, t_min, t_max)
     lib = _lib.load()
     L, Rx, Ry, Rz = _est_grid(aabbs, binary)
@@ -790,12 +787,31 @@ def est_march_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal:
     step, cone, near, far = float(step), float(cone_angle), float(near_plane), float(far_plane)
     cap = int(lib.mh_est_march_cap(step, float(diagonal), near, far))
     if cap <= 0:
-        raise ValueError(f"est_march_rays: step {step}, diagonal {diagonal}, planes [{near}, {far}] give no slot row")
+        raise ValueError(f"{who}: step {step}, diagonal {diagonal}, planes [{near}, {far}] give no slot row")
     head = (ptr(o), ptr(d), ptr(j), ptr(tmn), ptr(tmx))
     tail = (step, cone, near, far, ptr(aabbs), L, Rx, Ry, Rz, ptr(binary))
     if capacity is not None:
-        return _march_capped("mh_est_march_slots", head, N, tail, cap, dev, capacity)
-    return _march_ragged("est_march_rays", "mh_est_march_slots", head, N, tail, cap, dev)
+        return _march_capped(entry, head, N, tail, cap, dev, capacity)
+    return _march_ragged(who, entry, head, N, tail, cap, dev)
+
+
+def est_march_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal: float, cone_angle: float = 0.0,
+                   near_plane: float = 0.0, far_plane: float = 1e10, t_min=None, t_max=None, capacity: Optional[int] = None):
+    """The estimator's marcher (mh_est_march_slots + mh_march_pack; the definition is in include/morpheus_hip.h).
+    capacity None: march_rays' ragged result (ray_idx, t_starts, t_ends, ray_start, ray_cnt), one host read of M and the
+    doubling retry of an overflowing slot row.  With a capacity: march_rays_capped's seven results, no host read.
+    diagonal: of the coarsest box, a HOST number (the caller keeps it from construction)."""
+    return _est_slots_rays("est_march_rays", "mh_est_march_slots", rays_o, rays_d, jitter, step, aabbs, binary, diagonal, cone_angle,
+                           near_plane, far_plane, t_min, t_max, capacity)
+
+
+def est_traverse_rays(rays_o, rays_d, jitter, step: float, aabbs, binary, diagonal: float, cone_angle: float = 0.0,
+                      near_plane: float = 0.0, far_plane: float = 1e10, t_min=None, t_max=None, capacity: Optional[int] = None):
+    """The estimator's cell-by-cell traversal (mh_est_traverse_slots + mh_march_pack; the definition is in
+    include/morpheus_hip.h): est_march_rays' arguments and results, the samples placed run by run from the entry of every
+    occupied stretch of cells instead of on the lattice from the clip entry."""
+    return _est_slots_rays("est_traverse_rays", "mh_est_traverse_slots", rays_o, rays_d, jitter, step, aabbs, binary, diagonal,
+                           cone_angle, near_plane, far_plane, t_min, t_max, capacity)
 
 
 def est_occupied_list(binary):

@@ -8,7 +8,10 @@ inside every repetition):
             against OccGridEstimator.update_every_n_steps (levels = 1); the grid is a ball of radius 0.7 in [-1.01, 1.01]^3;
   sampling  --rays rays of a synthetic frame at default arguments, OccupancyGrid.sampling against OccGridEstimator.sampling on the
             same binaries (the two return the same samples: the count is reported once);
-  cone      OccGridEstimator(levels = 4).sampling(cone_angle = 0.004) on the same rays, every level holding the ball.
+  cone      OccGridEstimator(levels = 4).sampling(cone_angle = 0.004) on the same rays, every level holding the ball;
+  traversal the estimator's two placements on the same rays and binaries, alternating: sampling() on the lattice against
+            sampling() with traversal = "dda" (cell-by-cell, mh_est_traverse_slots); the sample counts of both are reported;
+  traversal_cone  the four-level cone case in both placements.
 
 EXPECTATION (written before the first run):
   * update: OccupancyGrid's refresh runs a top-k of res^3 / 4 keys over res^3 random keys; the estimator replaces it by a count,
@@ -18,6 +21,23 @@ EXPECTATION (written before the first run):
     boxes.  Within a few percent of each other, both bound by the host read of the sample count.
   * cone: steps grow past t = step / cone_angle, so fewer steps than the fixed lattice, but every lane walks the 64 steps of a trip:
     about 450 VALU operations per trip and wave on top of the occupancy read.  Same order as the default call.
+  * traversal (written before its first run).  A ray of the synthetic frame crosses the box on a chord of 2 to 3.5, the ball on at
+    most 1.4.  Lattice at step 0.005: 400 to 700 steps, one occupancy byte each (400 - 700 bytes a ray, three steps to a cell, so
+    a third of them new cache lines at worst), 7 to 11 trips of some 60 VALU operations.  Traversal: one byte per cell, 130 to
+    220 a ray, in 2 to 4 trips -- but a trip walks its 64 spans in lockstep, about 35 VALU operations a span (two IEEE divisions
+    for the stepped axis' exit), some 2300 a trip, plus about 15 per round of 64 samples: 5 to 10 thousand VALU operations a
+    ray against the lattice's one thousand.  2048 rays are 2048 waves on 1024 SIMDs: nothing queues, so a kernel lasts as long
+    as its longest wave -- the lattice's is a chain of ~10 dependent byte reads, the traversal's is VALU issue in the lockstep
+    walk.  Expect the traversal KERNEL to be bound by that walk and a few times the lattice kernel; expect the CALL (what is
+    timed here: two launches, a cumsum, the host read of the count, three allocations) to hide most of it: traversal slower by
+    a few tens of microseconds, 10 to 30 % of the call.  Sample counts: nearly equal (the occupied chord over the step, a run's
+    end rounded to the half step instead of the lattice phase).
+  * traversal_cone: four levels add up to six more segments, each with its own set-up (three more divisions an axis) and a
+    partly filled trip; the cone recurrence costs the writer 64 lockstep steps a round as it costs the lattice a trip.  The gap
+    to the lattice should narrow: the lattice pays its 450 operations on every trip of the whole chord, the traversal only on
+    rounds inside the ball.
+  What came out is in DESIGN 7j ("Measured: the two placements"): the traversal call is 1.8 x and 2.0 x the lattice call, so both
+  of the last two expectations were wrong -- a ray's spans are one dependent chain of scalar branches that nothing overlaps.
 """
 from __future__ import annotations
 
@@ -99,6 +119,18 @@ def main(argv=None) -> int:
     n4 = int(lv4.sampling(o, d, render_step_size=args.step, cone_angle=0.004)[0].numel())
     result["cone"] = dict(rays=int(o.shape[0]), samples=n4, levels=4, cone_angle=0.004,
                           **measure(estimator=lambda: lv4.sampling(o, d, render_step_size=args.step, cone_angle=0.004)))
+    # the two placements on the same estimator: the attribute is switched between the calls, which costs nothing on the device
+    def placed(g, traversal, **kw):
+        def call():
+            g.traversal = traversal
+            return g.sampling(o, d, render_step_size=args.step, **kw)
+        return call
+
+    for key, g, kw in (("traversal", new, {}), ("traversal_cone", lv4, dict(cone_angle=0.004))):
+        counts = {tr: int(placed(g, tr, **kw)()[0].numel()) for tr in ("lattice", "dda")}
+        result[key] = dict(rays=int(o.shape[0]), samples=counts, levels=g.levels, **kw,
+                           **measure(lattice=placed(g, "lattice", **kw), dda=placed(g, "dda", **kw)))
+        g.traversal = "lattice"
     line = json.dumps(result)
     print(line)
     if args.out:
