@@ -14,8 +14,12 @@
 //     M = 2.1M in the reference); d/dx is reduced over the 16 level-lanes of a point with DPP
 //     row operations, embedding gradients go out as fp32 atomics (same as the reference).
 //   * both tables (3.2 MB each) are L2-resident per XCD; gathers are 8-byte float2 loads.
+// The cell rule (grid_locate), the level table (GridMeta) and the fixed-point rule of the table gradient (fx_scales, the absmax
+// and finalize kernels) are grid.h's, shared with hashgrid_general.hip; the row former of this instantiation (grid_rows8) and the
+// brick kernels' own rounding trick (FX_MAGIC) are here.
 #include "common.h"
 #include "wave.h"
+#include "grid.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -25,32 +29,10 @@
 // the CPU oracle does the same, so features agree to the last bit of the interpolation.
 #pragma clang fp contract(off)
 
-struct GridMeta {
-    int32_t offsets[MH_MAX_LEVELS + 1];
-    int32_t res[MH_MAX_LEVELS];
-};
-
-struct Corner8 {
-    uint32_t row[8];
-    float w[8];
-};
-
-__device__ __forceinline__ uint32_t grid_row(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t res, uint32_t T,
-                                             bool dense, bool pow2) {
-    // get_grid_index (gridencoder.cu:61-79): dense x + y*res + z*res^2 while the running stride
-    // fits, else the xor-prime hash; for D=3 "stride > T after the loop" <=> res^3 > T.
-    uint32_t idx;
-    if (dense) {
-        idx = cx + cy * res + cz * res * res;  // < res^3 <= T: the modulo is the identity
-        return idx;
-    }
-    idx = (cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u);
-    return pow2 ? (idx & (T - 1)) : (idx % T);
-}
-
-// the rows of a cell's eight corners (corner c: bit 0 -> x + 1, bit 1 -> y + 1, bit 2 -> z + 1): the per-axis terms of
-// get_grid_index are formed ONCE for the two y and the two z values -- four 32-bit multiplies (v_mul_lo_u32: quarter rate) per cell
-// instead of two or three per corner; the same integers as grid_row() corner by corner
+// the rows of a cell's eight corners (corner c: bit 0 -> x + 1, bit 1 -> y + 1, bit 2 -> z + 1) by get_grid_index
+// (gridencoder.cu:61-79): dense x + y*res + z*res^2 (< res^3 <= T: the modulo is the identity) while the running stride fits, else
+// the xor-prime hash modulo T; for D=3 "stride > T after the loop" <=> res^3 > T.  The per-axis terms are formed ONCE for the two
+// y and the two z values -- four 32-bit multiplies (v_mul_lo_u32: quarter rate) per cell instead of two or three per corner
 __device__ __forceinline__ void grid_rows8(const uint32_t (&g)[3], const uint32_t (&g1)[3], uint32_t res, uint32_t T, bool dense,
                                            bool pow2, uint32_t (&row)[8]) {
     // branch-free over the lanes of a wave (its 16 level-lanes mix dense and hashed levels, and a divergent branch per corner cost
@@ -72,44 +54,6 @@ __device__ __forceinline__ void grid_rows8(const uint32_t (&g)[3], const uint32_
 #pragma unroll
         for (int c = 0; c < 8; c++) row[c] %= T;
     }
-}
-
-// n / d, correctly rounded (what the reference's fp32 `/` gives), for a divisor that stays the same over many quotients: hipcc
-// expands an IEEE division into ~14 VALU instructions (scale, reciprocal, two refinements, fix-up), and every (point, level) lane
-// of the grid kernels did three of them -- a tenth of the brick backward's instruction stream.  With r = RN(1 / d) (ONE division,
-// hoisted out of the loops: d = 2 bound is a kernel argument) two residual corrections give the correctly rounded quotient
-// (Markstein: q' = RN(q + RN(n - d q) r) is correctly rounded once q is within an ulp and r is the correctly rounded reciprocal);
-// checked against exact rational arithmetic on 2.2e5 numerators for seven divisors (tools/micro/README.md).  No scaling: the
-// operands here are O(1), far from the subnormal / overflow ranges the compiler's fix-up instructions exist for.
-__device__ __forceinline__ float exact_div(float n, float d, float r) {
-    const float q0 = n * r;
-    const float q1 = fmaf(fmaf(-d, q0, n), r, q0);
-    return fmaf(fmaf(-d, q1, n), r, q1);
-}
-
-// position inside level: returns false if the point is outside [0,1]^3
-__device__ __forceinline__ bool grid_locate(const float (&xv)[3], float bound, float two_bound, uint32_t res, uint32_t g[3],
-                                            float f[3]) {
-    bool inb = true;
-    const float inv = 1.0f / two_bound;                // loop-invariant in every caller
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        float u = exact_div(xv[d] + bound, two_bound, inv);  // grid.py:157, fp32 add then IEEE divide
-        // (an infinite coordinate makes exact_div's residual inf - inf = NaN where the IEEE quotient is +-inf: the ordered
-        //  comparison sends both -- and a NaN coordinate -- out of the box, as `u < 0 || u > 1` does for the reference's +-inf)
-        inb = inb && (u >= 0.0f && u <= 1.0f);
-        float pos = fminf(fmaxf(fmaf(u, (float)res, -0.5f), 0.0f), (float)(res - 1));
-        float fl = floorf(pos);
-        g[d] = (uint32_t)fl;
-        f[d] = pos - fl;
-    }
-    return inb;
-}
-
-__device__ __forceinline__ bool grid_locate(const float *__restrict__ x, int64_t p, float bound, float two_bound,
-                                            uint32_t res, uint32_t g[3], float f[3]) {
-    const float xv[3] = {x[p * 3 + 0], x[p * 3 + 1], x[p * 3 + 2]};
-    return grid_locate(xv, bound, two_bound, res, g, f);
 }
 
 __global__ __launch_bounds__(256) void grid_fwd_kernel(const float *__restrict__ x, const float2 *__restrict__ emb, GridMeta meta,
@@ -257,13 +201,9 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float2 *__restrict_
         float f[3];
         if (grid_locate(x, p, bound, two_bound, res, g, f)) {
             const float2 gr = grad[gid];
-            const uint32_t g1x = min(g[0] + 1, res - 1), g1y = min(g[1] + 1, res - 1), g1z = min(g[2] + 1, res - 1);
+            const uint32_t g1[3] = {min(g[0] + 1, res - 1), min(g[1] + 1, res - 1), min(g[2] + 1, res - 1)};
             uint32_t row[8];
-#pragma unroll
-            for (int c = 0; c < 8; c++) {
-                uint32_t cx = (c & 1) ? g1x : g[0], cy = (c & 2) ? g1y : g[1], cz = (c & 4) ? g1z : g[2];
-                row[c] = grid_row(cx, cy, cz, res, T, dense, pow2);
-            }
+            grid_rows8(g, g1, res, T, dense, pow2, row);
             float *ge = grad_emb + (size_t)meta.offsets[l] * 2;
 #pragma unroll
             for (int c = 0; c < 8; c++) {
@@ -304,7 +244,7 @@ __global__ __launch_bounds__(256) void grid_bwd_kernel(const float2 *__restrict_
 // gradients of its points in LDS (73 KB: sum over levels of (ceil(res/16)+2)^3 vertices x 2 channels
 // of int64 fixed point), and only the touched vertices are flushed with global atomics -- the 8
 // corner contributions of neighbouring samples collapse on-chip first.  (The on-chip accumulation is
-// 64-bit fixed point, see fx_scales below.)
+// 64-bit fixed point, see fx_scales in grid.h.)
 // =====================================================================================
 #define BRK 16
 #define NBRK (BRK * BRK * BRK)
@@ -326,8 +266,8 @@ __device__ __forceinline__ int brick_of(const float *__restrict__ x, int64_t p, 
     const float inv = 1.0f / two_bound;
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        const float u = exact_div(x[p * 3 + d] + bound, two_bound, inv);
-        if (!(u >= 0.0f && u <= 1.0f)) return NBRK;  // out of range (or not finite): no gradient (gridencoder.cu:279-284)
+        const float u = grid_unit(x[p * 3 + d], bound, two_bound, inv);
+        if (!grid_in_box(u)) return NBRK;  // out of range (or not finite): no gradient (gridencoder.cu:279-284)
         b[d] = min((int)floorf(u * (float)BRK), BRK - 1);
     }
     return (b[2] * BRK + b[1]) * BRK + b[0];
@@ -432,23 +372,6 @@ __global__ __launch_bounds__(256) void bin_scatter_kernel(const float *__restric
     }
 }
 
-// max |grad| over the whole feature-gradient tensor, as the raw bits of a non-negative float
-// (monotone in the value, so an integer atomicMax does the reduction)
-__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ g, int64_t n, uint32_t *__restrict__ out) {
-    uint32_t m = 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t n4 = n >> 2;   // n = M * 32 floats: whole float4s (the tail loop below covers any other caller)
-    const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 v = g4[i];
-        m = max(max(m, __float_as_uint(fabsf(v[0]))), __float_as_uint(fabsf(v[1])));
-        m = max(max(m, __float_as_uint(fabsf(v[2]))), __float_as_uint(fabsf(v[3])));
-    }
-    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max(m, __float_as_uint(fabsf(g[i])));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
 // LDS float atomics (ds_add_f32) run ~40x slower than integer ones on gfx950 (177 vs 4.6-6.4 cycles per
 // wave instruction, tools/micro/lds_atomics.hip), so vertex gradients are accumulated on-chip in 64-bit
 // fixed point: q = (int64) (v * 2^40 / G),  G = power of two >= max|grad|.  A vertex receives at most 2048
@@ -457,17 +380,9 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ g
 // order-independent -- more accurate than the float atomics it replaces, and ~25x faster.  (ds_add_f64 is also
 // fast, 8.1 cycles, but its same-address rate is 40 vs 26 cycles and the kernel came out 25 % slower with it, even
 // without the max|grad| pre-pass it makes unnecessary: measured, not kept.)
-#define FX_BITS 40
+// (FX_BITS, FX_LIMIT and fx_scales: grid.h.  The magic add is this kernel's way of rounding onto that grid.)
 #define FX_MAGIC 6755399441055744.0                 // 1.5 * 2^52
 #define FX_MAGIC_BITS 0x4338000000000000ULL
-#define FX_LIMIT 1099511627776.0f                   // 2^40: the fixed-point range a scaled gradient is clamped to
-__device__ __forceinline__ void fx_scales(uint32_t maxbits, float &to_fx, float &from_fx) {
-    int e = (int)(maxbits >> 23) + 1;   // biased exponent of the power of two above max|grad|
-    e = max(e, 60);                     // gradients below 2^-67 are accumulated with a fixed (coarser) scale
-    e = min(e, 254);
-    to_fx = __uint_as_float((uint32_t)(127 + FX_BITS + 127 - e) << 23);    // 2^(40 - (e-127))
-    from_fx = __uint_as_float((uint32_t)(127 - FX_BITS - 127 + e) << 23);  // 2^((e-127) - 40)
-}
 
 // Workgroup = BRK_THREADS = 1024 lanes: 64 points x 16 levels in flight per iteration, 16 waves sharing one accumulator.
 //
@@ -871,35 +786,13 @@ __global__ __launch_bounds__(BRK_THREADS, STAGED ? 4 : 8) void grid_bwd_brick_ke
     }
 }
 
-// grad_emb[i] += emb_acc[i] in the float scale of the call (from_fx of its max |grad|, times 2^acc_shift): one rounding per entry.
-__global__ void grid_acc_finalize_kernel(const long long *__restrict__ emb_acc, float *__restrict__ grad_emb, int64_t n, int acc_shift,
-                                         const uint32_t *__restrict__ gmax_bits) {
-    float to_fx, from_fx;
-    fx_scales(*gmax_bits, to_fx, from_fx);
-    const double scale = (double)from_fx * (double)(1LL << acc_shift);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const long long a = emb_acc[i];
-        if (a != 0) grad_emb[i] += (float)((double)a * scale);
-    }
-}
-
-static int fill_meta(GridMeta &m, const int32_t *offsets_host, const int32_t *res_host, int L) {
-    if (!offsets_host || !res_host || L < 1 || L > MH_MAX_LEVELS) return MH_ERR_ARG;
-    for (int i = 0; i <= L; i++) m.offsets[i] = offsets_host[i];
-    for (int i = 0; i < L; i++) {
-        m.res[i] = res_host[i];
-        if (res_host[i] < 2 || offsets_host[i + 1] <= offsets_host[i]) return MH_ERR_ARG;
-    }
-    return MH_OK;
-}
-
 extern "C" int mh_grid_encode_fwd(const float *x, const float *emb, const int32_t *offsets_host,
                                   const int32_t *res_host, float *out, int64_t M, int32_t L, int32_t n_levels,
                                   float bound, int32_t group, void *stream) {
     if (M == 0) return MH_OK;
     if (!x || !emb || !out || M < 0 || n_levels < 0 || n_levels > L || !(bound > 0.f) || group < 1) return MH_ERR_ARG;
     GridMeta meta;
-    int st = fill_meta(meta, offsets_host, res_host, L);
+    int st = grid_fill_meta(meta, offsets_host, res_host, L);
     if (st) return st;
     if (group == 6 && M % 6 == 0) {   // the finite-difference tap layout; any other hint runs ungrouped (same results)
         const int64_t n_groups = M / 6;
@@ -928,7 +821,7 @@ extern "C" int mh_grid_encode_bwd(const float *grad, const float *x, const float
     if (!grad || !x || !emb || !grad_emb || M < 0 || n_levels < 0 || n_levels > L || !(bound > 0.f)) return MH_ERR_ARG;
     if (grad_x && L != 16) return MH_ERR_ARG;  // d/dx reduction is specialised to 16-lane level groups
     GridMeta meta;
-    int st = fill_meta(meta, offsets_host, res_host, L);
+    int st = grid_fill_meta(meta, offsets_host, res_host, L);
     if (st) return st;
     const int64_t threads = M * L;
     const int64_t blocks = (threads + 255) / 256;
@@ -1069,7 +962,7 @@ extern "C" int mh_grid_encode_fwd_binned(const float *x, const float *emb, const
         !(bound > 0.f))
         return MH_ERR_ARG;
     GridMeta meta;
-    int st = fill_meta(meta, offsets_host, res_host, L);
+    int st = grid_fill_meta(meta, offsets_host, res_host, L);
     if (st) return st;
     BrickMeta bm;
     if ((st = fill_brick_meta(bm, res_host, L))) return st;
@@ -1092,7 +985,7 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
         !(bound > 0.f))
         return MH_ERR_ARG;
     GridMeta meta;
-    int st = fill_meta(meta, offsets_host, res_host, L);
+    int st = grid_fill_meta(meta, offsets_host, res_host, L);
     if (st) return st;
     BrickMeta bm;
     if ((st = fill_brick_meta(bm, res_host, L))) return st;
@@ -1104,15 +997,14 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
     // reduced here into the scratch word behind the work-item table
     // a table row receives at most 8 terms per point (hash collisions included), each at most 2^(FX_BITS - acc_shift) in fixed
     // point (the scale and the NaN / Inf clamp of grid_bwd_brick_kernel): keep 8 M such terms inside +-2^62
-    int acc_shift = 0;
-    while (acc_shift < 40 && (double)M * 8.0 > std::ldexp(1.0, 62 - FX_BITS + acc_shift)) acc_shift++;
+    const int acc_shift = grid_acc_shift(M, 8);
     const int64_t n_acc = (int64_t)offsets_host[L] * 2;
     if (!mh_zero_async(emb_acc, sizeof(int64_t) * (size_t)n_acc, mh_stream(stream))) return MH_ERR_LAUNCH;
     const uint32_t *gmax = gmax_bits;
     if (!gmax) {
         uint32_t *own = reinterpret_cast<uint32_t *>(const_cast<int32_t *>(brick_start)) + (2 * NBRK + 4);
         if (!mh_zero_async(own, sizeof(uint32_t), mh_stream(stream))) return MH_ERR_LAUNCH;
-        hipLaunchKernelGGL(absmax_kernel, dim3(1024), dim3(256), 0, mh_stream(stream), grad, M * (int64_t)L * 2, own);
+        grid_absmax_launch(grad, M * (int64_t)L * 2, own, mh_stream(stream));
         gmax = own;
     }
 #define BRK_LAUNCH(DXMODE, STG)                                                                                                \
@@ -1133,7 +1025,7 @@ extern "C" int mh_grid_encode_bwd_binned(const float *grad, const float *x, cons
 #undef BRK_LAUNCH
     MH_CHECK_LAUNCH();
     hipLaunchKernelGGL(grid_acc_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0,
-                       mh_stream(stream), reinterpret_cast<const long long *>(emb_acc), grad_emb, n_acc, acc_shift, gmax);
+                       mh_stream(stream), reinterpret_cast<const long long *>(emb_acc), grad_emb, n_acc, acc_shift, gmax, 0.0);
     MH_CHECK_LAUNCH();
     return MH_OK;
 }

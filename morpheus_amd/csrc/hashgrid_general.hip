@@ -12,19 +12,20 @@
 // Every sum into a table-shaped buffer (table gradient, total variation) goes through 64-bit fixed point: integer adds commute,
 // so the result is the same from run to run whatever order the waves arrive in, which float atomics cannot give.
 // This is the plain path: no brick staging.  The default configuration keeps hashgrid.hip's kernels.
+// The cell rule (grid_locate), the level table's validation (grid_fill_meta) and the fixed-point rule (fx_scales, fx_quantize, the
+// absmax and finalize kernels) are grid.h's, shared with hashgrid.hip; the row index of every grid type (gg_row) is this file's.
 #include "common.h"
 #include "wave.h"
+#include "grid.h"
 #include <algorithm>
 #include <cmath>
 
-// what is written is what runs: the explicit fmaf calls below are the single-rounding operations oracle/hashgrid.c and
-// hashgrid.hip make (`u * res - 0.5` and `+= w * value`, as nvcc -fmad=true fuses them), nothing else is contracted, so the fp32
-// restatement of the tests (tests/grid_general_oracle.py) takes the same cells as these kernels
+// what is written is what runs: the explicit fmaf calls below are the single-rounding operations oracle/hashgrid.c makes
+// (`+= w * value`, as nvcc -fmad=true fuses it), nothing else is contracted, so the fp32 restatement of the tests
+// (tests/grid_general_oracle.py) takes the same cells as these kernels
 #pragma clang fp contract(off)
 
-struct GGMeta {
-    int32_t off[MH_MAX_LEVELS + 1];
-    int32_t res[MH_MAX_LEVELS];
+struct GGMeta : GridMeta {
     uint32_t my[MH_MAX_LEVELS], mz[MH_MAX_LEVELS];   // get_grid_index's strides of y and z; 0 where its loop stopped before the axis
     int32_t hashed[MH_MAX_LEVELS];                   // gridtype == 0 and the running stride outgrew the table
 };
@@ -37,8 +38,8 @@ struct GGLevel {
 __device__ __forceinline__ GGLevel gg_level(const GGMeta &m, int l) {
     GGLevel v;
     v.res = (uint32_t)m.res[l];
-    v.off = (uint32_t)m.off[l];
-    v.T = (uint32_t)(m.off[l + 1] - m.off[l]);
+    v.off = (uint32_t)m.offsets[l];
+    v.T = (uint32_t)(m.offsets[l + 1] - m.offsets[l]);
     v.my = m.my[l], v.mz = m.mz[l];
     v.hashed = m.hashed[l] != 0;
     v.pow2 = (v.T & (v.T - 1)) == 0;
@@ -51,39 +52,6 @@ __device__ __forceinline__ GGLevel gg_level(const GGMeta &m, int l) {
 __device__ __forceinline__ uint32_t gg_row(uint32_t cx, uint32_t cy, uint32_t cz, const GGLevel &v) {
     const uint32_t idx = v.hashed ? (cx ^ (cy * 2654435761u) ^ (cz * 805459861u)) : (cx + cy * v.my + cz * v.mz);
     return v.pow2 ? (idx & (v.T - 1)) : (idx % v.T);
-}
-
-// n / d correctly rounded from r = RN(1 / d): hashgrid.hip's exact_div (two residual corrections), the same bits as the IEEE quotient
-__device__ __forceinline__ float gg_div(float n, float d, float r) {
-    const float q0 = n * r;
-    const float q1 = fmaf(fmaf(-d, q0, n), r, q0);
-    return fmaf(fmaf(-d, q1, n), r, q1);
-}
-
-// cell g and position f inside it (gridencoder.cu:105-111, :143-151); false for a point outside [0,1]^3 (or not finite).
-// normalized: the coordinates are u already (grad_total_variation's own random points, grid.py:184)
-__device__ __forceinline__ bool gg_locate(const float *__restrict__ x, int64_t p, float bound, float two_bound, int normalized,
-                                          uint32_t res, int align, uint32_t (&g)[3], float (&f)[3]) {
-    bool inb = true;
-    const float inv = 1.0f / two_bound;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const float xv = x[p * 3 + d];
-        const float u = normalized ? xv : gg_div(xv + bound, two_bound, inv);     // grid.py:157
-        inb = inb && (u >= 0.0f && u <= 1.0f);
-        float pos;
-        uint32_t c;
-        if (align) {
-            pos = u * (float)(res - 1);
-            c = min((uint32_t)floorf(pos), res - 2);
-        } else {
-            pos = fminf(fmaxf(fmaf(u, (float)res, -0.5f), 0.0f), (float)(res - 1));
-            c = (uint32_t)floorf(pos);
-        }
-        g[d] = c;
-        f[d] = pos - (float)c;
-    }
-    return inb;
 }
 
 __device__ __forceinline__ float gg_smoothstep(float v) { return v * v * (3.0f - 2.0f * v); }
@@ -149,7 +117,7 @@ __global__ __launch_bounds__(256) void gg_fwd_kernel(const float *__restrict__ x
         const GGLevel lv = gg_level(meta, l);
         uint32_t g[3];
         float f[3];
-        if (gg_locate(x, p, bound, two_bound, 0, lv.res, align, g, f)) {
+        if (grid_locate(x, p, bound, two_bound, lv.res, g, f, align)) {
             if (interp) {
 #pragma unroll
                 for (int d = 0; d < 3; d++) f[d] = gg_smoothstep(f[d]);
@@ -171,34 +139,8 @@ __global__ __launch_bounds__(256) void gg_fwd_kernel(const float *__restrict__ x
 }
 
 // ---- table gradient: 64-bit fixed point ----------------------------------------------------------------------------------------
-// A term w * g is rounded ONCE onto the grid 2^-(40 - shift) G, G the power of two above max |grad| (hashgrid.hip's FX_BITS and
-// scales), from the exact double product; the integer sums are exact and order-independent; one conversion to fp32 per table entry.
-#define GG_FX_BITS 40
-#define GG_FX_LIMIT 1099511627776.0f   // 2^40
-
-__device__ __forceinline__ void gg_fx_scales(uint32_t maxbits, float &to_fx, float &from_fx) {
-    int e = (int)(maxbits >> 23) + 1;
-    e = min(max(e, 60), 254);
-    to_fx = __uint_as_float((uint32_t)(127 + GG_FX_BITS + 127 - e) << 23);
-    from_fx = __uint_as_float((uint32_t)(127 - GG_FX_BITS - 127 + e) << 23);
-}
-
-// max |g| as the raw bits of a non-negative float (monotone in the value: an integer atomicMax reduces it)
-__global__ __launch_bounds__(256) void gg_absmax_kernel(const float *__restrict__ g, int64_t n, uint32_t *__restrict__ out) {
-    uint32_t m = 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) m = max(m, __float_as_uint(fabsf(g[i])));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
-// value * to_fx rounded to the nearest integer, saturated inside the headroom (a NaN gives the lower limit: v_med3 returns the
-// smallest operand then -- one bounded contribution, not an arbitrary bit pattern)
-__device__ __forceinline__ long long gg_fx(double v, float lim) {
-    const double c = fmin(fmax(v, (double)-lim), (double)lim);      // fmax(NaN, -lim) = -lim
-    return __double2ll_rn(c);
-}
-
+// A term w * g is rounded ONCE onto the grid 2^-(40 - shift) G, G the power of two above max |grad| (grid.h), from the exact double
+// product; the integer sums are exact and order-independent; one conversion to fp32 per table entry (grid_acc_finalize_kernel).
 template <int C, bool VEC>
 __global__ __launch_bounds__(256) void gg_bwd_emb_kernel(const float *__restrict__ grad, const float *__restrict__ x, GGMeta meta,
                                                          long long *__restrict__ acc, int acc_shift, int64_t M, int L, int align,
@@ -210,15 +152,15 @@ __global__ __launch_bounds__(256) void gg_bwd_emb_kernel(const float *__restrict
     const GGLevel lv = gg_level(meta, l);
     uint32_t g[3];
     float f[3];
-    if (!gg_locate(x, p, bound, two_bound, 0, lv.res, align, g, f)) return;     // gridencoder.cu:279-284
+    if (!grid_locate(x, p, bound, two_bound, lv.res, g, f, align)) return;     // gridencoder.cu:279-284
     if (interp) {
 #pragma unroll
         for (int d = 0; d < 3; d++) f[d] = gg_smoothstep(f[d]);                 // :301-304
     }
     float to_fx, from_fx;
-    gg_fx_scales(*gmax_bits, to_fx, from_fx);
+    fx_scales(*gmax_bits, to_fx, from_fx);
     to_fx = ldexpf(to_fx, -acc_shift);
-    const float lim = ldexpf(GG_FX_LIMIT, -acc_shift);
+    const float lim = ldexpf(FX_LIMIT, -acc_shift);
     float gr[C];
     gg_load<C, VEC>(grad + (p * L + l) * C, gr);
     double gd[C];
@@ -232,22 +174,7 @@ __global__ __launch_bounds__(256) void gg_bwd_emb_kernel(const float *__restrict
     for (int c = 0; c < 8; c++)
 #pragma unroll
         for (int k = 0; k < C; k++)
-            atomicAdd(a + (size_t)row[c] * C + k, (unsigned long long)gg_fx((double)w[c] * gd[k], lim));
-}
-
-// out[i] += acc[i] * scale, one rounding per entry; entries nothing was added to are not written
-__global__ __launch_bounds__(256) void gg_finalize_kernel(const long long *__restrict__ acc, float *__restrict__ out, int64_t n,
-                                                          int acc_shift, const uint32_t *__restrict__ gmax_bits, double fixed_scale) {
-    double scale = fixed_scale;
-    if (gmax_bits) {
-        float to_fx, from_fx;
-        gg_fx_scales(*gmax_bits, to_fx, from_fx);
-        scale = (double)from_fx * (double)(1LL << acc_shift);
-    }
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const long long a = acc[i];
-        if (a != 0) out[i] += (float)((double)a * scale);
-    }
+            atomicAdd(a + (size_t)row[c] * C + k, (unsigned long long)fx_quantize((double)w[c] * gd[k], lim));
 }
 
 // ---- d(loss)/dx -----------------------------------------------------------------------------------------------------------------
@@ -267,7 +194,7 @@ __global__ __launch_bounds__(256) void gg_bwd_dx_kernel(const float *__restrict_
         const GGLevel lv = gg_level(meta, l);
         uint32_t g[3];
         float f[3], df[3] = {1.f, 1.f, 1.f};
-        if (!gg_locate(x, p, bound, two_bound, 0, lv.res, align, g, f)) break;      // outside at one level = outside at all: zero
+        if (!grid_locate(x, p, bound, two_bound, lv.res, g, f, align)) break;      // outside at one level = outside at all: zero
         if (interp) {
 #pragma unroll
             for (int d = 0; d < 3; d++) df[d] = gg_smoothstep_d(f[d]), f[d] = gg_smoothstep(f[d]);
@@ -305,7 +232,7 @@ __global__ __launch_bounds__(256) void gg_bwd_dx_kernel(const float *__restrict_
             for (int k = 0; k < C; k++) res3[gd] += gr[k] * dy[k];
         }
     }
-    const float inv = 1.0f / two_bound;       // chain factor of u = (x + bound) / (2 bound), applied as hashgrid.hip applies it
+    const float inv = 1.0f / two_bound;       // chain factor of u = (x + bound) / (2 bound), applied once per point
 #pragma unroll
     for (int d = 0; d < 3; d++) grad_x[p * 3 + d] = res3[d] * inv;
 }
@@ -326,7 +253,7 @@ __global__ __launch_bounds__(256) void gg_tv_kernel(const float *__restrict__ x,
     const GGLevel lv = gg_level(meta, l);
     uint32_t g[3];
     float f[3];
-    if (!gg_locate(x, p, bound, two_bound, normalized, lv.res, align, g, f)) return;
+    if (!grid_locate(x, p, bound, two_bound, lv.res, g, f, align, normalized)) return;
     const float *tab = emb + (size_t)lv.off * C;
     const uint32_t row = gg_row(g[0], g[1], g[2], lv);
     float v[C], r[C], q[C];
@@ -360,7 +287,7 @@ __global__ __launch_bounds__(256) void gg_tv_kernel(const float *__restrict__ x,
 #pragma unroll
     for (int k = 0; k < C; k++) {
         const float addend = (w6 * r[k]) / sqrtf(q[k] + 1e-9f);
-        const long long t = gg_fx((double)addend * (double)to_fx, lim);
+        const long long t = fx_quantize((double)addend * (double)to_fx, lim);
         if (t != 0) atomicAdd(a + k, (unsigned long long)t);
     }
 }
@@ -369,19 +296,16 @@ __global__ __launch_bounds__(256) void gg_tv_kernel(const float *__restrict__ x,
 __global__ __launch_bounds__(256) void gg_wd_kernel(const float *__restrict__ emb, float *__restrict__ grad, GGMeta meta, int C,
                                                     float two_w) {
     const int l = blockIdx.y;
-    const int64_t a = (int64_t)meta.off[l] * C, n = (int64_t)(meta.off[l + 1] - meta.off[l]) * C;
-    const float T = (float)(uint32_t)(meta.off[l + 1] - meta.off[l]);
+    const int64_t a = (int64_t)meta.offsets[l] * C, n = (int64_t)(meta.offsets[l + 1] - meta.offsets[l]) * C;
+    const float T = (float)(uint32_t)(meta.offsets[l + 1] - meta.offsets[l]);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         grad[a + i] += two_w * emb[a + i] / T;
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 static int gg_fill_meta(GGMeta &m, const int32_t *offsets_host, const int32_t *res_host, int L, int gridtype) {
-    if (!offsets_host || !res_host || L < 1 || L > MH_MAX_LEVELS) return MH_ERR_ARG;
-    if (offsets_host[0] < 0) return MH_ERR_ARG;
-    for (int i = 0; i <= L; i++) m.off[i] = offsets_host[i];
+    if (int st = grid_fill_meta(m, offsets_host, res_host, L)) return st;
     for (int i = 0; i < L; i++) {
-        if (res_host[i] < 2 || offsets_host[i + 1] <= offsets_host[i]) return MH_ERR_ARG;
         const uint32_t res = (uint32_t)res_host[i], T = (uint32_t)(offsets_host[i + 1] - offsets_host[i]);
         // the stride loop of get_grid_index in its own uint32 arithmetic: axis 0 always (stride 1 <= T), then while stride <= T
         uint32_t stride = res;
@@ -394,7 +318,6 @@ static int gg_fill_meta(GGMeta &m, const int32_t *offsets_host, const int32_t *r
                 stride *= res;
             }
         }
-        m.res[i] = res_host[i];
         m.hashed[i] = (gridtype == 0 && stride > T) ? 1 : 0;
     }
     return MH_OK;
@@ -434,13 +357,6 @@ extern "C" int mh_grid_general_fwd(const float *x, const float *emb, const int32
     return MH_OK;
 }
 
-static int gg_acc_shift(int64_t M, int terms_per_point) {
-    // a row receives at most terms_per_point * M terms of at most 2^(40 - shift): keep their sum inside +-2^62
-    int s = 0;
-    while (s < 40 && (double)M * terms_per_point > std::ldexp(1.0, 62 - GG_FX_BITS + s)) s++;
-    return s;
-}
-
 extern "C" int mh_grid_general_bwd(const float *grad, const float *x, const float *emb, const int32_t *offsets_host,
                                    const int32_t *res_host, float *grad_emb, int64_t *emb_acc, float *grad_x, int64_t M, int32_t L,
                                    int32_t n_levels, int32_t C, int32_t gridtype, int32_t align_corners, int32_t interp, float bound,
@@ -459,9 +375,9 @@ extern "C" int mh_grid_general_bwd(const float *grad, const float *x, const floa
     // emb_acc: n_acc sums and, behind them, the word that receives max |grad|
     if (!mh_zero_async(emb_acc, sizeof(int64_t) * (size_t)(n_acc + 1), s)) return MH_ERR_LAUNCH;
     uint32_t *gmax = reinterpret_cast<uint32_t *>(emb_acc + n_acc);
-    hipLaunchKernelGGL(gg_absmax_kernel, dim3(1024), dim3(256), 0, s, grad, M * (int64_t)L * C, gmax);
+    grid_absmax_launch(grad, M * (int64_t)L * C, gmax, s);
     MH_CHECK_LAUNCH();
-    const int acc_shift = gg_acc_shift(M, 8);
+    const int acc_shift = grid_acc_shift(M, 8);
     const bool vec = gg_aligned(emb, C) && gg_aligned(grad, C);
     if (n_levels > 0) {
 #define GG_BWD(CC, VV)                                                                                                             \
@@ -471,7 +387,7 @@ extern "C" int mh_grid_general_bwd(const float *grad, const float *x, const floa
         GG_DISPATCH(C, vec, GG_BWD)
 #undef GG_BWD
         MH_CHECK_LAUNCH();
-        hipLaunchKernelGGL(gg_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0, s,
+        hipLaunchKernelGGL(grid_acc_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0, s,
                            reinterpret_cast<const long long *>(emb_acc), grad_emb, n_acc, acc_shift, gmax, 0.0);
         MH_CHECK_LAUNCH();
     }
@@ -507,9 +423,9 @@ extern "C" int mh_grid_grad_tv(const float *x, const float *emb, const int32_t *
         std::frexp(std::fabs(weight), &e);          // |weight| = m 2^e, 0.5 <= m < 1: 2^e > |weight|
         e = std::max(e, -60);
     }
-    const int acc_shift = gg_acc_shift(M, 1);
-    const float to_fx = std::ldexp(1.0f, GG_FX_BITS - acc_shift - e), lim = std::ldexp(1.0f, GG_FX_BITS - acc_shift);
-    const double from_fx = std::ldexp(1.0, e + acc_shift - GG_FX_BITS);
+    const int acc_shift = grid_acc_shift(M, 1);
+    const float to_fx = std::ldexp(1.0f, FX_BITS - acc_shift - e), lim = std::ldexp(1.0f, FX_BITS - acc_shift);
+    const double from_fx = std::ldexp(1.0, e + acc_shift - FX_BITS);
     const float w6 = weight / 6.0f;                 // `weight / (2 * D)`, gridencoder.cu:586
     const float b = normalized ? 1.0f : bound;
     const bool vec = gg_aligned(emb, C);
@@ -519,7 +435,7 @@ extern "C" int mh_grid_grad_tv(const float *x, const float *emb, const int32_t *
     GG_DISPATCH(C, vec, GG_TV)
 #undef GG_TV
     MH_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gg_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0, s,
+    hipLaunchKernelGGL(grid_acc_finalize_kernel, dim3((unsigned)std::min<int64_t>((n_acc + 255) / 256, 4096)), dim3(256), 0, s,
                        reinterpret_cast<const long long *>(emb_acc), grad_emb, n_acc, 0, (const uint32_t *)nullptr, from_fx);
     MH_CHECK_LAUNCH();
     return MH_OK;
@@ -532,7 +448,7 @@ extern "C" int mh_grid_grad_wd(const float *emb, const int32_t *offsets_host, fl
         return MH_ERR_ARG;
     GGMeta meta = {};
     int64_t widest = 0;
-    for (int i = 0; i <= L; i++) meta.off[i] = offsets_host[i];
+    for (int i = 0; i <= L; i++) meta.offsets[i] = offsets_host[i];
     for (int i = 0; i < L; i++) {
         if (offsets_host[i + 1] <= offsets_host[i]) return MH_ERR_ARG;
         widest = std::max<int64_t>(widest, (int64_t)(offsets_host[i + 1] - offsets_host[i]) * C);

@@ -190,6 +190,31 @@ def test_eight_levels_with_an_input_gradient():
     judge_blocks("L=8 d/dx", xg.grad.cpu().numpy(), case.grad_x(g, F32), case.grad_x(g, F64), [("all", slice(None))])
 
 
+@pytest.mark.parametrize("C", (1, 4))
+def test_upstream_gradient_starting_one_float_into_a_buffer(C):
+    """a contiguous upstream gradient whose storage starts 4 bytes into an allocation (what autograd hands over for one half of a
+    `cat`): the maximum pre-pass and the row loads may make no 16-byte access to it, so x.grad and the table gradient equal, bit
+    for bit, those of the same values in a tensor of their own"""
+    emb, offs, res = table("one", C)
+    assert emb.shape[0] == 4096
+    x = points(65)
+    values = torch.from_numpy(upstream(len(x), C)).to(DEV)
+    buf = torch.zeros(values.numel() + 1, device=DEV)
+    buf[1:] = values.reshape(-1)
+    view = buf[1:].view_as(values)
+    assert view.is_contiguous() and view.data_ptr() == buf.data_ptr() + 4 and buf.data_ptr() % 16 == 0
+
+    def run(grad):
+        xg = torch.from_numpy(x).to(DEV).requires_grad_(True)
+        e = torch.from_numpy(emb).to(DEV).requires_grad_(True)
+        ops.grid_encode_general(xg, e, offs, res, BOUND, None, C).backward(grad)
+        return xg.grad, e.grad
+
+    (gx_view, ge_view), (gx_own, ge_own) = run(view), run(values.clone())
+    assert bool(ge_own.abs().sum() > 0) and bool(gx_own.abs().sum() > 0)
+    assert torch.equal(gx_view, gx_own) and torch.equal(ge_view, ge_own)
+
+
 # ---- total variation and weight decay ---------------------------------------------------------------------------------------------
 TV_WEIGHT = 1e-3
 

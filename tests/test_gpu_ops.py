@@ -102,7 +102,8 @@ def test_grid_forward_binned_bit_identical(n_levels):
     assert int(outside.sum()) > 20_000 and bool((out[outside] == 0).all())
     assert torch.equal(out, ref)
     # ... and through the autograd op, which takes the binned form by call size and hands its binning to the backward
-    before = lib.mh_grid_stage_min_points(0)
+    before = lib.mh_grid_stage_min_points(-1)
+    lib.mh_grid_stage_min_points(0)
     try:
         xs, e = x.clone().requires_grad_(True), embg.clone().requires_grad_(True)
         feat = ops.grid_encode(xs, e, offs, res, 1.01, max_level=n_levels / 16.0)
@@ -993,7 +994,8 @@ def test_grid_large_batch_gradients():
     assert torch.equal(gx1, gx2)
     from morpheus_amd import _lib
     lib = _lib.load()
-    before = lib.mh_grid_stage_min_points(1 << 40)             # ... and the single call in the gathering form: the same bits
+    before = lib.mh_grid_stage_min_points(-1)                  # (a set call returns the NEW value: query first)
+    lib.mh_grid_stage_min_points(1 << 40)                      # ... and the single call in the gathering form: the same bits
     try:
         ge3, gx3 = run(M)
     finally:
