@@ -17,8 +17,8 @@ import torch
 
 from .build import HEADER, SO as _BUILT_SO
 
-# MORPHEUS_HIP_LIB: load another build of the SAME library (a variant from tools/build_variant_lib.sh or
-# tools/build_head_lib.sh, compared on one box by tools/gpu/lib_ab.sh);
+# MORPHEUS_HIP_LIB: load another build of the SAME library (`python -m morpheus_amd.build --name NAME [--rev REV] [-- FLAG ...]`:
+# the product's recipe and per-file flags on another revision or with extra flags, compared on one box by tools/gpu/lib_ab.sh);
 # the default is the in-tree build, and there is still no fallback to anything that is not this library
 SO = os.environ.get("MORPHEUS_HIP_LIB") or _BUILT_SO
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU-box script: A/B of two builds of the library on one box: the in-tree build against morpheus_amd/_build/libmorpheus_head.so
-# (another source state compiled in the container).  Arguments: "name|bench flags" ...
+# (another revision, built beforehand with `python -m morpheus_amd.build --name head --rev REV`).  Arguments: "name|bench flags" ...
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out/libab
 for rep in 1 2; do
@@ -9,6 +9,7 @@ for lib in head new; do
   for spec in "$@"; do
     name="${spec%%|*}"; flags="${spec#*|}"
     timeout 600 python bench.py $flags --no-cpu-baseline > gpurun_out/libab/${name}_${lib}_$rep.log 2> gpurun_out/libab/${name}_${lib}_$rep.err
+    rc=$?; [ $rc -eq 0 ] || { echo "$name $lib rep $rep: bench.py failed ($rc), starting nothing more on this GPU"; exit 1; }
     python - "gpurun_out/libab/${name}_${lib}_$rep.log" "$name $lib" <<'PY'
 import json, sys
 try:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Where does a warp_fwd_kernel wave spend its time?  Needs the trace build of the library:
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DMH_PHASE_TRACE -o morpheus_amd/_build/libmorpheus_trace.so morpheus_amd/csrc/*.hip
+  python -m morpheus_amd.build --name trace -- -DMH_PHASE_TRACE          (morpheus_amd/_build/libmorpheus_trace.so)
 Wave 0 of every 64th workgroup stamps s_memtime at the phase boundaries; this prints the mean duration of each phase."""
 import ctypes
 import os

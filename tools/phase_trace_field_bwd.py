@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Where does a wave of field_fused_sdf_kernel spend a tile?  Needs the trace build of the library:
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -shared -DMH_PHASE_TRACE -o morpheus_amd/_build/libmorpheus_trace.so morpheus_amd/csrc/*.hip
+  python -m morpheus_amd.build --name trace -- -DMH_PHASE_TRACE          (morpheus_amd/_build/libmorpheus_trace.so)
 and MORPHEUS_HIP_LIB pointing at it (tools/gpu/trace_field_bwd.sh); MORPHEUS_FIELD_BWD=f32|b3 selects the arithmetic, argv[1] = 1
 for the colour + sdf pass (cfg3's call), 0 for the sdf-only pass (the finite-difference taps).  Wave 0 of every 8th workgroup stamps
 s_memtime at the phase boundaries of its third tile."""
