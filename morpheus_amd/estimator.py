@@ -34,7 +34,8 @@ stays so: `sampling_as(traversal, ...)` is `sampling` with the placement of that
 With `levels=1`, a centred cubic box and default planes `sampling` returns `OccupancyGrid.sampling`'s samples bit for bit, and
 the two classes load each other's `state_dict()`.
 
-`packed`, `src_index`, `n_valid`, `overflow`, `sample_capacity` and `fixed_jitter` have `OccupancyGrid`'s meaning, so
+`sample_packed` is `occgrid.PackedSampling`'s: the same `PackedSamples` record as `OccupancyGrid` gives, remembered as `last`
+(which `packed`, `src_index` and `n_valid` read), and `overflow`, `sample_capacity` and `fixed_jitter` with the same meaning, so
 `HotPathRenderer(model, cfg, estimator, ...)` and the graph-captured step take this class unchanged.
 There is no CPU path: CPU tensors raise MorpheusHipError, as everywhere in the package.
 """
@@ -119,17 +120,22 @@ class OccGridEstimator(PackedSampling, torch.nn.Module):
             self._set_diagonal(a.detach().cpu().numpy())
 
     # -- sampling --------------------------------------------------------------------------------
-    @torch.no_grad()
     def sampling(self, rays_o, rays_d, sigma_fn=None, alpha_fn=None, near_plane=0.0, far_plane=1e10, t_min=None, t_max=None,
                  render_step_size=1e-3, early_stop_eps=1e-4, alpha_thre=0.0, stratified=False, cone_angle=0.0):
         """nerfacc's OccGridEstimator.sampling (signature and defaults recalled, agreement unverified) -> (ray_indices int32,
-        t_starts, t_ends); `self.packed` = (ray_start, ray_cnt) of what is returned.
+        t_starts, t_ends): the first three fields of `sample_packed`'s record, which `self.last` keeps.
         sigma_fn / alpha_fn: fn(t_starts, t_ends, ray_indices) -> [M] densities / opacities of the marched samples; the samples
         with transmittance under early_stop_eps or opacity under min(alpha_thre, mean of the non-negative occs) are dropped
-        (ops.visibility_prune) and `self.src_index` holds the marched position of every returned sample.
+        (ops.visibility_prune) and the record's `src_index` holds the marched position of every returned sample.
         Without a density function the two thresholds are ignored, as nerfacc does -- `OccupancyGrid.sampling` raises there.
         t_min / t_max: float32 [n_rays] on the device.  `sample_capacity` set: fixed-length results and no host read.
         The placement is `self.traversal`; everything else here works alike on both."""
+        return self.sample_packed(rays_o, rays_d, sigma_fn=sigma_fn, alpha_fn=alpha_fn, alpha_thre=alpha_thre,
+                                  early_stop_eps=early_stop_eps, stratified=stratified, near_plane=near_plane, far_plane=far_plane,
+                                  t_min=t_min, t_max=t_max, render_step_size=render_step_size, cone_angle=cone_angle)[:3]
+
+    def _marcher(self, rays_o, rays_d, sigma_fn, alpha_fn, alpha_thre, early_stop_eps, near_plane=0.0, far_plane=1e10, t_min=None,
+                 t_max=None, render_step_size=1e-3, cone_angle=0.0):
         if sigma_fn is not None and alpha_fn is not None:
             raise ValueError("sampling: give sigma_fn or alpha_fn, not both")
         if not (0.0 <= alpha_thre <= 1.0) or not (0.0 <= early_stop_eps <= 1.0):
@@ -144,10 +150,9 @@ class OccGridEstimator(PackedSampling, torch.nn.Module):
 
         def march(u, capacity):
             return rays(rays_o, rays_d, u, float(render_step_size), self.aabbs, self.binaries.view(torch.uint8), self._diagonal,
-                        float(cone_angle), float(near_plane), float(far_plane), t_min, t_max, capacity=capacity)
+                        float(cone_angle), float(near_plane), float(far_plane), t_min, t_max, capacity=capacity), None
 
-        return self._sample(rays_o.shape[0], rays_o.device, stratified, march, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
-                            lambda cap: ops.est_threshold(self.occs, cap))
+        return march, lambda cap: ops.est_threshold(self.occs, cap)
 
     def sampling_as(self, traversal: str, rays_o, rays_d, **kw):
         """`sampling(rays_o, rays_d, **kw)` with the placement `traversal` for this one call; the attribute is left as it was"""

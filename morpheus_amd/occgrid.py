@@ -13,11 +13,14 @@ here follow its published 0.5.x behaviour as summarised in SURVEY.md C.9 and are
     pruned by visibility (csrc/visibility.hip: T >= early_stop_eps and alpha >= min(alpha_thre, mean(occs)), include/morpheus_hip.h; recalled
     from nerfacc 0.5.x, NOT verified).  The reference passes sigma_fn=None, alpha_thre=0, early_stop_eps=0: no pruning,
     the marcher's samples as they are.  Cone marching (cone_angle != 0) is not implemented.
+`sampling` returns nerfacc's three tensors; `sample_packed` (PackedSampling) returns everything a consumer of the samples needs
+as one PackedSamples record -- the three tensors, the rays' ranges, the fixed-capacity count, the pruning's source positions,
+midpoints where the kernel made them -- and `sampling` is its first three fields.
 The heavy part of an update is occ_eval_fn = model.density on up to resolution^3 points, which runs on the HIP kernels.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -35,11 +38,24 @@ def check_prune_args(sigma_fn, alpha_fn, alpha_thre, early_stop_eps):
         raise ValueError(f"sampling: alpha_thre ({alpha_thre}) and early_stop_eps ({early_stop_eps}) lie in [0, 1]")
 
 
+class PackedSamples(NamedTuple):
+    """The packed samples of one sampling call, as every consumer takes them: rec[:3] is nerfacc's (ray_indices, t_starts,
+    t_ends).  A plain tuple of tensors built on the host -- no launch, no device read, nothing registered on a module."""
+    ray_indices: torch.Tensor
+    t_starts: torch.Tensor
+    t_ends: torch.Tensor
+    ray_start: torch.Tensor                       # int32 [N]: where every ray's samples begin
+    ray_cnt: torch.Tensor                         # int32 [N]
+    n_valid: Optional[torch.Tensor] = None        # fixed-capacity sampling: int32 0-dim device count of the entries that are samples
+    src_index: Optional[torch.Tensor] = None      # pruned sampling: int32 [M], the position every sample had before (None: nothing was pruned)
+    xyz: Optional[torch.Tensor] = None            # [M, 3] midpoints o + d (ts + te) / 2 where the sampler's kernel already produced them
+
+
 class PackedSampling:
-    """What `OccupancyGrid.sampling` and `estimator.OccGridEstimator.sampling` share; the class keeps its own argument rules, its
-    march and its threshold.  State, with the same meaning in both classes:
-      packed    (ray_start, ray_cnt) of the last sampling() call, consumed by the compositor
-      src_index pruned sampling: the marched position of every returned sample (None: nothing was pruned)
+    """What `OccupancyGrid`, `estimator.OccGridEstimator` and `render.UniformSampler` share: `sample_packed`, the one path from
+    `sampling`'s arguments to a PackedSamples record; the class keeps its own argument rules, its march and its threshold
+    (`_marcher`).  State, with the same meaning in every class:
+      last      the record of the last call; `packed` = (ray_start, ray_cnt), `src_index` and `n_valid` read it
       fixed_jitter  parity runs pin the per-ray jitter (a float: one value for every ray, chunk-invariant; a tensor: per ray)
       sample_capacity  None = off: ragged packed samples sized by one device->host sync, as nerfacc does.  With a capacity the
                 packed arrays always have that length, the first `n_valid` (a device int) entries are the samples and the rest is
@@ -48,17 +64,25 @@ class PackedSampling:
                 capacity -- its tail rays were truncated -- and is the caller's cue to raise the capacity."""
 
     def _init_sampling_state(self):
-        self.packed = None
-        self.src_index = None
+        self.last: Optional[PackedSamples] = None
         self.fixed_jitter: Optional[torch.Tensor] = None
         self.sample_capacity: Optional[int] = None
-        self.n_valid: Optional[torch.Tensor] = None
         self.overflow: Optional[torch.Tensor] = None
 
-    def _sample(self, n: int, dev, stratified: bool, march: Callable, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
-                threshold: Callable):
-        """march(u, capacity) -> the ragged five results (capacity None) or the fixed-capacity seven (ops.march_rays /
-        ops.march_rays_capped and ops.est_march_rays); threshold(alpha_thre) -> the pruning threshold as a device scalar."""
+    packed = property(lambda self: None if self.last is None else (self.last.ray_start, self.last.ray_cnt))
+    src_index = property(lambda self: None if self.last is None else self.last.src_index)
+    n_valid = property(lambda self: None if self.last is None else self.last.n_valid)
+
+    @torch.no_grad()
+    def sample_packed(self, rays_o, rays_d, sigma_fn=None, alpha_fn=None, alpha_thre=0.0, early_stop_eps=0.0, stratified=False,
+                      **how) -> PackedSamples:
+        """`sampling`'s arguments (`how`: the class's own, by keyword) -> the record, which `last` remembers: the jitter choice,
+        the march, the optional visibility pruning.  self._marcher(rays_o, rays_d, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
+        **how) checks the arguments by the class's rules and gives march(u, capacity) -> (the ragged five results or, with a
+        capacity, the fixed-capacity seven of ops.march_rays / ops.march_rays_capped, the midpoints or None) and
+        threshold(alpha_thre) -> the pruning threshold, a float or a device scalar."""
+        march, threshold = self._marcher(rays_o, rays_d, sigma_fn, alpha_fn, alpha_thre, early_stop_eps, **how)
+        n, dev = rays_o.shape[0], rays_o.device
         if isinstance(self.fixed_jitter, float):
             u = torch.full((n,), self.fixed_jitter, device=dev)
         elif self.fixed_jitter is not None:
@@ -68,26 +92,26 @@ class PackedSampling:
         else:
             u = None
         capped = self.sample_capacity is not None
-        out = march(u, int(self.sample_capacity) if capped else None)
+        out, xyz = march(u, int(self.sample_capacity) if capped else None)
         ri, ts, te, rs, rc = out[:5]
+        n_valid = src = None
         if capped:
-            self.n_valid = out[5]
+            n_valid = out[5]
             if self.overflow is None:
                 self.overflow = torch.zeros((), dtype=torch.int32, device=dev)
             self.overflow.copy_(torch.maximum(self.overflow, out[6]))
-        else:
-            self.n_valid = None
-        self.packed, self.src_index = (rs, rc), None
         fn = sigma_fn if sigma_fn is not None else alpha_fn
         if fn is not None and ts.shape[0] > 0:
             thre = threshold(float(alpha_thre)) if alpha_thre > 0 else None      # formed on the device
             out = ops.visibility_prune(fn(ts, te, ri), ts, te, rs, rc, float(early_stop_eps), thre, alpha_form=sigma_fn is None,
                                        padded=capped)
-            ri, ts, te, rs, rc, self.src_index = out[:6]
+            ri, ts, te, rs, rc, src = out[:6]
             if capped:
-                self.n_valid = out[6]
-            self.packed = (rs, rc)
-        return ri, ts, te
+                n_valid = out[6]
+            if xyz is not None:
+                xyz = xyz.index_select(0, src.long())
+        self.last = PackedSamples(ri, ts, te, rs, rc, n_valid, src, xyz)
+        return self.last
 
 
 class OccupancyGrid(PackedSampling, torch.nn.Module):
@@ -111,15 +135,20 @@ class OccupancyGrid(PackedSampling, torch.nn.Module):
         self._init_sampling_state()
 
     # -- sampling --------------------------------------------------------------------------------
-    @torch.no_grad()
     def sampling(self, rays_o, rays_d, sigma_fn=None, render_step_size=1e-3, alpha_thre=0.0, stratified=False,
                  cone_angle=0.0, early_stop_eps=0.0, alpha_fn=None):
-        """nerfacc's OccGridEstimator.sampling -> (ray_indices, t_starts, t_ends); `self.packed` = (ray_start, ray_cnt) of what
-        is returned.  sigma_fn / alpha_fn: called as fn(t_starts, t_ends, ray_indices) -> [M] densities / opacities of the
-        marched samples (not called when there is none); the samples with transmittance under early_stop_eps or opacity under
-        min(alpha_thre, mean(occs)) are dropped (ops.visibility_prune), `self.src_index` then holds the marched position of
-        every returned sample.  The defaults are the reference's call (no pruning); nerfacc's own default early_stop_eps is 1e-4.
-        nerfacc silently ignores alpha_thre / early_stop_eps when neither function is given; here that is a ValueError."""
+        """nerfacc's OccGridEstimator.sampling -> (ray_indices, t_starts, t_ends): the first three fields of `sample_packed`'s
+        record, which `self.last` keeps.  sigma_fn / alpha_fn: called as fn(t_starts, t_ends, ray_indices) -> [M] densities /
+        opacities of the marched samples (not called when there is none); the samples with transmittance under early_stop_eps
+        or opacity under min(alpha_thre, mean(occs)) are dropped (ops.visibility_prune), the record's `src_index` then holds the
+        marched position of every returned sample.  The defaults are the reference's call (no pruning); nerfacc's own default
+        early_stop_eps is 1e-4.  nerfacc silently ignores alpha_thre / early_stop_eps when neither function is given; here that
+        is a ValueError."""
+        return self.sample_packed(rays_o, rays_d, sigma_fn=sigma_fn, alpha_fn=alpha_fn, alpha_thre=alpha_thre,
+                                  early_stop_eps=early_stop_eps, stratified=stratified, render_step_size=render_step_size,
+                                  cone_angle=cone_angle)[:3]
+
+    def _marcher(self, rays_o, rays_d, sigma_fn, alpha_fn, alpha_thre, early_stop_eps, render_step_size=1e-3, cone_angle=0.0):
         if cone_angle != 0.0:
             raise NotImplementedError("cone marching (cone_angle != 0) is not used by the reference's call "
                                       "(morpheus.py:629-638) and is not implemented")
@@ -129,12 +158,11 @@ class OccupancyGrid(PackedSampling, torch.nn.Module):
 
         def march(u, capacity):
             if capacity is None:
-                return ops.march_rays(rays_o, rays_d, u, step, self.bound, binary)
-            return ops.march_rays_capped(rays_o, rays_d, u, step, self.bound, binary, capacity)
+                return ops.march_rays(rays_o, rays_d, u, step, self.bound, binary), None
+            return ops.march_rays_capped(rays_o, rays_d, u, step, self.bound, binary, capacity), None
 
         # nerfacc's rule: the opacity threshold never exceeds the grid's mean occupancy value
-        return self._sample(rays_o.shape[0], rays_o.device, stratified, march, sigma_fn, alpha_fn, alpha_thre, early_stop_eps,
-                            lambda cap: torch.clamp(self.occs.mean(), max=cap))
+        return march, lambda cap: torch.clamp(self.occs.mean(), max=cap)
 
     # -- occupancy update -------------------------------------------------------------------------
     def _cell_points(self, idx: torch.Tensor) -> torch.Tensor:

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import ops, volrend
+from .occgrid import PackedSamples
 
 
 @torch.no_grad()
@@ -45,15 +46,25 @@ def _ray_indices(ray_start, ray_cnt, M: int, n_valid):
 @torch.no_grad()
 def importance_sampling(ray_start, ray_cnt, t_starts, t_ends, n_importance: int, weights=None, sigmas=None, det: bool = False,
                         jitter=None, eps: float = 1e-5, n_valid=None, with_xyz: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-    """The packed samples (ray_start, ray_cnt int32 [N]; t_starts, t_ends [M]) cut at n_importance draws per ray from the
-    piecewise-constant pdf (w_i + eps) / sum over each ray's own intervals
-    -> (ray_indices, t_starts, t_ends, ray_start, ray_cnt[, xyz][, n_valid]).
+    """`refine_samples` on loose arrays: the packed samples (ray_start, ray_cnt int32 [N]; t_starts, t_ends [M]; n_valid as the
+    record's) -> (ray_indices, t_starts, t_ends, ray_start, ray_cnt[, xyz][, n_valid]): xyz with with_xyz, the new n_valid last
+    when one was given."""
+    rec = refine_samples(PackedSamples(None, t_starts, t_ends, ray_start, ray_cnt, n_valid), n_importance, weights, sigmas, det,
+                         jitter, eps, with_xyz)
+    return rec[:5] + ((rec.xyz,) if with_xyz is not None else ()) + ((rec.n_valid,) if n_valid is not None else ())
+
+
+@torch.no_grad()
+def refine_samples(rec: PackedSamples, n_importance: int, weights=None, sigmas=None, det: bool = False, jitter=None,
+                   eps: float = 1e-5, with_xyz: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> PackedSamples:
+    """The record's samples (its ray_indices are not read: the ranges say the same) cut at n_importance draws per ray from the
+    piecewise-constant pdf (w_i + eps) / sum over each ray's own intervals -> the record of the refined samples.
     weights [M], or sigmas [M] (densities: they go through the compositor's weights kernel, volrend.render_weight_from_density,
     first) -- one of the two.  det: the draws sit at (k + 0.5) / n, the reference's det=True grid; else at (k + jitter[r, k]) / n,
-    jitter fp32 [N, n] in [0, 1) (None: torch.rand).  n_valid (int32 0-dim, device): the inputs have a fixed capacity and only
+    jitter fp32 [N, n] in [0, 1) (None: torch.rand).  rec.n_valid (int32 0-dim, device): the inputs have a fixed capacity and only
     their first n_valid entries are samples (occgrid.PackedSampling.sample_capacity); the outputs then have length M + n N, the
-    new n_valid is returned last and nothing is read by the host.  with_xyz = (rays_o, rays_d): also the midpoints' positions.
-    A ray without samples keeps none; n_importance = 0 returns the input."""
+    result carries the new n_valid and nothing is read by the host.  with_xyz = (rays_o, rays_d): also the midpoints' positions.
+    A ray without samples keeps none; n_importance = 0 returns the input's samples."""
     if (weights is None) == (sigmas is None):
         raise ValueError("importance_sampling: give weights or sigmas, one of the two")
     if det and jitter is not None:
@@ -61,23 +72,21 @@ def importance_sampling(ray_start, ray_cnt, t_starts, t_ends, n_importance: int,
     n = int(n_importance)
     if n < 0:
         raise ValueError(f"importance_sampling: n_importance = {n}")
+    ray_start, ray_cnt, t_starts, t_ends, n_valid = rec.ray_start, rec.ray_cnt, rec.t_starts, rec.t_ends, rec.n_valid
     ops.require_gpu(ray_start, ray_cnt, t_starts, t_ends, weights, sigmas, jitter, n_valid)
     N, M = ray_start.shape[0], t_starts.shape[0]
-    padded = n_valid is not None
     if n == 0:
         ri = _ray_indices(ray_start, ray_cnt, M, n_valid)
-        out = (ri, t_starts, t_ends, ray_start, ray_cnt)
+        xyz = None
         if with_xyz is not None:
-            out += (ops.sample_positions_nograd(with_xyz[0].detach(), with_xyz[1].detach(), ri, t_starts, t_ends),)
-        return out + (n_valid,) if padded else out
+            xyz = ops.sample_positions_nograd(with_xyz[0].detach(), with_xyz[1].detach(), ri, t_starts, t_ends)
+        return PackedSamples(ri, t_starts, t_ends, ray_start, ray_cnt, n_valid, None, xyz)
     if weights is None:
         weights = volrend.render_weight_from_density(t_starts, t_ends, sigmas.detach().reshape(-1).float(),
                                                      packed_info=torch.stack((ray_start, ray_cnt), dim=1))[0]
     if not det and jitter is None:
         jitter = torch.rand(N, n, device=t_starts.device)
     o, d = with_xyz if with_xyz is not None else (None, None)
-    out = ops.resample_packed(weights, t_starts, t_ends, ray_start, ray_cnt, n, None if det else jitter, eps, padded=padded,
-                              rays_o=o, rays_d=d)
-    ri, ts, te, rs, rc, xyz = out[:6]
-    res = (ri, ts, te, rs, rc) + ((xyz,) if with_xyz is not None else ())
-    return res + (out[6],) if padded else res
+    out = ops.resample_packed(weights, t_starts, t_ends, ray_start, ray_cnt, n, None if det else jitter, eps,
+                              padded=n_valid is not None, rays_o=o, rays_d=d)
+    return PackedSamples(*out[:5], n_valid=out[6] if n_valid is not None else None, xyz=out[5])

@@ -325,16 +325,16 @@ def test_pruned_training_render_equals_render_of_the_kept_samples():
         harness.bench_loss(res, timg, tdep).backward()
         return res, {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
 
-    seen, sampling = [], grid.sampling
+    seen, sample_packed = [], grid.sample_packed      # what the renderer calls: sampling() is its first three fields
 
     def recording(*a_, **kw):
-        out = sampling(*a_, **kw)
-        seen.append(tuple(t.clone() for t in out))
+        out = sample_packed(*a_, **kw)
+        seen.append(tuple(t.clone() for t in out[:3]))
         return out
 
-    grid.sampling = recording
+    grid.sample_packed = recording
     res_a, g_a = run(rend)
-    grid.sampling = sampling
+    grid.sample_packed = sample_packed
     (ri, ts, te), = seen
     assert 0 < ri.numel() == res_a["sdf"].shape[0]
     n_marched = grid.sampling(data["rays_o"][0], data["rays_d"][0], render_step_size=model.config["render"]["step_size"])[0].numel()

@@ -74,7 +74,7 @@ def main(argv=None) -> int:
     # function is handed inside that same call (the train workload moves the model and the grid from call to call, so counts of
     # different calls do not compare); without pruning the two are the same number
     counts = dict(returned=0, marched=0, calls=0)
-    sampling = grid.sampling
+    sampling = grid.sample_packed      # what the renderer calls; sampling() is its first three fields
 
     def counting(*a, **kw):
         out = sampling(*a, **kw)
@@ -133,9 +133,9 @@ def main(argv=None) -> int:
             torch.cuda.synchronize()
             wall.append((time.perf_counter() - t0) * 1e3)
         counts.update(returned=0, marched=0, calls=0)
-        grid.sampling = counting
+        grid.sample_packed = counting
         call()
-        grid.sampling = sampling
+        grid.sample_packed = sampling
         torch.cuda.synchronize()
         returned = counts["returned"]
         marched = counts["marched"] if pruning() else returned
