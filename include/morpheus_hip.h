@@ -1212,6 +1212,61 @@ int mh_resample_packed(const float *weights, const float *t_starts, const float 
                        const float *rays_d, int32_t *out_ray_idx, float *out_t_starts, float *out_t_ends, float *xyz,
                        void *stream);
 
+/* ---- image resampling (csrc/imageops.hip; morpheus_amd/imageops.py is its Python face) ---------------------------------------
+ * Purely additive: MH_ABI_VERSION is unchanged.  csrc/imageops.hip's header states every operation; tests/imageops_oracle.py
+ * restates it.
+ * mh_resize_bilinear_fwd: x fp32, B images of C <= 4 channels at Hi x Wi, [B,Hi,Wi,C] (nhwc != 0) or [B,C,Hi,Wi] -> y fp32
+ *   [B,C,Ho,Wo] = mul * bilinear(x) + add, PyTorch's upsample_bilinear2d with align_corners=False and no scale factor.
+ * mh_resize_bilinear_bwd: gy fp32 [B,C,Ho,Wo] -> gx fp32 in x's layout = mul * (the adjoint of the interpolation applied to gy),
+ *   every element written; a gather in a fixed order without atomics: the same bits on every run.
+ * mh_resize_area_masked: image [Hi,Wi,3] fp32 in [0,1] or uint8 (image_u8 != 0: value / 255), mask fp32 [Hi,Wi] or NULL (all
+ *   kept) -> out fp32 [3,Ho,Wo]: img * m + (1 - m), m = mask > 0.5, averaged over each output pixel's source box with the exact
+ *   fractional overlaps.  Ho <= Hi and Wo <= Wi; an enlarging axis is MH_ERR_ARG.
+ * mh_frame_to_u8: out[i] = (uint8) of x[i] * 255 held to [0, 255] (NaN: 0), truncated.
+ * mh_depth_to_u8: out[i] = (uint8) of (d[i] - min) / (max - min + 1e-6f) * 255, min / max over the n values found on the device
+ *   (two launches, no host read; NaN-free input); range: int32 scratch of mh_depth_range_words words. */
+int mh_resize_bilinear_fwd(const float *x, int32_t B, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t nhwc,
+                           float mul, float add, float *y, void *stream);
+int mh_resize_bilinear_bwd(const float *gy, int32_t B, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t nhwc,
+                           float mul, float *gx, void *stream);
+int mh_resize_area_masked(const void *image, int32_t image_u8, const float *mask, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                          float *out, void *stream);
+int mh_frame_to_u8(const float *x, int64_t n, uint8_t *out, void *stream);
+int32_t mh_depth_range_words(void);
+int mh_depth_to_u8(const float *depth, int64_t n, int32_t *range, uint8_t *out, void *stream);
+
+/* ---- the Zero-1-to-3 guidance shell (csrc/guidance.hip; morpheus_amd/guidance.py is its Python face) -------------------------
+ * Purely additive: MH_ABI_VERSION is unchanged.  What zero123_utils.py:Zero123.train_step does around its networks; the file's
+ * header states every operation, tests/guidance_oracle.py restates it.  Every entry point is one launch; nothing is read back.
+ * mh_sds_view: the view deltas polar / azimuth (degrees) and radius fp32 [B] against R <= mh_sds_max_refs reference views
+ *   (ref_polars, ref_azimuths, ref_radii, user_ws fp32 [R]) -> T fp32 [R,B,4], angles fp32 [B,R] (degrees), scale fp32 [B],
+ *   ws fp32 [B,R].
+ * mh_sds_view_bank: the same with R = 1 against a bank of K keyframes (kf_index int64 [K], the four fp32 [K] arrays): the keyframe
+ *   nearest to frame_id[0] (int64, device; the lowest index on a tie), or with target != 0 keyframe 0 with the view re-expressed
+ *   relative to it; chosen int64 [1] = the keyframe's index in the bank.
+ * mh_sds_angles: v1 fp32 [N1,3], v2 fp32 [N2,3] rows [r, theta, phi] in radians -> out fp32 [N1,N2], the angle in radians.
+ * mh_sds_noise: latents, noise fp32 [B,n], t int64 [B], alphas_cumprod fp32 [T] -> x_in fp32 [2B,n]:
+ *   sqrt(a_t) latents + sqrt(1 - a_t) noise in both halves.  t outside [0, T) is held to the table's ends.
+ * mh_sds_grad: noise_preds fp32 [R,2B,n] (unconditional half first), ws fp32 [B,R], noise fp32 [B,n], scale fp32 [B] ->
+ *   grad fp32 [B,n] = nan_to_num(scale (1 - a_t) (sum_k w_k (u_k + s (c_k - u_k)) / sum_k w_k - noise)) and loss fp32 [1] =
+ *   0.5 sum grad^2 / B, summed in a fixed order.  partials: float64 scratch of mh_sds_grad_blocks values; ticket: uint32 [1],
+ *   zero before the first call and left zero by every call. */
+int32_t mh_sds_max_refs(void);
+int32_t mh_sds_grad_blocks(void);
+int mh_sds_view(const float *polar, const float *azimuth, const float *radius, int32_t B, const float *ref_polars,
+                const float *ref_azimuths, const float *ref_radii, const float *user_ws, int32_t R, float grad_scale, float *T,
+                float *angles, float *scale, float *ws, void *stream);
+int mh_sds_view_bank(const float *polar, const float *azimuth, const float *radius, int32_t B, const int64_t *frame_id,
+                     const int64_t *kf_index, int32_t K, const float *ref_polars, const float *ref_azimuths,
+                     const float *ref_radii, const float *user_ws, int32_t target, float grad_scale, int64_t *chosen, float *T,
+                     float *angles, float *scale, float *ws, void *stream);
+int mh_sds_angles(const float *v1, int32_t N1, const float *v2, int32_t N2, float *out, void *stream);
+int mh_sds_noise(const float *latents, const float *noise, const int64_t *t, const float *alphas_cumprod, int32_t T, int32_t B,
+                 int64_t n, float *x_in, void *stream);
+int mh_sds_grad(const float *noise_preds, const float *ws, const float *noise, const int64_t *t, const float *alphas_cumprod,
+                int32_t T, const float *scale, float guidance_scale, int32_t R, int32_t B, int64_t n, float *grad,
+                double *partials, uint32_t *ticket, float *loss, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
