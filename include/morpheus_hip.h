@@ -350,6 +350,34 @@ int64_t mh_warp_skip_zero_lines(int64_t set);
 int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
                    const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
                    float *out_topo, float *acts, int64_t M, void *stream);
+/* Eliding: a writer that does not send an all-zero parked line (a row whose word bit is 0) to memory.  The entries above write
+ * every line, and whoever reads whole tiles may rely on it.  The *_elide entries carry one flag per call:
+ * mh_warp_fwd_b3_elide(elide = 1): the H rows without a non-zero are NOT written; the line words, the sign masks and the
+ *   encoding rows always are.  Same outputs.
+ * mh_warp_bwd_data_b3_elide(elided = 1): the dPre rows of layers 0..4 whose bit is 0 are NOT written and hold whatever the scratch
+ *   held before (dPre5's live rows are always written; dPre4 follows skip_dpre4).  g_x keeps its bits.
+ * mh_warp_wgrad_b3_elide(elided = 1): the tiles were written by an eliding call, so the launches go by the words whatever
+ *   mh_warp_skip_zero_lines says at that moment -- every gradient keeps its bits.
+ * elided = 1 needs mh_warp_regen_dpre4(M) (the per-layer weight-gradient kernels: the merged small-batch kernels read every row),
+ * else MH_ERR_ARG; a flag of 0 is the entry without the suffix.  The caller decides once, at forward time, with mh_warp_elides(M),
+ * and whoever elided a scratch hands it only to *_elide entries with elided = 1 (morpheus_amd/ops.py: warp_mlp(elide=True) carries
+ * the decision to its backward in the autograd ctx).
+ * mh_warp_elides(M): what a call on M points may elide: 0 = nothing (no mh_warp_regen_dpre4(M), or mh_warp_skip_zero_lines off),
+ *   else the value of mh_warp_elide_zero_lines.
+ * mh_warp_elide_zero_lines: process-wide switch for the A/B: 2 = forward and backward-data elide (the default), 1 = backward-data
+ *   only, 0 = no call elides; set < 0: query only.  Returns the value in force.  MORPHEUS_WARP_ELIDE_ZERO_LINES sets it when the
+ *   library is loaded. */
+int64_t mh_warp_elide_zero_lines(int64_t set);
+int32_t mh_warp_elides(int64_t M);
+int mh_warp_fwd_b3_elide(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
+                         const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                         float *out_topo, float *acts, int64_t M, int32_t elide, void *stream);
+int mh_warp_bwd_data_b3_elide(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
+                              int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4,
+                              int32_t elided, void *stream);
+int mh_warp_wgrad_b3_elide(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
+                           const void *w3T_t, int32_t regen_dpre4, int32_t elided, float *workspace, float *dw_raw, float *db_raw,
+                           int64_t M, void *stream);
 /* backward-data: consumes g_deform [M,3], g_topo [M,2] (either may be NULL = zero), acts from the
  * forward and the TRANSPOSED packs; writes g_x [M,3] (d/dx through the frequency encoding; pass NULL when the
  * sample positions carry no gradient and the first-layer transposed GEMM is skipped) and

@@ -106,6 +106,8 @@ def load():
             lib.mh_grid_stage_min_points(int(os.environ["MORPHEUS_GRID_STAGE_MIN_POINTS"]))
         if os.environ.get("MORPHEUS_WARP_SKIP_ZERO_LINES"):        # A/B switch, see include/morpheus_hip.h (0: fetch every parked row)
             lib.mh_warp_skip_zero_lines(int(os.environ["MORPHEUS_WARP_SKIP_ZERO_LINES"]))
+        if os.environ.get("MORPHEUS_WARP_ELIDE_ZERO_LINES"):       # A/B switch, see include/morpheus_hip.h (0: every parked line is written)
+            lib.mh_warp_elide_zero_lines(int(os.environ["MORPHEUS_WARP_ELIDE_ZERO_LINES"]))
         _fns.update(fns)
         _lib = lib
     return _lib

@@ -3069,17 +3069,34 @@ extern "C" int64_t mh_warp_skip_zero_lines(int64_t set) {
 // dPre4 is regenerated by the large-batch (one launch per layer) weight-gradient path only
 extern "C" int32_t mh_warp_regen_dpre4(int64_t M) { return M > 0 && n_tiles_for(M) >= WG_PER_LAYER_TILES ? 1 : 0; }
 
+// Process-wide switch of eliding (mlp_b3.hip: B3Park): 2 = forward and backward-data elide, the default; 1 = backward-data only;
+// 0 = no call elides (the A/B); set < 0 only reads it.  mh_warp_elides(M) is the whole decision a caller takes at forward time: the per-layer kernels (the only readers that go by the
+// words) will serve the call's weight gradients, they do skip, and eliding is on.  The call then carries it to its backward, where
+// neither switch is asked again.
+static std::atomic<int64_t> g_warp_elide_zero_lines{2};
+extern "C" int64_t mh_warp_elide_zero_lines(int64_t set) {
+    if (set >= 0) g_warp_elide_zero_lines.store(set > 2 ? 2 : set, std::memory_order_relaxed);
+    return g_warp_elide_zero_lines.load(std::memory_order_relaxed);
+}
+extern "C" int32_t mh_warp_elides(int64_t M) {
+    return mh_warp_regen_dpre4(M) && g_warp_skip_zero_lines.load(std::memory_order_relaxed) != 0
+               ? (int32_t)g_warp_elide_zero_lines.load(std::memory_order_relaxed)
+               : 0;
+}
+
 extern "C" int64_t mh_warp_wgrad_workspace_floats(int64_t M) {
     const WarpWg w = warp_wg_geometry();
     return mh_mlp_wgrad_workspace_floats(12, w.in, w.out, n_tiles_for(M));
 }
 
-extern "C" int mh_warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
-                                const void *w3T_t, int32_t regen_dpre4, float *workspace, float *dw_raw, float *db_raw, int64_t M,
-                                void *stream) {
+// elided: the tiles' all-zero rows were not written (mh_warp_bwd_data_b3_elide): the launches must go by the words
+static int warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
+                         const void *w3T_t, int32_t regen_dpre4, bool elided, float *workspace, float *dw_raw, float *db_raw, int64_t M,
+                         void *stream) {
     if (M == 0) return MH_OK;
     if (M < 0 || !w3T_d || !w3T_t) return MH_ERR_ARG;
     if (regen_dpre4 && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;      // (the small-batch launches read dPre4)
+    if (elided && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;           // (the merged small-batch kernels read every row)
     const WarpWg w = warp_wg_geometry();
     WgRegenHost rg;
     for (int k = 0; k < WG_MAX_LAYERS; k++) rg.on[k] = false;
@@ -3101,10 +3118,20 @@ extern "C" int mh_warp_wgrad_b3(const float *acts, const float *dpre, const floa
             if (l <= 4) ln.a_off[net * 6 + l] = word0 + l * 4;
             if (l >= 1) ln.b_off[net * 6 + l] = word0 + (l - 1) * 4;
         }
-    const bool skip = g_warp_skip_zero_lines.load(std::memory_order_relaxed) != 0;
+    const bool skip = elided || g_warp_skip_zero_lines.load(std::memory_order_relaxed) != 0;
     return wgrad_impl(acts, dpre, (int64_t)WARP_ACT_ROWS * TILE, (int64_t)WARP_DPRE_ROWS * TILE, 12, w.act_off, w.dpre_off, w.in, w.out,
                       w.in_live, w.out_live, workspace, dw_raw, db_raw, n_tiles_for(M), stream, true, regen_dpre4 ? &rg : nullptr,
                       skip ? &ln : nullptr);
+}
+extern "C" int mh_warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
+                                const void *w3T_t, int32_t regen_dpre4, float *workspace, float *dw_raw, float *db_raw, int64_t M,
+                                void *stream) {
+    return warp_wgrad_b3(acts, dpre, g_deform, g_topo, w3T_d, w3T_t, regen_dpre4, false, workspace, dw_raw, db_raw, M, stream);
+}
+extern "C" int mh_warp_wgrad_b3_elide(const float *acts, const float *dpre, const float *g_deform, const float *g_topo,
+                                      const void *w3T_d, const void *w3T_t, int32_t regen_dpre4, int32_t elided, float *workspace,
+                                      float *dw_raw, float *db_raw, int64_t M, void *stream) {
+    return warp_wgrad_b3(acts, dpre, g_deform, g_topo, w3T_d, w3T_t, regen_dpre4, elided != 0, workspace, dw_raw, db_raw, M, stream);
 }
 
 // ---- fused field backward (backward-data + weight gradients, see field_fused_*_kernel) ---------------------------------

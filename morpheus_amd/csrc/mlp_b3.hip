@@ -206,13 +206,64 @@ __device__ __forceinline__ void b3_quarter_step(const f32x4 *__restrict__ w, con
     for (int t = 0; t < 2; t++) acc[T0 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t].h, bh[s].h, acc[T0 + t], 0, 0, 0);
 }
 
+// ---- eliding parking stores (round 9) ---------------------------------------------------------------------------------------
+// A parked row whose line-word bit is 0 is all zero bits and no reader fetches it (mlp.hip: wg_line_ptr), so an ELIDE kernel does
+// not send it to memory.  The store stays where it is -- one instruction per accumulator register on every path, no branch, the
+// same count in vmcnt -- and goes through a buffer descriptor of the wave's own tile: a lane whose row is elided gets bit 31 of its
+// byte offset set, which is past the descriptor's range, and the hardware's range check drops that lane's store before it reaches
+// the cache.  A row is one half-wave (32 lanes x 4 bytes = one 128-byte line), so an elided row moves no byte.  The descriptor is
+// built from readfirstlane'd halves of the tile pointer: hipcc takes everything derived from threadIdx as divergent and would wrap
+// each store in a waterfall loop otherwise.
+__device__ __forceinline__ uint32_t b3_or_half(uint32_t v);      // (with the line words, below)
+struct B3Park {
+    __amdgpu_buffer_rsrc_t srd;      // the wave's tile, num_records = its bytes
+    uint32_t lane;                   // byte offset of the lane inside a 32-row block: its point and acc_row's 4 h rows
+    uint32_t gone;                   // `lane` with bit 31 set
+};
+// up to 32 row bits of a block (bit set <-> the row has a non-zero), OR-ed over each lane half
+struct B3Rows {
+    uint32_t k0, k1;                 // half 0's and half 1's bits in scalar registers
+};
+constexpr int B3_AUX_NT = 2;         // the nt bit of a gfx94x / gfx950 buffer instruction: what PARK_STORE's non-temporal store sets
+template <int TILE_ROWS>
+__device__ __forceinline__ void b3_park_tile(B3Park &pk, float *tile, int pt, int h) {
+    const uint64_t a = reinterpret_cast<uint64_t>(tile);
+    const uint64_t u = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32);
+    static_assert((int64_t)TILE_ROWS * TILE * 4 < (1ll << 31), "an elided lane's offset (bit 31) must lie past the tile");
+    pk.srd = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), 0, TILE_ROWS * TILE * 4, 0x00020000);
+    pk.lane = (uint32_t)((4 * h * TILE + pt) * 4);
+    pk.gone = pk.lane | 0x80000000u;
+}
+// sign / non-zero bits the lanes hold -> the rows' bits (for whole words: the line word the forward parks, b3_park_line_word)
+__device__ __forceinline__ B3Rows b3_rows(uint32_t m) {
+    const uint32_t v = b3_or_half(m);      // lanes 31 and 63 hold their half's OR
+    const uint32_t k0 = __builtin_amdgcn_readlane(v, 31), k1 = __builtin_amdgcn_readlane(v, 63);
+    B3Rows w;
+    w.k0 = k0;
+    w.k1 = k1;
+    return w;
+}
+// register r of output tile t -> row 32 t + acc_row(r, h) of the block at byte `blk` of the tile (wave-uniform), unless bit `bit`
+// of the rows' word says the row is all zero
+__device__ __forceinline__ void b3_park_elide(float v, const B3Park &pk, uint32_t blk, const B3Rows &w, int bit, int t, int r) {
+    // the two halves' bits as a lane mask, made in the scalar unit: one v_cndmask per store is all the vector unit sees of it
+    const uint64_t on = (uint64_t)(uint32_t)__builtin_amdgcn_sbfe(w.k0, bit, 1) | ((uint64_t)(uint32_t)__builtin_amdgcn_sbfe(w.k1, bit, 1) << 32);
+    const uint32_t off = __builtin_amdgcn_inverse_ballot_w64(on) ? pk.lane : pk.gone;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), pk.srd, (int)off + acc_row(r, 0) * TILE * 4, (int)blk + 32 * t * TILE * 4,
+                                          B3_AUX_NT);
+}
+
 // registers 8 s2 .. 8 s2 + 7 of output tile t: ReLU in place, park, their 8 mask bits, the slices of k16 step 2t + s2
-template <bool PARK>
+// ELIDE: the eight rows' bits (the OR of the lanes' non-zero bits over each half) are made BEFORE the stores, and a row without a
+// non-zero is not stored (b3_park_elide; blk = byte offset of the H block in the tile)
+template <bool PARK, bool ELIDE = false>
 __device__ __forceinline__ void b3_epilogue_eighth(f32x16 (&acc)[4], float *__restrict__ ht, uint32_t (&mt)[4], int pt, int h,
-                                                   Frag (&bh)[8], Frag (&bm)[8], Frag (&bl)[8], int t, int s2) {
+                                                   Frag (&bh)[8], Frag (&bm)[8], Frag (&bl)[8], int t, int s2, const B3Park &pk,
+                                                   uint32_t blk) {
 #pragma unroll
     for (int r = 8 * s2; r < 8 * s2 + 8; r++) acc[t][r] = relu_i(acc[t][r]);
-    if (PARK) {
+    if (PARK && !ELIDE) {
 #pragma unroll
         for (int r = 8 * s2; r < 8 * s2 + B3_PARK_STORES_EIGHTH; r++) PARK_STORE(acc[t][r], &ht[(32 * t + acc_row(r, h)) * TILE + pt]);
     }
@@ -220,6 +271,11 @@ __device__ __forceinline__ void b3_epilogue_eighth(f32x16 (&acc)[4], float *__re
 #pragma unroll
     for (int r = 8 * s2 + 7; r >= 8 * s2; r--) m = push_nz(m, acc[t][r]);
     mt[t] |= m << (8 * s2);
+    if (PARK && ELIDE) {
+        const B3Rows w = b3_rows(m);
+#pragma unroll
+        for (int r = 8 * s2; r < 8 * s2 + B3_PARK_STORES_EIGHTH; r++) b3_park_elide(acc[t][r], pk, blk, w, r - 8 * s2, t, r);
+    }
 #pragma unroll
     for (int e2 = 0; e2 < 4; e2++)
         split2(acc[t][8 * s2 + 2 * e2], acc[t][8 * s2 + 2 * e2 + 1], bh[2 * t + s2].u[e2], bm[2 * t + s2].u[e2], bl[2 * t + s2].u[e2]);
@@ -227,14 +283,14 @@ __device__ __forceinline__ void b3_epilogue_eighth(f32x16 (&acc)[4], float *__re
 }
 
 // the epilogue of output tiles T0, T0+1 only: ReLU, park, sign-mask halves, slices of k16 steps 2 T0 .. 2 T0 + 3
-template <int T0, bool PARK>
+template <int T0, bool PARK, bool ELIDE = false>
 __device__ __forceinline__ void b3_epilogue_half(f32x16 (&acc)[4], float *__restrict__ ht, uint32_t (&mt)[4], int pt, int h,
-                                                 Frag (&bh)[8], Frag (&bm)[8], Frag (&bl)[8]) {
+                                                 Frag (&bh)[8], Frag (&bm)[8], Frag (&bl)[8], const B3Park &pk, uint32_t blk) {
 #pragma unroll
     for (int t = T0; t < T0 + 2; t++) {
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[t][r] = relu_i(acc[t][r]);
-        if (PARK) {
+        if (PARK && !ELIDE) {
 #pragma unroll
             for (int r = 0; r < 16; r++) PARK_STORE(acc[t][r], &ht[(32 * t + acc_row(r, h)) * TILE + pt]);
         }
@@ -242,6 +298,11 @@ __device__ __forceinline__ void b3_epilogue_half(f32x16 (&acc)[4], float *__rest
 #pragma unroll
         for (int r = 15; r >= 0; r--) m = push_nz(m, acc[t][r]);
         mt[t] = m;
+        if (PARK && ELIDE) {
+            const B3Rows w = b3_rows(m);
+#pragma unroll
+            for (int r = 0; r < 16; r++) b3_park_elide(acc[t][r], pk, blk, w, r, t, r);
+        }
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++)
 #pragma unroll
@@ -404,7 +465,8 @@ __device__ __forceinline__ void b3_park_line_word(float *__restrict__ tile, int 
     if (pt == 31) reinterpret_cast<uint2 *>(tile + WARP_LINE_ROW * TILE)[idx * 2 + h] = make_uint2(lo, hi);
 }
 
-template <int NW, bool PARK>
+// ELIDE (round 9): the H rows without a non-zero are not stored; the line words, the sign masks and the encoding rows always are
+template <int NW, bool PARK, bool ELIDE = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
     const float *__restrict__ x, const int32_t *__restrict__ slot, const float *__restrict__ bias0_d,
     const float *__restrict__ bias0_t, const f32x4 *__restrict__ w3_d, const f32x4 *__restrict__ w3_t,
@@ -438,6 +500,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
         for (int k = 0; k < 20; k++) tile[(2 * k + h) * TILE + pt] = bin0[k];
     }
     uint2 *mk = PARK ? reinterpret_cast<uint2 *>(tile + WARP_HID_ROWS * TILE) : nullptr;
+    B3Park pk;
+    if (ELIDE) b3_park_tile<WARP_ACT_ROWS>(pk, tile, pt, h);
 
     for (int net = 0; net < 2; net++) {
         const f32x4 *wn = net ? w3_t : w3_d;
@@ -461,7 +525,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
         b3_slot_issue<B3_KH_F4, NT>(wn, B3_L0_F4 + B3_KH_F4, 0);           // L1.k1 -> slot 0
         b3_dma_fence();
         // layer 0's tiles 0, 1 here (a 72-MFMA layer has nothing to hide them under); its tiles 2, 3 under layer 1's Q1
-        b3_epilogue_half<0, PARK>(acc, ht, mt, pt, h, bh, bm, bl);
+        const uint32_t hb = (uint32_t)((64 + net * 640) * TILE * 4);      // the net's H1 block, bytes into the tile
+        b3_epilogue_half<0, PARK, ELIDE>(acc, ht, mt, pt, h, bh, bm, bl, pk, hb);
         __builtin_amdgcn_sched_barrier(0);
         // layers 1..4: 128 -> 128
         for (int l = 1; l <= 4; l++) {
@@ -475,7 +540,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 b3_step<0>(slot1, bh, bm, bl, acc, lane, c);
-                b3_epilogue_eighth<PARK>(acc, hp, mt, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1);
+                b3_epilogue_eighth<PARK, ELIDE>(acc, hp, mt, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1, pk, hb + (uint32_t)((l - 1) * 128 * TILE * 4));
             }
             b3_pin_slices<4>(bh, bm, bl);
             asm volatile("" : "+v"(mt[2]), "+v"(mt[3]));
@@ -511,7 +576,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 b3_step<2>(slot0, bh, bm, bl, acc, lane, 4 + c);
-                b3_epilogue_eighth<PARK>(acc, hl, mt, pt, h, bh, bm, bl, c >> 1, c & 1);
+                b3_epilogue_eighth<PARK, ELIDE>(acc, hl, mt, pt, h, bh, bm, bl, c >> 1, c & 1, pk, hb + (uint32_t)(l * 128 * TILE * 4));
             }
             b3_pin_slices<0>(bh, bm, bl);
             asm volatile("" : "+v"(mt[0]), "+v"(mt[1]));
@@ -535,7 +600,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             b3_l5_step(slot1, bh, bm, bl, o[0], lane, c);
-            b3_epilogue_eighth<PARK>(acc, ht + 4 * 128 * TILE, mt, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1);
+            b3_epilogue_eighth<PARK, ELIDE>(acc, ht + 4 * 128 * TILE, mt, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1, pk, hb + (uint32_t)(4 * 128 * TILE * 4));
         }
         b3_pin_slices<4>(bh, bm, bl);
         asm volatile("" : "+v"(mt[2]), "+v"(mt[3]));
@@ -573,9 +638,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 #define B3_NETT_F4 (B3_T5_F4 + 4 * B3_LH_F4 + B3_T0_F4)  // 29 184 float4 per net
 
 // masked accumulators -> parked dPre tile (PARK) + the next transposed layer's B operands
-template <bool PARK = true>
+// ELIDE: rows whose bit of pk.drop is set are not stored (b3_park_elide)
+template <bool PARK = true, bool ELIDE = false>
 __device__ __forceinline__ void b3_epilogue_bwd(const f32x16 (&acc)[4], uint2 m, float *__restrict__ dt, int pt, int h, Frag (&bh)[8],
-                                                Frag (&bm)[8], Frag (&bl)[8]) {
+                                                Frag (&bm)[8], Frag (&bl)[8], const B3Park &pk, uint32_t blk, const B3Rows (&rows)[2]) {
     mfma_results_settle();
 #pragma unroll
     for (int t = 0; t < 4; t++) {
@@ -583,7 +649,10 @@ __device__ __forceinline__ void b3_epilogue_bwd(const f32x16 (&acc)[4], uint2 m,
         float y[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) y[r] = mask_bit(mw, r, acc[t][r]);
-        if (PARK) {
+        if (PARK && ELIDE) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) b3_park_elide(y[r], pk, blk, rows[t >> 1], 16 * (t & 1) + r, t, r);
+        } else if (PARK) {
 #pragma unroll
             for (int r = 0; r < 16; r++) PARK_STORE(y[r], &dt[(32 * t + acc_row(r, h)) * TILE + pt]);
         }
@@ -596,20 +665,30 @@ __device__ __forceinline__ void b3_epilogue_bwd(const f32x16 (&acc)[4], uint2 m,
 }
 
 // backward flavour of b3_epilogue_eighth: registers 8 s2 .. 8 s2 + 7 of tile t masked by their ReLU bits -> parked dPre, slices
+template <bool ELIDE = false>
 __device__ __forceinline__ void b3_epilogue_bwd_eighth(f32x16 (&acc)[4], uint2 m, float *__restrict__ dt, int pt, int h, Frag (&bh)[8],
-                                                       Frag (&bm)[8], Frag (&bl)[8], int t, int s2) {
+                                                       Frag (&bm)[8], Frag (&bl)[8], int t, int s2, const B3Park &pk, uint32_t blk,
+                                                       const B3Rows (&rows)[2]) {
     const uint32_t mw = (t < 2 ? m.x : m.y) >> (16 * (t & 1));
 #pragma unroll
     for (int r = 8 * s2; r < 8 * s2 + 8; r++) acc[t][r] = mask_bit(mw, r, acc[t][r]);
+    if (ELIDE) {
 #pragma unroll
-    for (int r = 8 * s2; r < 8 * s2 + B3_PARK_STORES_EIGHTH; r++) PARK_STORE(acc[t][r], &dt[(32 * t + acc_row(r, h)) * TILE + pt]);
+        for (int r = 8 * s2; r < 8 * s2 + B3_PARK_STORES_EIGHTH; r++) b3_park_elide(acc[t][r], pk, blk, rows[t >> 1], 16 * (t & 1) + r, t, r);
+    } else {
+#pragma unroll
+        for (int r = 8 * s2; r < 8 * s2 + B3_PARK_STORES_EIGHTH; r++) PARK_STORE(acc[t][r], &dt[(32 * t + acc_row(r, h)) * TILE + pt]);
+    }
 #pragma unroll
     for (int e2 = 0; e2 < 4; e2++)
         split2(acc[t][8 * s2 + 2 * e2], acc[t][8 * s2 + 2 * e2 + 1], bh[2 * t + s2].u[e2], bm[2 * t + s2].u[e2], bl[2 * t + s2].u[e2]);
 }
 
 // PARK4 = false (round 6): dPre4 is not parked -- the layer-4 weight-gradient launch regenerates it (mlp.hip: wgrad_regen_b3_kernel)
-template <int NW, bool PARK4 = true>
+// ELIDE (round 9): every reader of this call's scratch goes by the line words; dPre_l is masked by H_(l+1)'s ReLU signs, so the
+// word of H_(l+1) -- the OR of the sign words this kernel holds anyway, over each lane half -- says which dPre_l rows are all zero,
+// and those are not stored.  dPre5's live rows carry no word and are always written.
+template <int NW, bool PARK4 = true, bool ELIDE = false>
 __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__restrict__ x, const float *__restrict__ g_deform,
                                                                  const float *__restrict__ g_topo, const f32x4 *__restrict__ w3T_d,
                                                                  const f32x4 *__restrict__ w3T_t, int n_bands,
@@ -627,6 +706,10 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
     const float *atile = acts + tile_id * (int64_t)(WARP_ACT_ROWS * TILE);
     float *dtile = dpre + tile_id * (int64_t)(WARP_DPRE_ROWS * TILE);
     float gx[3] = {0.f, 0.f, 0.f};
+    B3Park pk;
+    B3Rows rows[2];
+    uint32_t blk = 0;
+    if (ELIDE) b3_park_tile<WARP_DPRE_ROWS>(pk, dtile, pt, h);
 
     b3_stage_issue<B3_T5_F4, NW * 64>(w3T_d);
     for (int net = 0; net < 2; net++) {
@@ -666,7 +749,12 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
         b3_stage_issue<B3_LH_F4, NW * 64>(wt);
         b3_dma_fence();
         // dPre_4 from T5's output (the short first stage: nothing to hide it under)
-        b3_epilogue_bwd<PARK4>(acc, msk[4], dt + 4 * 128 * TILE, pt, h, bh, bm, bl);
+        if (ELIDE && PARK4) {
+            blk = (uint32_t)((net * 672 + 4 * 128) * TILE * 4);
+            rows[0] = b3_rows(msk[4].x);
+            rows[1] = b3_rows(msk[4].y);
+        }
+        b3_epilogue_bwd<PARK4, ELIDE>(acc, msk[4], dt + 4 * 128 * TILE, pt, h, bh, bm, bl, pk, blk, rows);
         for (int l = 4; l >= 1; l--) {
             // dH_l = W_l^T dPre_l in quarters (see the forward kernel): tiles 0, 1 are complete after the third quarter and
             // their half of dPre_{l-1} (mask by H_l's ReLU bits, park, slice) runs under the fourth quarter's MFMAs
@@ -674,6 +762,16 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
                 b3_stage_wait();                             // no parking stores behind this DMA: vmcnt(KEEP) would not cover it
             else
                 b3_stage_wait_keep<B3_KEEP_BWD>();           // behind the DMA: the 32 parking stores of tiles 2, 3
+            // (ELIDE: the layer's sign words are taken from the register array ONCE and held, so that the row bits add no second
+            // scratch read to the loop)
+            uint2 ml;
+            if (ELIDE) {
+                ml = msk[l - 1];
+                asm volatile("" : "+v"(ml.x), "+v"(ml.y));
+                blk = (uint32_t)((net * 672 + (l - 1) * 128) * TILE * 4);
+                rows[0] = b3_rows(ml.x);
+                rows[1] = b3_rows(ml.y);
+            }
             acc_zero<4>(acc);
             b3_quarter<0, 0>(lds_b3, bh, bm, bl, acc, lane);
             b3_quarter<2, 0>(lds_b3, bh, bm, bl, acc, lane);
@@ -682,7 +780,7 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 b3_quarter_step<2>(lds_b3, bh, bm, bl, acc, lane, 4 + c);
-                b3_epilogue_bwd_eighth(acc, msk[l - 1], dt + (l - 1) * 128 * TILE, pt, h, bh, bm, bl, c >> 1, c & 1);
+                b3_epilogue_bwd_eighth<ELIDE>(acc, ELIDE ? ml : msk[l - 1], dt + (l - 1) * 128 * TILE, pt, h, bh, bm, bl, c >> 1, c & 1, pk, blk, rows);
             }
             b3_pin_slices<0>(bh, bm, bl);
 #pragma unroll
@@ -702,7 +800,7 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
             b3_dma_fence();
 #pragma unroll
             for (int c = 0; c < 4; c++)
-                b3_epilogue_bwd_eighth(acc, msk[l - 1], dt + (l - 1) * 128 * TILE, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1);
+                b3_epilogue_bwd_eighth<ELIDE>(acc, ELIDE ? ml : msk[l - 1], dt + (l - 1) * 128 * TILE, pt, h, bh, bm, bl, 2 + (c >> 1), c & 1, pk, blk, rows);
         }
         if (g_x) {
             // d(enc features) = W0^T dPre0; rows ordered (kk = 16t + r, h = lane>>5).  Skipped when nobody asks for d/dx
@@ -1011,6 +1109,12 @@ static int b3_lds_opt_in() {
                 hipSuccess ||
             hipFuncSetAttribute((const void *)(warp_bwd_b3_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
                 hipSuccess ||
+            hipFuncSetAttribute((const void *)(warp_fwd_b3_kernel<8, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
+                hipSuccess ||
+            hipFuncSetAttribute((const void *)(warp_bwd_b3_kernel<8, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
+                hipSuccess ||
+            hipFuncSetAttribute((const void *)(warp_bwd_b3_kernel<8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
+                hipSuccess ||
             hipFuncSetAttribute((const void *)warp_fwd_b3_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
                 hipSuccess ||
             hipFuncSetAttribute((const void *)warp_bwd_b3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS_BYTES) !=
@@ -1055,13 +1159,15 @@ extern "C" int64_t mh_warp_w3T_bytes(void) { return (int64_t)B3_NETT_F4 * 16; }
 // tile per SIMD and twice the CUs.
 static inline bool b3_small_batch(int64_t M) { return M <= (int64_t)BLOCK_PTS * mh_cu_count(); }
 
-extern "C" int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
-                                   int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4,
-                                   void *stream) {
+// elided: the forward elided this scratch (mh_warp_fwd_b3_elide); the dPre rows under the same words are not written either
+static int warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
+                            int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4, bool elided,
+                            void *stream) {
     if (M == 0) return MH_OK;
     if (M < 0 || !x || !w3T_d || !w3T_t || !acts || !dpre || n_bands < 0 || n_bands > 6) return MH_ERR_ARG;
     const bool small = b3_small_batch(M);
     if (skip_dpre4 && small) return MH_ERR_ARG;       // (mh_warp_regen_dpre4(M) is never set for such a batch)
+    if (elided && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;      // only the per-layer weight-gradient kernels go by the words
     const int64_t blocks = small ? (M + BLOCK_PTS - 1) / BLOCK_PTS : (M + B3_BLOCK_PTS - 1) / B3_BLOCK_PTS;
     if (blocks > 0x7fffffffLL) return MH_ERR_ARG;
     if (b3_lds_opt_in() != MH_OK) return MH_ERR_LAUNCH;
@@ -1069,6 +1175,14 @@ extern "C" int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const 
         hipLaunchKernelGGL(warp_bwd_b3_kernel<4>, dim3((unsigned)blocks), dim3(256), B3_LDS_BYTES, mh_stream(stream), x, g_deform,
                            g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t), (int)n_bands,
                            acts, dpre, g_x, M, mh_mlp_tiles(M));
+    else if (elided && skip_dpre4)
+        hipLaunchKernelGGL((warp_bwd_b3_kernel<8, false, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
+                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
+    else if (elided)
+        hipLaunchKernelGGL((warp_bwd_b3_kernel<8, true, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
+                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
     else if (skip_dpre4)
         hipLaunchKernelGGL((warp_bwd_b3_kernel<8, false>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream), x,
                            g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
@@ -1080,11 +1194,23 @@ extern "C" int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const 
     MH_CHECK_LAUNCH();
     return MH_OK;
 }
+extern "C" int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
+                                   int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4,
+                                   void *stream) {
+    return warp_bwd_data_b3(x, g_deform, g_topo, w3T_d, w3T_t, n_bands, acts, dpre, g_x, M, skip_dpre4, false, stream);
+}
+extern "C" int mh_warp_bwd_data_b3_elide(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d,
+                                         const void *w3T_t, int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M,
+                                         int32_t skip_dpre4, int32_t elided, void *stream) {
+    return warp_bwd_data_b3(x, g_deform, g_topo, w3T_d, w3T_t, n_bands, acts, dpre, g_x, M, skip_dpre4, elided != 0, stream);
+}
 
-extern "C" int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                              const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
-                              float *out_topo, float *acts, int64_t M, void *stream) {
+// elide: the H rows without a non-zero are not written; every reader of this scratch must then go by the line words
+static int warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
+                       const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform, float *out_topo,
+                       float *acts, int64_t M, bool elide, void *stream) {
     if (M == 0) return MH_OK;
+    if (elide && (!acts || M < 0 || !mh_warp_regen_dpre4(M))) return MH_ERR_ARG;      // only the per-layer weight-gradient kernels go by the words
     if (M < 0 || !x || !bias0_d || !bias0_t || !w3_d || !w3_t || !bias_d || !bias_t || !out_deform || !out_topo || n_bands < 0 ||
         n_bands > 6)
         return MH_ERR_ARG;
@@ -1102,7 +1228,11 @@ extern "C" int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *
         else
             B3_FWD_LAUNCH(4, false, 256);
     } else {
-        if (acts)
+        if (acts && elide)
+            hipLaunchKernelGGL((warp_fwd_b3_kernel<8, true, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
+                               x, slot, bias0_d, bias0_t, reinterpret_cast<const f32x4 *>(w3_d), reinterpret_cast<const f32x4 *>(w3_t),
+                               bias_d, bias_t, (int)n_bands, out_deform, out_topo, acts, M, mh_mlp_tiles(M));
+        else if (acts)
             B3_FWD_LAUNCH(8, true, B3_THREADS);
         else
             B3_FWD_LAUNCH(8, false, B3_THREADS);
@@ -1110,4 +1240,14 @@ extern "C" int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *
 #undef B3_FWD_LAUNCH
     MH_CHECK_LAUNCH();
     return MH_OK;
+}
+extern "C" int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
+                              const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                              float *out_topo, float *acts, int64_t M, void *stream) {
+    return warp_fwd_b3(x, slot, bias0_d, bias0_t, w3_d, w3_t, bias_d, bias_t, n_bands, out_deform, out_topo, acts, M, false, stream);
+}
+extern "C" int mh_warp_fwd_b3_elide(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
+                                    const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                                    float *out_topo, float *acts, int64_t M, int32_t elide, void *stream) {
+    return warp_fwd_b3(x, slot, bias0_d, bias0_t, w3_d, w3_t, bias_d, bias_t, n_bands, out_deform, out_topo, acts, M, elide != 0, stream);
 }

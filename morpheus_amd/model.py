@@ -557,7 +557,8 @@ class scene_representation(nn.Module):
         tu, slot, identity = self._slots(t, frame_slots)
         opnd, code_w = self._warp_operands()
         bias0_d, bias0_t = self._warp_bias0(tu, code_w)                   # per-frame first-layer bias
-        deform, topo = ops.warp_mlp(x, slot, bias0_d, bias0_t, self._n_bands(), opnd, slots_are_identity=identity)
+        # elide: nobody but this call's own backward reads its parked tiles, so their all-zero lines need not be written
+        deform, topo = ops.warp_mlp(x, slot, bias0_d, bias0_t, self._n_bands(), opnd, slots_are_identity=identity, elide=True)
         app_code = None
         if self.use_app:                                                  # model.py:418-420: one code row per sample
             rows = self.app_code.sample(tu[:, None])                      # [F,48], F = distinct frames / slots

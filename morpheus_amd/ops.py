@@ -1429,7 +1429,7 @@ class _WarpMLP(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, slot, bias0_d, bias0_t, token, n_bands, opnd, slots_are_identity=False):
+    def forward(ctx, x, slot, bias0_d, bias0_t, token, n_bands, opnd, slots_are_identity=False, elide=False):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(x, bias0_d, bias0_t)
         lib = _lib.load()
@@ -1441,7 +1441,17 @@ class _WarpMLP(torch.autograd.Function):
         deform, topo = torch.empty(M, 3, device=dev), torch.empty(M, 2, device=dev)
         b0d, b0t = bias0_d.detach().contiguous(), bias0_t.detach().contiguous()
         slot_c = None if slot is None else slot.contiguous()
-        if opnd.w3 is not None:
+        # Eliding (include/morpheus_hip.h): decided ONCE, here, and carried to the backward, which asks no switch again -- whoever
+        # wrote the scratch without its all-zero lines is bound to read it by the words.  Several slots: the backward reads dPre0's
+        # rows straight out of the scratch (per_pt_d / per_pt_t), so such a call elides nothing.
+        level = 0
+        if elide and need_grad and opnd.w3 is not None and opnd.wT3 is not None and bias0_d.shape[0] == 1:
+            level = lib.mh_warp_elides(M)
+        ctx.elided, ctx.elided_fwd = level >= 1, level >= 2
+        if ctx.elided_fwd:
+            _timed("mh_warp_fwd_b3_elide", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
+                   n_bands, ptr(deform), ptr(topo), ptr(acts), M, 1, key="mh_warp_fwd")
+        elif opnd.w3 is not None:
             _timed("mh_warp_fwd_b3", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
                    n_bands, ptr(deform), ptr(topo), ptr(acts), M, key="mh_warp_fwd")
         else:
@@ -1470,7 +1480,10 @@ class _WarpMLP(torch.autograd.Function):
         # b3, large batches: dPre4 (16 KB of a tile's 172) is not parked, the layer-4 weight-gradient launches make it again from
         # the incoming gradient, the ReLU sign words and the T5 slices -- the same bits (include/morpheus_hip.h: mh_warp_wgrad_b3)
         regen = bool(ctx.b3 and REGEN_DPRE4 and lib.mh_warp_regen_dpre4(M))
-        if ctx.b3:
+        if ctx.elided:
+            _timed("mh_warp_bwd_data_b3_elide", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre),
+                   ptr(g_x), M, int(regen), 1, key="mh_warp_bwd_data")
+        elif ctx.b3:
             _timed("mh_warp_bwd_data_b3", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre),
                    ptr(g_x), M, int(regen), key="mh_warp_bwd_data")
         else:
@@ -1482,8 +1495,12 @@ class _WarpMLP(torch.autograd.Function):
             raw_len = dw_len + sum(_WARP_WG[3])
             assert raw_len == jp.raw_len
             raw = torch.empty(raw_len, device=dev) if M > 0 else torch.zeros(raw_len, device=dev)      # (an empty call writes nothing)
-            _timed("mh_warp_wgrad_b3", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), ptr(ws),
-                   ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
+            if ctx.elided:
+                _timed("mh_warp_wgrad_b3_elide", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), 1, ptr(ws),
+                       ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
+            else:
+                _timed("mh_warp_wgrad_b3", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), ptr(ws),
+                       ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
         else:
             raw = _wgrad(lib, acts, dpre, WARP_ACT_ROWS * 32, WARP_DPRE_ROWS * 32, _WARP_WG[0], _WARP_WG[1], _WARP_WG[2],
                          _WARP_WG[3], n_tiles, dev, "warp", b3=False, in_live=_WARP_WG[4], out_live=_WARP_WG[5])
@@ -1501,7 +1518,7 @@ class _WarpMLP(torch.autograd.Function):
                 idx = slot.long()
                 g_b0d = torch.zeros(ctx.n_slots, 128, device=dev).index_add_(0, idx, per_pt_d)
                 g_b0t = torch.zeros(ctx.n_slots, 128, device=dev).index_add_(0, idx, per_pt_t)
-        return (g_x, None, g_b0d, g_b0t, raw, None, None, None)
+        return (g_x, None, g_b0d, g_b0t, raw, None, None, None, None)
 
 
 def _warp_wg_geometry():
@@ -1521,10 +1538,12 @@ def _warp_wg_geometry():
 
 _WARP_WG = _warp_wg_geometry()
 
-def warp_mlp(x, slot, bias0_d, bias0_t, n_bands, opnd: MLPOperands, slots_are_identity: bool = False):
+def warp_mlp(x, slot, bias0_d, bias0_t, n_bands, opnd: MLPOperands, slots_are_identity: bool = False, elide: bool = False):
     """slots_are_identity: slot[i] == i for every sample (bias0 rows are per sample): the first-layer bias gradient is then
-    the per-point dPre0 rows themselves; any other slot map goes through index_add_."""
-    return _WarpMLP.apply(x, slot, bias0_d, bias0_t, opnd.token, n_bands, opnd, slots_are_identity)
+    the per-point dPre0 rows themselves; any other slot map goes through index_add_.
+    elide: the call MAY leave all-zero parked lines unwritten where that pays (b3, one slot, a batch of the per-layer weight-gradient
+    path, both switches on: mh_warp_elides) -- same outputs and gradients; without it every line of the scratch is written."""
+    return _WarpMLP.apply(x, slot, bias0_d, bias0_t, opnd.token, n_bands, opnd, slots_are_identity, elide)
 
 
 def _field_fwd(lib, xc, fs, fc, tp, beta_c, n_bands, with_color, opnd, need_grad):
