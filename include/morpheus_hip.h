@@ -25,14 +25,14 @@
  *   mh_warp_* / mh_field_*      models/model.py:412-437 (warp), :273-307 (get_sigma_albedo),
  *                               models/decoders.py:59-64, models/encodings.py:35-57,
  *                               models/density.py:22-31 -- plain PyTorch in the reference
- *   mh_mlp_wgrad                the weight-gradient GEMMs autograd ran for those MLPs
+ *   mh_warp_wgrad               the weight-gradient GEMMs autograd ran for the warp MLPs
  *   mh_adam_step / mh_adan_step torch.optim.Adam (morpheus.py:154-155) / models/optimizer.py:101-256 (Adan, morpheus.py:146-150)
  *   mh_freq_encode_fwd / _bwd   external/encoders/freqencoder/src/freqencoder.cu:28-94 (freq.py:15-52), and the progressive
  *                               max_level of FreqEncoder_torch, models/encodings.py:35-57
  *   mh_sh_encode_fwd / _bwd     external/encoders/shencoder/src/shencoder.cu:28-end (sphere_harmonics.py:14-58)
- * The warp / field entries exist in two arithmetic forms of the SAME interface -- fp32 in, fp32 out, same parked tiles:
- * native fp32 MFMA (no suffix) and exact three-way bf16 splits (_b3: fp32-faithful, what the Python side calls by default --
- * morpheus_amd/ops.py, MORPHEUS_MLP); mh_b3_slice cuts the weight operands of the latter.
+ * The warp / field entries run in two arithmetic forms behind ONE interface -- fp32 in, fp32 out, same parked tiles -- chosen by
+ * their `arith` argument: native fp32 MFMA (MH_ARITH_F32) and exact three-way bf16 splits (MH_ARITH_B3: fp32-faithful, what the
+ * Python side calls by default -- morpheus_amd/ops.py, MORPHEUS_MLP); mh_b3_slice cuts the weight operands of the latter.
  */
 #ifndef MORPHEUS_HIP_H
 #define MORPHEUS_HIP_H
@@ -48,7 +48,7 @@ extern "C" {
 #define MH_ERR_LAUNCH 2  /* hipGetLastError() != hipSuccess after the launch */
 #define MH_ERR_OVERFLOW 3 /* a result count does not fit the output's int32 indices (mh_mc_count) */
 
-#define MH_ABI_VERSION 9   /* 9: emb_acc of mh_grid_encode_bwd_binned (order-independent table gradient), later mh_subdiv_count / mh_subdiv_emit (additive: the number stays); 8: mh_smooth_points_*, mh_bg_blend_* (the last operator chains inside render_rays), live-row counts of mh_mlp_wgrad(_b3), mh_warp_wgrad_b3 / mh_warp_regen_dpre4 and skip_dpre4 of mh_warp_bwd_data_b3; 7: the fp16 x 2 (_h2) entry points removed (not fp32-faithful; round-5 verdict item 8); 6: mh_grid_stage_min_points, mh_grid_encode_fwd_binned; 5: accumulate flags of mh_grid_encode_bwd_binned (d/dx) and mh_field_bwd_fused (raw; d(beta) is raw[24 928]); 4: mh_graph_*, mh_masked_mean_*, mh_ortho_perturb_*, mh_pose_apply_*, mh_render_loss_*; 3: round-3 prune (measured-loser entry points removed), n_valid in mh_sdf_losses_* */
+#define MH_ABI_VERSION 10   /* 10: one MLP entry point per pass with an `arith` argument (mh_warp_fwd, mh_warp_bwd_data, mh_warp_wgrad, mh_field_fwd, mh_field_bwd_fused; MH_ARITH_F32 / MH_ARITH_B3) and mh_warp_raw_floats; removed: mh_warp_fwd_b3, mh_warp_fwd_b3_elide, mh_warp_bwd_data_b3, mh_warp_bwd_data_b3_elide, mh_mlp_wgrad, mh_mlp_wgrad_b3, mh_mlp_wgrad_workspace_floats, mh_warp_wgrad_b3, mh_warp_wgrad_b3_elide, mh_field_fwd_b3, mh_field_bwd_fused_b3; 9: emb_acc of mh_grid_encode_bwd_binned (order-independent table gradient), later mh_subdiv_count / mh_subdiv_emit (additive: the number stays); 8: mh_smooth_points_*, mh_bg_blend_* (the last operator chains inside render_rays), live-row counts of mh_mlp_wgrad and mh_mlp_wgrad_b3, mh_warp_wgrad_b3 / mh_warp_regen_dpre4 and skip_dpre4 of mh_warp_bwd_data_b3; 7: the fp16 x 2 (_h2) entry points removed (not fp32-faithful; round-5 verdict item 8); 6: mh_grid_stage_min_points, mh_grid_encode_fwd_binned; 5: accumulate flags of mh_grid_encode_bwd_binned (d/dx) and mh_field_bwd_fused (raw; d(beta) is raw[24 928]); 4: mh_graph_*, mh_masked_mean_*, mh_ortho_perturb_*, mh_pose_apply_*, mh_render_loss_*; 3: round-3 prune (measured-loser entry points removed), n_valid in mh_sdf_losses_* */
 #define MH_MAX_LEVELS 32
 #define MH_TILE 32       /* sample points per wavefront tile in the MLP kernels */
 
@@ -283,143 +283,145 @@ int mh_sdf_losses_bwd(const float *pred_sdf, const float *t_starts, const float 
 int mh_sample_positions_bwd(const float *g_xyz, const float *t_starts, const float *t_ends, const int32_t *ray_start,
                             const int32_t *ray_cnt, int32_t N, float *g_o, float *g_d, void *stream);
 
-/* ---- fused tiny-MLP evaluators on fp32 MFMA (v_mfma_f32_32x32x2_f32) -------------------------
- * Weight operands are PRE-PACKED by the host into the MFMA A-fragment order (see
- * morpheus_amd/packing.py): for layer l, tile mt, k-quad q: float4 per lane.  `wpack` is the
- * concatenation of all layers of the net(s); layer geometry is fixed by the kernel.
- * Activation scratch ("acts") is written by the forward when acts != NULL and consumed by the
- * backward: per 32-point tile, per layer, feature-major [F][32] fp32 (the weight-gradient GEMM's operand),
- * followed by the hidden layers' ReLU sign masks (one bit per lane and output row) that backward-data reads
- * instead of the activations themselves.
+/* ---- fused tiny-MLP evaluators: the warp nets (deform_net + topo_net) and the field nets (sdf_net + color_net) ---------------
+ * One entry point per pass.  Values, parked tiles, accumulation and results are fp32 in either arithmetic; `arith` says how a
+ * product reaches the matrix cores and which pack the weight operand (a `const void *`) is:
+ *   MH_ARITH_F32 (0): the native fp32 MFMA (v_mfma_f32_32x32x2_f32; csrc/mlp.hip).  Weights are PRE-PACKED by the host into the
+ *     MFMA A-fragment order (morpheus_amd/packing.py): for layer l, tile mt, k-quad q: float4 per lane; a pack is the
+ *     concatenation of all layers of the net(s) (mh_*_wpack_floats / mh_*_wpackT_floats floats), layer geometry fixed by the kernel.
+ *   MH_ARITH_B3 (1): exact fp32 products on the bf16 matrix pipe (csrc/mlp_b3.hip; what the Python side calls by default --
+ *     morpheus_amd/ops.py, MORPHEUS_MLP).  Every fp32 operand is cut into three bf16 slices (hi + mid + lo == x exactly) and a
+ *     product is the six significant cross terms through v_mfma_f32_32x32x16_bf16 with fp32 accumulation: fp32-grade results (what
+ *     is dropped is <= 3 * 2^-24 of a product), 6/16 of the fp32-MFMA cycles.  Only the weight operand has its own pack, the
+ *     SLICED one (mh_*_w3_bytes / mh_*_w3T_bytes bytes), cut by mh_b3_slice; activations and gradients are sliced on the fly.
+ *   Any other value: MH_ERR_ARG.  Both forms of a pass take the same arguments otherwise, give the same outputs up to fp32
+ *   summation order, and write and read the same parked tiles -- a scratch parked by one may be consumed by the other.
+ * Activation scratch ("acts") is written by the forward when acts != NULL and consumed by the backward: per 32-point tile, per
+ * layer, feature-major [F][32] fp32 (the weight-gradient GEMM's operand), followed by the hidden layers' ReLU sign masks (one bit
+ * per lane and output row) that backward-data reads instead of the activations themselves.
  *
- * mh_warp_fwd: deform = deform_net([freq(x), code]), topo = topo_net(same)
- *   x [M,3]; slot [M] int32 -> row of bias0 (per-frame first-layer bias  W0[:,39:87].code + b0,
- *   computed by the caller; one row per distinct frame time); bias0_{d,t}: [n_slots,128];
- *   n_bands: frequency bands kept (progressive max_level), 0..6;
- *   out_deform [M,3]; out_topo [M,2];  acts: NULL or scratch of mh_warp_acts_floats(M) floats. */
+ * mh_b3_slice: fp32 fragments in the 32x32x16 order (packing.py: fwd3_index; per layer [out tile][k16 step][lane][8]) ->
+ *   per layer three bf16 planes [hi | mid | lo][out tile][k16 step][lane][8 bf16].  src_off / n in floats (n % 8 == 0),
+ *   dst_off in 16-byte units; host arrays of n_layers entries (<= 16).
+ * Sliced packs: mh_warp_w3_bytes() per warp net (layer 0 padded to whole 512 x 16-byte DMA rounds), mh_warp_w3T_bytes() per warp
+ *   net TRANSPOSED (T5, T4..T1, T0; packing.py: bwd3_index), mh_field_w3_bytes() for the six field layers (resident in LDS:
+ *   packing.py field_joint_packer().b3_layers), mh_field_w3T_bytes() for them transposed (field_joint_packer().b3T_layers:
+ *   TC2 | TC1 | TC0 | TS2 | TS1 | TS0). */
+#define MH_ARITH_F32 0
+#define MH_ARITH_B3 1
 int64_t mh_mlp_tiles(int64_t M);        /* 32-point tiles the kernels touch: 4 * ceil(M/128) */
 int64_t mh_warp_acts_floats(int64_t M);
 int64_t mh_warp_dpre_floats(int64_t M);
 int64_t mh_warp_wpack_floats(void);   /* per net, forward pack */
 int64_t mh_warp_wpackT_floats(void);  /* per net, transposed pack */
-int mh_warp_fwd(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t,
-                const float *wpack_d, const float *wpack_t, const float *bias_d, const float *bias_t,
-                int32_t n_bands, float *out_deform, float *out_topo, float *acts, int64_t M, void *stream);
-/* ---- the same networks with exact fp32 products on the bf16 matrix pipe (csrc/mlp_b3.hip) ------
- * Every fp32 operand is cut into three bf16 slices (hi + mid + lo == x exactly) and a product is the six significant
- * cross terms through v_mfma_f32_32x32x16_bf16 with fp32 accumulation: fp32-grade results (what is dropped is <= 3 * 2^-24
- * of a product), 6/16 of the fp32-MFMA cycles.  Values, parked tiles and the C-ABI stay fp32; only the weight operand has
- * its own pack.
- *
- * mh_b3_slice: fp32 fragments in the 32x32x16 order (packing.py: fwd3_index; per layer [out tile][k16 step][lane][8]) ->
- *   per layer three bf16 planes [hi | mid | lo][out tile][k16 step][lane][8 bf16].  src_off / n in floats (n % 8 == 0),
- *   dst_off in 16-byte units; host arrays of n_layers entries (<= 16).
- * mh_warp_fwd_b3: mh_warp_fwd with w3_{d,t} = one net's sliced pack (mh_warp_w3_bytes() bytes: layer 0 padded to whole
- *   512 x 16-byte DMA rounds).  Same outputs, same parked tiles (mh_warp_bwd_data / mh_mlp_wgrad consume them).
- * mh_warp_bwd_data_b3: mh_warp_bwd_data with the TRANSPOSED sliced packs (mh_warp_w3T_bytes() bytes per net: T5, T4..T1,
- *   T0; packing.py: bwd3_index).  Same dPre tiles, same g_x.  skip_dpre4 = 1: the 128 dPre4 rows of both nets (16 KB of a tile's
- *   172) are NOT written -- mh_warp_wgrad_b3(regen_dpre4 = 1) makes them again from the incoming gradient, the ReLU sign words and
- *   the T5 slices, bit for bit (dPre4 = relu'(H5) W5^T dPre5 and dPre5 IS the incoming gradient); allowed when
- *   mh_warp_regen_dpre4(M) says so (the large-batch weight-gradient path).
- * mh_warp_wgrad_b3: mh_mlp_wgrad_b3 for the 12 layers of the two warp nets, their tile geometry on this side of the ABI; g_deform /
- *   g_topo / w3T_*: what mh_warp_bwd_data_b3 was given (read only with regen_dpre4 = 1; the gradients may be NULL = zero);
- *   workspace: mh_warp_wgrad_workspace_floats(M) floats; dw_raw / db_raw as mh_mlp_wgrad. */
-/* mh_field_fwd_b3: mh_field_fwd with the sliced pack of the six field layers (mh_field_w3_bytes() bytes, resident in LDS:
- *   packing.py field_joint_packer().b3_layers).  Same outputs, same parked tiles (mh_field_bwd_fused consumes them). */
-int64_t mh_field_w3_bytes(void);
-int mh_field_fwd_b3(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const void *w3,
-                    const float *bias, const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma,
-                    float *albedo, float *acts, int64_t M, void *stream);
-int mh_b3_slice(const float *src, void *dst, int32_t n_layers, const int32_t *src_off_host, const int32_t *n_host,
-                const int32_t *dst_off_f4_host, void *stream);
 int64_t mh_warp_w3_bytes(void);
 int64_t mh_warp_w3T_bytes(void);
-int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
-                        int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4, void *stream);
-int32_t mh_warp_regen_dpre4(int64_t M);
-int64_t mh_warp_wgrad_workspace_floats(int64_t M);
-int mh_warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
-                     const void *w3T_t, int32_t regen_dpre4, float *workspace, float *dw_raw, float *db_raw, int64_t M, void *stream);
-/* Line words: mh_warp_fwd_b3 parks, in the dead rows of the tile's H0 block (from row 40 on: [net][hidden layer 1..5][half h]
+int64_t mh_field_acts_floats(int64_t M);
+int64_t mh_field_wpack_floats(void);
+int64_t mh_field_wpackT_floats(void);
+int64_t mh_field_w3_bytes(void);
+int64_t mh_field_w3T_bytes(void);
+int mh_b3_slice(const float *src, void *dst, int32_t n_layers, const int32_t *src_off_host, const int32_t *n_host,
+                const int32_t *dst_off_f4_host, void *stream);
+
+/* Line words and eliding (MH_ARITH_B3 only; every eliding flag with MH_ARITH_F32 is MH_ERR_ARG).
+ * Line words: the b3 warp forward parks, in the dead rows of the tile's H0 block (from row 40 on: [net][hidden layer 1..5][half h]
  * uint64, 160 bytes), which of the tile's parked rows carry a non-zero: bit 16 t + r of half h <-> row 32 t + (r & 3) + 8 (r >> 2)
- * + 4 h of that layer's H block.  The per-layer kernels of mh_warp_wgrad_b3 (large batches) fetch a zero line in place of a row
+ * + 4 h of that layer's H block.  The per-layer kernels of mh_warp_wgrad (large batches) fetch a zero line in place of a row
  * whose bit is 0 -- of an H block and of the dPre block masked by the same ReLU signs; every result keeps its bits.
  * mh_warp_skip_zero_lines: process-wide switch of that skipping (1 = on, the default; 0 = every row is fetched; set < 0: query
- * only).  Returns the value in force.  The words are parked either way. */
-int64_t mh_warp_skip_zero_lines(int64_t set);
-int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                   const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
-                   float *out_topo, float *acts, int64_t M, void *stream);
-/* Eliding: a writer that does not send an all-zero parked line (a row whose word bit is 0) to memory.  The entries above write
- * every line, and whoever reads whole tiles may rely on it.  The *_elide entries carry one flag per call:
- * mh_warp_fwd_b3_elide(elide = 1): the H rows without a non-zero are NOT written; the line words, the sign masks and the
- *   encoding rows always are.  Same outputs.
- * mh_warp_bwd_data_b3_elide(elided = 1): the dPre rows of layers 0..4 whose bit is 0 are NOT written and hold whatever the scratch
+ * only).  Returns the value in force.  The words are parked either way.
+ * Eliding: a writer that does not send an all-zero parked line (a row whose word bit is 0) to memory.  A call with its flag at 0
+ * writes every line, and whoever reads whole tiles may rely on it.  One flag per call:
+ * mh_warp_fwd(elide = 1): the H rows without a non-zero are NOT written; the line words, the sign masks and the encoding rows
+ *   always are.  Same outputs.  Needs acts.
+ * mh_warp_bwd_data(elided = 1): the dPre rows of layers 0..4 whose bit is 0 are NOT written and hold whatever the scratch
  *   held before (dPre5's live rows are always written; dPre4 follows skip_dpre4).  g_x keeps its bits.
- * mh_warp_wgrad_b3_elide(elided = 1): the tiles were written by an eliding call, so the launches go by the words whatever
+ * mh_warp_wgrad(elided = 1): the tiles were written by an eliding call, so the launches go by the words whatever
  *   mh_warp_skip_zero_lines says at that moment -- every gradient keeps its bits.
- * elided = 1 needs mh_warp_regen_dpre4(M) (the per-layer weight-gradient kernels: the merged small-batch kernels read every row),
- * else MH_ERR_ARG; a flag of 0 is the entry without the suffix.  The caller decides once, at forward time, with mh_warp_elides(M),
- * and whoever elided a scratch hands it only to *_elide entries with elided = 1 (morpheus_amd/ops.py: warp_mlp(elide=True) carries
- * the decision to its backward in the autograd ctx).
+ * A flag of 1 needs mh_warp_regen_dpre4(M) (the per-layer weight-gradient kernels: the merged small-batch kernels read every row),
+ * else MH_ERR_ARG.  The caller decides once, at forward time, with mh_warp_elides(M), and whoever elided a scratch hands it on
+ * only with elided = 1 (morpheus_amd/ops.py: warp_mlp(elide=True) carries the decision to its backward in the autograd ctx).
  * mh_warp_elides(M): what a call on M points may elide: 0 = nothing (no mh_warp_regen_dpre4(M), or mh_warp_skip_zero_lines off),
  *   else the value of mh_warp_elide_zero_lines.
  * mh_warp_elide_zero_lines: process-wide switch for the A/B: 2 = forward and backward-data elide (the default), 1 = backward-data
  *   only, 0 = no call elides; set < 0: query only.  Returns the value in force.  MORPHEUS_WARP_ELIDE_ZERO_LINES sets it when the
- *   library is loaded. */
+ *   library is loaded.
+ * mh_warp_regen_dpre4(M): 1 when a call on M points takes the large-batch weight-gradient path (one launch per layer), the only
+ *   one that can make dPre4 again; see mh_warp_bwd_data. */
+int64_t mh_warp_skip_zero_lines(int64_t set);
 int64_t mh_warp_elide_zero_lines(int64_t set);
 int32_t mh_warp_elides(int64_t M);
-int mh_warp_fwd_b3_elide(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                         const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
-                         float *out_topo, float *acts, int64_t M, int32_t elide, void *stream);
-int mh_warp_bwd_data_b3_elide(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
-                              int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4,
-                              int32_t elided, void *stream);
-int mh_warp_wgrad_b3_elide(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
-                           const void *w3T_t, int32_t regen_dpre4, int32_t elided, float *workspace, float *dw_raw, float *db_raw,
-                           int64_t M, void *stream);
-/* backward-data: consumes g_deform [M,3], g_topo [M,2] (either may be NULL = zero), acts from the
- * forward and the TRANSPOSED packs; writes g_x [M,3] (d/dx through the frequency encoding; pass NULL when the
- * sample positions carry no gradient and the first-layer transposed GEMM is skipped) and
- * dpre scratch (same geometry as acts) for mh_mlp_wgrad. */
-int mh_warp_bwd_data(const float *x, const float *g_deform, const float *g_topo, const float *wpackT_d,
-                     const float *wpackT_t, int32_t n_bands, const float *acts, float *dpre, float *g_x,
-                     int64_t M, void *stream);
+int32_t mh_warp_regen_dpre4(int64_t M);
+
+/* mh_warp_fwd: deform = deform_net([freq(x), code]), topo = topo_net(same)
+ *   x [M,3]; slot [M] int32 -> row of bias0 (per-frame first-layer bias  W0[:,39:87].code + b0,
+ *   computed by the caller; one row per distinct frame time); bias0_{d,t}: [n_slots,128];
+ *   w_{d,t}: one net's forward pack of `arith`;  n_bands: frequency bands kept (progressive max_level), 0..6;
+ *   out_deform [M,3]; out_topo [M,2];  acts: NULL or scratch of mh_warp_acts_floats(M) floats;  elide: see above. */
+int mh_warp_fwd(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w_d, const void *w_t,
+                const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform, float *out_topo, float *acts,
+                int64_t M, int32_t arith, int32_t elide, void *stream);
+/* mh_warp_bwd_data: consumes g_deform [M,3], g_topo [M,2] (either may be NULL = zero), acts from the forward and the TRANSPOSED
+ *   packs wT_{d,t} of `arith`; writes g_x [M,3] (d/dx through the frequency encoding; pass NULL when the sample positions carry no
+ *   gradient and the first-layer transposed GEMM is skipped) and dpre scratch (mh_warp_dpre_floats(M) floats) for mh_warp_wgrad.
+ *   skip_dpre4 = 1 (MH_ARITH_B3 only, else MH_ERR_ARG): the 128 dPre4 rows of both nets (16 KB of a tile's 172) are NOT written --
+ *   mh_warp_wgrad(regen_dpre4 = 1) makes them again from the incoming gradient, the ReLU sign words and the T5 slices, bit for bit
+ *   (dPre4 = relu'(H5) W5^T dPre5 and dPre5 IS the incoming gradient); allowed when mh_warp_regen_dpre4(M) says so (the
+ *   large-batch weight-gradient path).  elided: see above. */
+int mh_warp_bwd_data(const float *x, const float *g_deform, const float *g_topo, const void *wT_d, const void *wT_t,
+                     int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t arith, int32_t skip_dpre4,
+                     int32_t elided, void *stream);
+/* mh_warp_wgrad: the weight gradients of the 12 layers of the two warp nets from the tiles the two calls above parked (their
+ *   geometry is on this side of the ABI):  dW_l[out][in] = sum_pts dpre_l[out][pt] * act_l[in][pt],  db_l[out] = sum_pts dpre_l[out][pt].
+ *   MFMA launches (one per layer for large batches, one or two for all layers otherwise) write per-chunk partials into `workspace`
+ *   (mh_warp_wgrad_workspace_floats(M) floats), one reduction launch sums them into raw (mh_warp_raw_floats() floats) =
+ *   [dW of deform layers 0..5 | topo layers 0..5][db of the same twelve], feature counts padded to multiples of 32, in tile-row
+ *   order (the caller maps rows back to the natural layout, morpheus_amd/packing.py).
+ *   Live rows: 40 of the first layer's 64 input rows and 3 | 2 of the last layer's 32 dPre rows carry values.  Rows behind them
+ *   are never read -- the producing kernels do not write them -- and the dW rows / columns of those pad features are unspecified
+ *   (the caller's row map does not gather them).
+ *   MH_ARITH_B3: both fp32 operands are sliced on the fly; g_deform / g_topo / w3T_{d,t}: what mh_warp_bwd_data was given (the
+ *   packs must not be NULL; the rest is read only with regen_dpre4 = 1, and the gradients may be NULL = zero).  regen_dpre4,
+ *   elided: see above.  MH_ARITH_F32: regen_dpre4, elided and those four pointers must be 0 / NULL, else MH_ERR_ARG. */
+int64_t mh_warp_wgrad_workspace_floats(int64_t M);
+int64_t mh_warp_raw_floats(void);
+int mh_warp_wgrad(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
+                  const void *w3T_t, int32_t arith, int32_t regen_dpre4, int32_t elided, float *workspace, float *raw, int64_t M,
+                  void *stream);
 
 /* mh_field_fwd: canonical field  sdf_net([freq(xc), hash, topo]) -> sdf, sigma (Laplace), geo;
  *               color_net([hash_c, geo]) -> sigmoid -> albedo.
- *   xc [M,3]; feat_s / feat_c [M,32] (hash features); topo NULL or [M,2]; beta: DEVICE scalar = |beta_p|+1e-4
- *   (a pointer, so the host never synchronises to read the learnable beta);
- *   with_color = 0 skips color_net (FD-normal taps, occupancy queries). */
-int64_t mh_field_acts_floats(int64_t M);
-int64_t mh_field_wpack_floats(void);
-int64_t mh_field_wpackT_floats(void);
-int mh_field_fwd(const float *xc, const float *feat_s, const float *feat_c, const float *topo,
-                 const float *wpack, const float *bias, const float *beta, int32_t n_bands, int32_t with_color,
-                 float *sdf, float *sigma, float *albedo, float *acts, int64_t M, void *stream);
-/* weight gradients: for `n_layers` (<= 16) layers described by HOST arrays (offsets in floats into the
- * acts / dpre tiles, feature counts padded to multiples of 32):
- *   dW_l[out][in] = sum_pts dpre_l[out][pt] * act_l[in][pt],  db_l[out] = sum_pts dpre_l[out][pt]
- * One MFMA launch per layer writes per-chunk partials into `workspace`
- * (mh_mlp_wgrad_workspace_floats(...) floats), one reduction launch sums them into
- *   dw_raw [sum_l out_l*in_l]  followed contiguously by  db_raw [sum_l out_l]   (db_raw == dw_raw + sum_l out_l*in_l)
- * in tile-row order (the caller maps rows back to the natural layout, morpheus_amd/packing.py).
- * in_live_host / out_live_host (HOST arrays, or NULL = every row): how many rows of layer l's input tile / dPre tile carry
- * values (the warp nets: 40 of the first layer's 64 input rows, 3 | 2 of the last layer's 32 dPre rows).  Rows behind them are
- * never read -- the producing kernels do not write them -- and the dW rows / columns of those pad features are unspecified
- * (the caller's row map does not gather them).  128-row layers take out_live = 128. */
-int64_t mh_mlp_wgrad_workspace_floats(int32_t n_layers, const int32_t *in_feats_host,
-                                      const int32_t *out_feats_host, int64_t n_tiles);
-int mh_mlp_wgrad(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
-                 int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
-                 const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
-                 const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles, void *stream);
-/* the same GEMM with exact fp32 products from three bf16 slices on the bf16 matrix pipe (see mh_warp_fwd_b3): both fp32
- * operands are sliced on the fly, same arguments, same outputs. */
-int mh_mlp_wgrad_b3(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
-                    int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
-                    const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
-                    const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles, void *stream);
+ *   xc [M,3]; feat_s / feat_c [M,32] (hash features); topo NULL or [M,2]; w: the forward pack of `arith` for the six field layers;
+ *   beta: DEVICE scalar = |beta_p|+1e-4 (a pointer, so the host never synchronises to read the learnable beta);
+ *   with_color = 0 skips color_net (FD-normal taps, occupancy queries);  acts: NULL or mh_field_acts_floats(M) floats. */
+int mh_field_fwd(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const void *w, const float *bias,
+                 const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma, float *albedo, float *acts,
+                 int64_t M, int32_t arith, void *stream);
+/* mh_field_bwd_fused: backward of the field nets: backward-data AND weight gradients in one pass per net; the weight-gradient
+ * accumulators stay in registers, so the pre-activation gradients never reach HBM (no `dpre` buffer).
+ *   g_sdf, g_sigma [M], g_albedo [M,3] (any may be NULL) -> g_xc [M,3] or NULL (freq path only; the hash path's d/dx comes
+ *   from mh_grid_encode_bwd), g_feat_s, g_feat_c [M,32], g_topo [M,2].  sdf / albedo are the forward's outputs (Laplace and
+ *   sigmoid derivatives are formed from them).  wT: the TRANSPOSED pack of `arith`.
+ *   gmax_bits: NULL, or 2 DEVICE words zeroed by the caller that receive max |g_feat_s| and max |g_feat_c| as raw float
+ *   bits (atomicMax) -- what mh_grid_encode_bwd_binned needs for its fixed-point accumulation.
+ *   dgeo_scratch [mh_field_dgeo_floats(M)] (d(geo) handed from the colour launch to the sdf launch; may be NULL when
+ *   with_color == 0), workspace [mh_field_bwd_fused_workspace_floats(M)] (per-wave partial sums), and
+ *   raw [24 928 + 1] = the weight gradient in mh_warp_wgrad's tile-row format for the layer list s0, s1, s2, c0, c1, c2
+ *   (dW tiles | db tiles; the colour part is zero when with_color == 0) followed by dL/dbeta (one float, summed in a fixed
+ *   order).  accumulate == 0: raw is written; != 0: this call's gradients are ADDED to raw -- the field queries of one
+ *   training step (render, finite-difference taps, regularisers) sum their weight gradients in place, no caller-side adds.
+ * mh_field_bwd_pair_min_points: tuning knob (process-wide) of the MH_ARITH_B3 form: a with-colour call of at least this many
+ *   points runs the pair form of its two launches (512-thread workgroups, two waves per SIMD that share a tile's chain and
+ *   weight-gradient work); smaller calls and the sdf-only pass run the one-wave kernels.  Every output is bit-identical either
+ *   way.  set < 0: query only.  Returns the value in force (default 0: every with-colour call). */
+int64_t mh_field_bwd_fused_workspace_floats(int64_t M);
+int64_t mh_field_dgeo_floats(int64_t M);
+int64_t mh_field_bwd_pair_min_points(int64_t set);
+int mh_field_bwd_fused(const float *xc, const float *sdf, const float *albedo, const float *g_sdf, const float *g_sigma,
+                       const float *g_albedo, const void *wT, const float *beta, int32_t n_bands, int32_t with_color,
+                       const float *acts, float *dgeo_scratch, float *workspace, float *raw, int32_t accumulate, float *g_xc,
+                       float *g_feat_s, float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, int32_t arith, void *stream);
 
 /* ---- weight-norm parametrisation of every weight-normed layer, one launch each way ---------- */
 /* Replaces nn.utils.weight_norm on the Linear layers of deform_net / topo_net / color_net (models/decoders.py:51-52),
@@ -432,38 +434,6 @@ int mh_weight_norm_bwd(int32_t n_layers, const float *const *v_host, const float
                        const float *const *dw_host, float *const *dv_host, float *const *dg_host,
                        const int32_t *rows_host, const int32_t *cols_host, void *stream);
 
-/* Backward of the field nets: backward-data AND weight gradients in one pass per net; the weight-gradient accumulators
- * stay in registers, so the pre-activation gradients never reach HBM (no `dpre` buffer).
- *   g_sdf, g_sigma [M], g_albedo [M,3] (any may be NULL) -> g_xc [M,3] or NULL (freq path only; the hash path's d/dx comes
- *   from mh_grid_encode_bwd), g_feat_s, g_feat_c [M,32], g_topo [M,2].  sdf / albedo are the forward's outputs (Laplace and
- *   sigmoid derivatives are formed from them).
- *   gmax_bits: NULL, or 2 DEVICE words zeroed by the caller that receive max |g_feat_s| and max |g_feat_c| as raw float
- *   bits (atomicMax) -- what mh_grid_encode_bwd_binned needs for its fixed-point accumulation.
- *   dgeo_scratch [mh_field_dgeo_floats(M)] (d(geo) handed from the colour launch to the sdf launch; may be NULL when
- *   with_color == 0), workspace [mh_field_bwd_fused_workspace_floats(M)] (per-wave partial sums), and
- *   raw [24 928 + 1] = the weight gradient in mh_mlp_wgrad's tile-row format for the layer list s0, s1, s2, c0, c1, c2
- *   (dW tiles | db tiles; the colour part is zero when with_color == 0) followed by dL/dbeta (one float, summed in a fixed
- *   order).  accumulate == 0: raw is written; != 0: this call's gradients are ADDED to raw -- the field queries of one
- *   training step (render, finite-difference taps, regularisers) sum their weight gradients in place, no caller-side adds. */
-int64_t mh_field_bwd_fused_workspace_floats(int64_t M);
-int64_t mh_field_dgeo_floats(int64_t M);
-int mh_field_bwd_fused(const float *xc, const float *sdf, const float *albedo, const float *g_sdf, const float *g_sigma,
-                       const float *g_albedo, const float *wpackT, const float *beta, int32_t n_bands, int32_t with_color,
-                       const float *acts, float *dgeo_scratch, float *workspace, float *raw, int32_t accumulate, float *g_xc,
-                       float *g_feat_s, float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream);
-/* The same pass with exact fp32 products from three bf16 slices on the bf16 matrix pipe (see mh_warp_fwd_b3): w3T = the sliced
- * TRANSPOSED pack of the six field layers (packing.py field_joint_packer().b3T_layers: TC2 | TC1 | TC0 | TS2 | TS1 | TS0,
- * mh_field_w3T_bytes() bytes, cut by mh_b3_slice).  Same arguments otherwise, same outputs up to fp32 summation order. */
-int64_t mh_field_w3T_bytes(void);
-int mh_field_bwd_fused_b3(const float *xc, const float *sdf, const float *albedo, const float *g_sdf, const float *g_sigma,
-                          const float *g_albedo, const void *w3T, const float *beta, int32_t n_bands, int32_t with_color,
-                          const float *acts, float *dgeo_scratch, float *workspace, float *raw, int32_t accumulate, float *g_xc,
-                          float *g_feat_s, float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream);
-/* Tuning knob (process-wide) of mh_field_bwd_fused_b3: a with-colour call of at least this many points runs the pair form of its
- * two launches (512-thread workgroups, two waves per SIMD that share a tile's chain and weight-gradient work); smaller calls and
- * the sdf-only pass run the one-wave kernels.  Every output is bit-identical either way.  set < 0: query only.  Returns the
- * value in force (default 0: every with-colour call). */
-int64_t mh_field_bwd_pair_min_points(int64_t set);
 /* ---- optimiser step over the flat parameter bucket (the step after the path) ---- */
 /* Replaces torch.optim.Adam(model.get_params_all(lr), betas=(0.9,0.99), eps=1e-15).step() of morpheus.py:154-155,
  * :1401-1424 (no weight decay, no amsgrad).  params/grads/exp_avg/exp_avg_sq: [n] fp32 device buffers, 16-byte aligned.

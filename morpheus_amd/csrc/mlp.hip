@@ -24,7 +24,7 @@
 //    forward in backward: 128 MACs per stored float makes the store cheaper than the recompute.
 //  * Backward is two kernels: backward-data (same register-resident chain with transposed packs,
 //    ReLU derivative from sign masks the forward parks next to the activations, writes dPre tiles) and
-//    mh_mlp_wgrad (dW = dPre . act^T as MFMA over the point axis, per-chunk partials summed by a
+//    mh_warp_wgrad (dW = dPre . act^T as MFMA over the point axis, per-chunk partials summed by a
 //    reduction launch; no atomics anywhere).
 //  * The kernels are ISSUE-bound: on gfx950 one wave's VALU / store / DMA instructions do not issue under
 //    the co-resident wave's fp32 MFMAs (tools/phase_trace.py), so every non-MFMA instruction of the layer
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(FIELD_THREADS, 1) void field_fwd_kernel(const float
 // =====================================================================================
 // canonical field, FUSED backward: backward-data AND weight gradients in one pass, dPre never leaves the chip.
 //
-// A split form (backward-data kernel + mh_mlp_wgrad, removed in round 3) wrote every layer's pre-activation gradient
+// A split form (backward-data kernel + a weight-gradient GEMM like the warp nets', removed in round 3) wrote every layer's pre-activation gradient
 // (1.4 KB per point) and read it back together with the parked activations (3.1 KB per point): 9.7 GB of HBM traffic per
 // step at the benchmark size (2.76 ms against 2.13 ms for this form).  Here a wave keeps the weight-gradient
 // accumulators of its net IN REGISTERS across all its tiles -- the field nets are small enough: sdf_net 14 336 floats =
@@ -2627,7 +2627,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_kernel(const float *__restrict__
 
 // All layers of a net group in ONE launch: block b belongs to the layer whose block range holds it.  Used for small
 // batches, where one launch per layer (12 for the warp nets) is mostly ramp-up, drain and launch gaps; big batches keep
-// the per-layer launches (see mh_mlp_wgrad).
+// the per-layer launches (see wgrad_impl).
 #define WG_MAX_LAYERS 16
 struct WgAll {
     int32_t n;
@@ -2743,9 +2743,11 @@ extern "C" int64_t mh_field_wpack_floats(void) { return FIELD_WPACK; }
 extern "C" int64_t mh_field_wpackT_floats(void) { return FIELD_WPACKT; }
 extern "C" int64_t mh_mlp_tiles(int64_t M) { return n_tiles_for(M); }
 
-extern "C" int mh_warp_fwd(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t,
-                           const float *wpack_d, const float *wpack_t, const float *bias_d, const float *bias_t,
-                           int32_t n_bands, float *out_deform, float *out_topo, float *acts, int64_t M, void *stream) {
+// The native fp32 MFMA forms of the three passes whose entry points live beside their b3 forms (mlp_b3.hip: mh_warp_fwd,
+// mh_warp_bwd_data, mh_field_fwd with arith = MH_ARITH_F32); declared in mlp_dev.h, not exported.
+int warp_fwd_f32(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const float *wpack_d,
+                 const float *wpack_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                 float *out_topo, float *acts, int64_t M, void *stream) {
     if (M == 0) return MH_OK;
     if (M < 0 || !x || !bias0_d || !bias0_t || !wpack_d || !wpack_t || !bias_d || !bias_t || !out_deform || !out_topo ||
         n_bands < 0 || n_bands > 6)
@@ -2766,9 +2768,8 @@ extern "C" int mh_warp_fwd(const float *x, const int32_t *slot, const float *bia
     return MH_OK;
 }
 
-extern "C" int mh_warp_bwd_data(const float *x, const float *g_deform, const float *g_topo, const float *wpackT_d,
-                                const float *wpackT_t, int32_t n_bands, const float *acts, float *dpre, float *g_x,
-                                int64_t M, void *stream) {
+int warp_bwd_data_f32(const float *x, const float *g_deform, const float *g_topo, const float *wpackT_d, const float *wpackT_t,
+                      int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, void *stream) {
     if (M == 0) return MH_OK;
     if (M < 0 || !x || !wpackT_d || !wpackT_t || !acts || !dpre || n_bands < 0 || n_bands > 6) return MH_ERR_ARG;
     const int64_t blocks = (M + BLOCK_PTS - 1) / BLOCK_PTS;
@@ -2799,9 +2800,9 @@ static int field_lds_opt_in() {
     return MH_OK;
 }
 
-extern "C" int mh_field_fwd(const float *xc, const float *feat_s, const float *feat_c, const float *topo,
-                            const float *wpack, const float *bias, const float *beta, int32_t n_bands, int32_t with_color,
-                            float *sdf, float *sigma, float *albedo, float *acts, int64_t M, void *stream) {
+int field_fwd_f32(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const float *wpack,
+                  const float *bias, const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma,
+                  float *albedo, float *acts, int64_t M, void *stream) {
     if (M == 0) return MH_OK;
     if (M < 0 || !xc || !feat_s || !wpack || !bias || !sdf || n_bands < 0 || n_bands > 6 || !beta) return MH_ERR_ARG;
     if (with_color && (!feat_c || !albedo)) return MH_ERR_ARG;
@@ -2835,8 +2836,8 @@ static inline int wg_chunks(int out_pad, int64_t n_tiles, int n_layers) {
     return (int)(c < 1 ? 1 : c);
 }
 
-extern "C" int64_t mh_mlp_wgrad_workspace_floats(int32_t n_layers, const int32_t *in_feats_host,
-                                                 const int32_t *out_feats_host, int64_t n_tiles) {
+static int64_t wgrad_workspace_floats(int32_t n_layers, const int32_t *in_feats_host, const int32_t *out_feats_host,
+                                      int64_t n_tiles) {
     int64_t tot = 0;
     for (int l = 0; l < n_layers; l++)
         tot += (int64_t)wg_chunks(out_feats_host[l], n_tiles, n_layers) * ((int64_t)in_feats_host[l] * out_feats_host[l] + out_feats_host[l]);
@@ -2859,14 +2860,17 @@ struct WgLineHost {
     int a_off[WG_MAX_LAYERS], b_off[WG_MAX_LAYERS];
 };
 
+// Weight gradients of `n_layers` (<= 16) layers described by host arrays (offsets in floats into the acts / dpre tiles, feature
+// counts padded to multiples of 32; in_live / out_live: the rows of layer l's input tile / dPre tile that carry values, or NULL =
+// every row -- rows behind them are never read).  raw = [dW of layer 0 | 1 | ...][db of layer 0 | 1 | ...] in tile-row order.
 static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
                       int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
                       const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
-                      const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles, void *stream,
+                      const int32_t *out_live_host, float *workspace, float *raw, int64_t n_tiles, void *stream,
                       bool b3, const WgRegenHost *regen = nullptr, const WgLineHost *lines = nullptr) {
     if (n_tiles == 0 || n_layers == 0) return MH_OK;
-    if (!acts || !dpre || !act_off_host || !dpre_off_host || !in_feats_host || !out_feats_host || !workspace || !dw_raw ||
-        !db_raw || n_layers < 0 || n_layers > WG_MAX_LAYERS || n_tiles < 0)
+    if (!acts || !dpre || !act_off_host || !dpre_off_host || !in_feats_host || !out_feats_host || !workspace || !raw ||
+        n_layers < 0 || n_layers > WG_MAX_LAYERS || n_tiles < 0)
         return MH_ERR_ARG;
     for (int l = 0; l < n_layers; l++) {
         const int in = in_feats_host[l], out = out_feats_host[l];
@@ -2876,7 +2880,7 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
         // the slice-once kernels take every dPre row of their 128-row layers
         if (out_live_host && out == 128 && out_live_host[l] != 128) return MH_ERR_ARG;
     }
-    // workspace: [dW partials of layer 0 | 1 | ...][db partials of layer 0 | 1 | ...]; outputs: dw_raw | db_raw
+    // workspace: [dW partials of layer 0 | 1 | ...][db partials of layer 0 | 1 | ...]; output: raw = dW | db
     WgReduce rd;
     rd.n = 2 * n_layers;
     rd.accumulate = 0;
@@ -2892,7 +2896,6 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
     }
     int64_t dw_total = 0;
     for (int l = 0; l < n_layers; l++) dw_total += (int64_t)in_feats_host[l] * out_feats_host[l];
-    if (db_raw != dw_raw + dw_total) return MH_ERR_ARG;  // dw_raw and db_raw must be one contiguous buffer (checked BEFORE any launch)
     rd.first[0] = 0;
     // One launch per layer for big batches, ONE launch for all layers for small ones (measured on MI355X, same box):
     // at 2 M points the merged launch is slower (warp nets 6.6 vs 6.0 ms: workgroups of different layers stream
@@ -2958,8 +2961,7 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
 #undef WG_LAUNCH
             MH_CHECK_LAUNCH();
         }
-        // reduction segments: dW of layer l, then (second half) db of layer l; both outputs live in ONE buffer:
-        // out = dw_raw for e < dw_total, db_raw is addressed relative to dw_raw via out_off (caller passes them contiguous)
+        // reduction segments: dW of layer l, then (second half) db of layer l, behind the dw_total floats of dW in raw
         rd.chunks[l] = chunks;
         rd.len[l] = in * out;
         rd.part_off[l] = dw_poff[l];
@@ -3012,33 +3014,15 @@ static int wgrad_impl(const float *acts, const float *dpre, int64_t acts_tile_fl
     for (int s = 0; s < rd.n; s++) rd.first[s + 1] = rd.first[s] + rd.len[s];
     const int64_t total = rd.first[rd.n];
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, mh_stream(stream), workspace,
-                       dw_raw, rd);
+                       raw, rd);
     MH_CHECK_LAUNCH();
     return MH_OK;
 }
 
-extern "C" int mh_mlp_wgrad(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
-                            int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
-                            const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
-                            const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles,
-                            void *stream) {
-    return wgrad_impl(acts, dpre, acts_tile_floats, dpre_tile_floats, n_layers, act_off_host, dpre_off_host, in_feats_host,
-                      out_feats_host, in_live_host, out_live_host, workspace, dw_raw, db_raw, n_tiles, stream, false);
-}
-
-extern "C" int mh_mlp_wgrad_b3(const float *acts, const float *dpre, int64_t acts_tile_floats, int64_t dpre_tile_floats,
-                               int32_t n_layers, const int32_t *act_off_host, const int32_t *dpre_off_host,
-                               const int32_t *in_feats_host, const int32_t *out_feats_host, const int32_t *in_live_host,
-                               const int32_t *out_live_host, float *workspace, float *dw_raw, float *db_raw, int64_t n_tiles,
-                               void *stream) {
-    return wgrad_impl(acts, dpre, acts_tile_floats, dpre_tile_floats, n_layers, act_off_host, dpre_off_host, in_feats_host,
-                      out_feats_host, in_live_host, out_live_host, workspace, dw_raw, db_raw, n_tiles, stream, true);
-}
-
-// ---- the warp nets' weight gradients with their geometry on this side of the ABI ----------------------------------------------------
-// (the 12 layers of deform_net + topo_net in the tiles of mh_warp_fwd / mh_warp_bwd_data; morpheus_amd/ops.py used to spell the
-// offsets out).  regen_dpre4: the two layer-4 launches regenerate dPre4 (wgrad_regen_b3_kernel) -- the caller ran
-// mh_warp_bwd_data_b3 with skip_dpre4 = 1, and both decisions come from mh_warp_regen_dpre4(M).
+// ---- the warp nets' weight gradients; their tile geometry is stated here and in mlp_dev.h, nowhere else ---------------------------
+// (the 12 layers of deform_net + topo_net in the tiles of mh_warp_fwd / mh_warp_bwd_data).  regen_dpre4: the two layer-4 launches
+// regenerate dPre4 (wgrad_regen_b3_kernel) -- the caller ran mh_warp_bwd_data with skip_dpre4 = 1, and both decisions come from
+// mh_warp_regen_dpre4(M).
 struct WarpWg {
     int32_t act_off[12], dpre_off[12], in[12], out[12], in_live[12], out_live[12];
 };
@@ -3086,18 +3070,30 @@ extern "C" int32_t mh_warp_elides(int64_t M) {
 
 extern "C" int64_t mh_warp_wgrad_workspace_floats(int64_t M) {
     const WarpWg w = warp_wg_geometry();
-    return mh_mlp_wgrad_workspace_floats(12, w.in, w.out, n_tiles_for(M));
+    return wgrad_workspace_floats(12, w.in, w.out, n_tiles_for(M));
+}
+extern "C" int64_t mh_warp_raw_floats(void) {
+    const WarpWg w = warp_wg_geometry();
+    int64_t n = 0;
+    for (int k = 0; k < 12; k++) n += (int64_t)w.in[k] * w.out[k] + w.out[k];
+    return n;
 }
 
-// elided: the tiles' all-zero rows were not written (mh_warp_bwd_data_b3_elide): the launches must go by the words
-static int warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
-                         const void *w3T_t, int32_t regen_dpre4, bool elided, float *workspace, float *dw_raw, float *db_raw, int64_t M,
-                         void *stream) {
+// elided: the tiles' all-zero rows were not written (mh_warp_bwd_data with elided = 1): the launches must go by the words
+extern "C" int mh_warp_wgrad(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
+                             const void *w3T_t, int32_t arith, int32_t regen_dpre4, int32_t elided, float *workspace, float *raw,
+                             int64_t M, void *stream) {
+    if (arith != MH_ARITH_F32 && arith != MH_ARITH_B3) return MH_ERR_ARG;
+    if (arith == MH_ARITH_F32 && (regen_dpre4 || elided || g_deform || g_topo || w3T_d || w3T_t)) return MH_ERR_ARG;
     if (M == 0) return MH_OK;
-    if (M < 0 || !w3T_d || !w3T_t) return MH_ERR_ARG;
+    if (M < 0) return MH_ERR_ARG;
+    const WarpWg w = warp_wg_geometry();
+    if (arith == MH_ARITH_F32)
+        return wgrad_impl(acts, dpre, (int64_t)WARP_ACT_ROWS * TILE, (int64_t)WARP_DPRE_ROWS * TILE, 12, w.act_off, w.dpre_off, w.in,
+                          w.out, w.in_live, w.out_live, workspace, raw, n_tiles_for(M), stream, false);
+    if (!w3T_d || !w3T_t) return MH_ERR_ARG;
     if (regen_dpre4 && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;      // (the small-batch launches read dPre4)
     if (elided && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;           // (the merged small-batch kernels read every row)
-    const WarpWg w = warp_wg_geometry();
     WgRegenHost rg;
     for (int k = 0; k < WG_MAX_LAYERS; k++) rg.on[k] = false;
     rg.M = M;
@@ -3120,18 +3116,8 @@ static int warp_wgrad_b3(const float *acts, const float *dpre, const float *g_de
         }
     const bool skip = elided || g_warp_skip_zero_lines.load(std::memory_order_relaxed) != 0;
     return wgrad_impl(acts, dpre, (int64_t)WARP_ACT_ROWS * TILE, (int64_t)WARP_DPRE_ROWS * TILE, 12, w.act_off, w.dpre_off, w.in, w.out,
-                      w.in_live, w.out_live, workspace, dw_raw, db_raw, n_tiles_for(M), stream, true, regen_dpre4 ? &rg : nullptr,
+                      w.in_live, w.out_live, workspace, raw, n_tiles_for(M), stream, true, regen_dpre4 ? &rg : nullptr,
                       skip ? &ln : nullptr);
-}
-extern "C" int mh_warp_wgrad_b3(const float *acts, const float *dpre, const float *g_deform, const float *g_topo, const void *w3T_d,
-                                const void *w3T_t, int32_t regen_dpre4, float *workspace, float *dw_raw, float *db_raw, int64_t M,
-                                void *stream) {
-    return warp_wgrad_b3(acts, dpre, g_deform, g_topo, w3T_d, w3T_t, regen_dpre4, false, workspace, dw_raw, db_raw, M, stream);
-}
-extern "C" int mh_warp_wgrad_b3_elide(const float *acts, const float *dpre, const float *g_deform, const float *g_topo,
-                                      const void *w3T_d, const void *w3T_t, int32_t regen_dpre4, int32_t elided, float *workspace,
-                                      float *dw_raw, float *db_raw, int64_t M, void *stream) {
-    return warp_wgrad_b3(acts, dpre, g_deform, g_topo, w3T_d, w3T_t, regen_dpre4, elided != 0, workspace, dw_raw, db_raw, M, stream);
 }
 
 // ---- fused field backward (backward-data + weight gradients, see field_fused_*_kernel) ---------------------------------
@@ -3161,11 +3147,16 @@ extern "C" int64_t mh_field_bwd_pair_min_points(int64_t set) {
     return g_pair_min_points.load(std::memory_order_relaxed);
 }
 
-static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *albedo, const float *g_sdf,
-                                const float *g_sigma, const float *g_albedo, const float *wpackT, const float *beta,
-                                int32_t n_bands, int32_t with_color, const float *acts, float *dgeo_scratch,
-                                float *workspace, float *raw, int32_t accumulate, float *g_xc, float *g_feat_s, float *g_feat_c,
-                                float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream, bool b3) {
+// wT: the fp32 transposed pack, or (arith = MH_ARITH_B3) the sliced one of the six field layers (packing.py
+// field_joint_packer().b3T_layers: TC2 | TC1 | TC0 | TS2 | TS1 | TS0, mh_field_w3T_bytes() bytes)
+extern "C" int mh_field_bwd_fused(const float *xc, const float *sdf, const float *albedo, const float *g_sdf,
+                                  const float *g_sigma, const float *g_albedo, const void *wT, const float *beta,
+                                  int32_t n_bands, int32_t with_color, const float *acts, float *dgeo_scratch,
+                                  float *workspace, float *raw, int32_t accumulate, float *g_xc, float *g_feat_s,
+                                  float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, int32_t arith, void *stream) {
+    if (arith != MH_ARITH_F32 && arith != MH_ARITH_B3) return MH_ERR_ARG;
+    const bool b3 = arith == MH_ARITH_B3;
+    const float *wpackT = reinterpret_cast<const float *>(wT);
     if (M == 0) return MH_OK;
     if (M < 0 || !xc || !sdf || !wpackT || !acts || !workspace || !raw || n_bands < 0 || n_bands > 6 || !beta) return MH_ERR_ARG;
     if (with_color && (!albedo || !dgeo_scratch)) return MH_ERR_ARG;
@@ -3243,7 +3234,7 @@ static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *
 #undef FUSED_LAUNCH_COLOR
 #undef FUSED_LAUNCH_SDF
     MH_CHECK_LAUNCH();
-    // reduce the per-workgroup partials into raw = [dW s0..c2 | db s0..c2] (mh_mlp_wgrad's output format).  On the sdf-only pass the
+    // reduce the per-workgroup partials into raw = [dW s0..c2 | db s0..c2] (mh_warp_wgrad's output format).  On the sdf-only pass the
     // colour net's segments are reduced over ZERO chunks, i.e. written as 0 by the same launch (no separate memsets)
     const int n_l = with_color ? 6 : 3;
     WgReduce rd;
@@ -3275,28 +3266,8 @@ static int field_bwd_fused_impl(const float *xc, const float *sdf, const float *
     return MH_OK;
 }
 
-extern "C" int mh_field_bwd_fused(const float *xc, const float *sdf, const float *albedo, const float *g_sdf,
-                                  const float *g_sigma, const float *g_albedo, const float *wpackT, const float *beta,
-                                  int32_t n_bands, int32_t with_color, const float *acts, float *dgeo_scratch,
-                                  float *workspace, float *raw, int32_t accumulate, float *g_xc, float *g_feat_s,
-                                  float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream) {
-    return field_bwd_fused_impl(xc, sdf, albedo, g_sdf, g_sigma, g_albedo, wpackT, beta, n_bands, with_color, acts, dgeo_scratch,
-                                workspace, raw, accumulate, g_xc, g_feat_s, g_feat_c, g_topo, gmax_bits, M, stream, false);
-}
-
-// The same pass with exact fp32 products from three bf16 slices on the bf16 matrix pipe: w3T = the sliced TRANSPOSED pack of the
-// six field layers (packing.py field_joint_packer().b3T_layers: TC2 | TC1 | TC0 | TS2 | TS1 | TS0).  Same arguments otherwise.
 extern "C" int64_t mh_field_w3T_bytes(void) {
     return (int64_t)(FUSED_TC2(1) + FUSED_TC1(1) + FUSED_TC0(1) + FUSED_TS2(1) + FUSED_TS1(1) + FUSED_TS0(1)) * 16;
-}
-extern "C" int mh_field_bwd_fused_b3(const float *xc, const float *sdf, const float *albedo, const float *g_sdf,
-                                     const float *g_sigma, const float *g_albedo, const void *w3T, const float *beta,
-                                     int32_t n_bands, int32_t with_color, const float *acts, float *dgeo_scratch,
-                                     float *workspace, float *raw, int32_t accumulate, float *g_xc, float *g_feat_s,
-                                     float *g_feat_c, float *g_topo, uint32_t *gmax_bits, int64_t M, void *stream) {
-    return field_bwd_fused_impl(xc, sdf, albedo, g_sdf, g_sigma, g_albedo, reinterpret_cast<const float *>(w3T), beta, n_bands,
-                                with_color, acts, dgeo_scratch, workspace, raw, accumulate, g_xc, g_feat_s, g_feat_c, g_topo,
-                                gmax_bits, M, stream, true);
 }
 
 extern "C" int mh_abi_version(void) { return MH_ABI_VERSION; }

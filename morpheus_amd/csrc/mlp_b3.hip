@@ -632,7 +632,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 1 : 2) void warp_fwd_b3_kernel(
 
 // ---- backward-data -------------------------------------------------------------------------------------------------
 // Same chain, transposed packs (T5, T4..T1, T0), ReLU derivative from the sign masks the forward parked; parks dPre tiles in
-// mlp.hip's layout for mh_mlp_wgrad.
+// mlp.hip's layout for mh_warp_wgrad.
 #define B3_T5_F4 1536                                   // 3 planes x 4 tiles x 2 k16 steps x 64 lanes
 #define B3_T0_F4 3072                                   // 3 planes x 2 tiles x 8 k16 steps x 64 lanes
 #define B3_NETT_F4 (B3_T5_F4 + 4 * B3_LH_F4 + B3_T0_F4)  // 29 184 float4 per net
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(NW * 64, 2) void warp_bwd_b3_kernel(const float *__
             d5[1] = g[p * nout + 1];
             if (nout == 3) d5[2] = g[p * nout + 2];
         }
-        // dPre5's live rows only (0..nout-1 <= 3: registers 0..3 of the lower half; mh_mlp_wgrad reads no row behind them, wg_row)
+        // dPre5's live rows only (0..nout-1 <= 3: registers 0..3 of the lower half; mh_warp_wgrad reads no row behind them, wg_row)
         if (h == 0) {
 #pragma unroll
             for (int r = 0; r < 4; r++) dt[(640 + r) * TILE + pt] = d5[r];
@@ -1127,11 +1127,16 @@ static int b3_lds_opt_in() {
 
 extern "C" int64_t mh_field_w3_bytes(void) { return (int64_t)FB3_F4 * 16; }
 
-extern "C" int mh_field_fwd_b3(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const void *w3,
-                               const float *bias, const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma,
-                               float *albedo, float *acts, int64_t M, void *stream) {
+// w: the fp32 pack (arith = MH_ARITH_F32: mlp.hip's kernel) or the sliced pack of the six field layers
+extern "C" int mh_field_fwd(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const void *w,
+                            const float *bias, const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma,
+                            float *albedo, float *acts, int64_t M, int32_t arith, void *stream) {
+    if (arith == MH_ARITH_F32)
+        return field_fwd_f32(xc, feat_s, feat_c, topo, reinterpret_cast<const float *>(w), bias, beta, n_bands, with_color, sdf, sigma,
+                             albedo, acts, M, stream);
+    if (arith != MH_ARITH_B3) return MH_ERR_ARG;
     if (M == 0) return MH_OK;
-    if (M < 0 || !xc || !feat_s || !w3 || !bias || !sdf || n_bands < 0 || n_bands > 6 || !beta) return MH_ERR_ARG;
+    if (M < 0 || !xc || !feat_s || !w || !bias || !sdf || n_bands < 0 || n_bands > 6 || !beta) return MH_ERR_ARG;
     if (with_color && (!feat_c || !albedo)) return MH_ERR_ARG;
     const int64_t n_tiles = mh_mlp_tiles(M);   // dead tail tiles are processed too: the backward reads every scratch tile
     static MhOncePerDevice ok;
@@ -1144,7 +1149,7 @@ extern "C" int mh_field_fwd_b3(const float *xc, const float *feat_s, const float
     const int64_t need = (n_tiles + FB3_THREADS / 64 - 1) / (FB3_THREADS / 64);
     const int64_t cus = mh_cu_count();
     hipLaunchKernelGGL(field_fwd_b3_kernel, dim3((unsigned)(need < cus ? need : cus)), dim3(FB3_THREADS), FB3_F4 * 16,
-                       mh_stream(stream), xc, feat_s, feat_c, topo, reinterpret_cast<const f32x4 *>(w3), bias, beta, (int)n_bands,
+                       mh_stream(stream), xc, feat_s, feat_c, topo, reinterpret_cast<const f32x4 *>(w), bias, beta, (int)n_bands,
                        (int)with_color, sdf, sigma, albedo, acts, M, n_tiles);
     MH_CHECK_LAUNCH();
     return MH_OK;
@@ -1159,12 +1164,18 @@ extern "C" int64_t mh_warp_w3T_bytes(void) { return (int64_t)B3_NETT_F4 * 16; }
 // tile per SIMD and twice the CUs.
 static inline bool b3_small_batch(int64_t M) { return M <= (int64_t)BLOCK_PTS * mh_cu_count(); }
 
-// elided: the forward elided this scratch (mh_warp_fwd_b3_elide); the dPre rows under the same words are not written either
-static int warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
-                            int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4, bool elided,
-                            void *stream) {
+// wT_{d,t}: the fp32 transposed packs (arith = MH_ARITH_F32: mlp.hip's kernel) or the sliced ones
+// elided: the forward elided this scratch (mh_warp_fwd with elide = 1); the dPre rows under the same words are not written either
+extern "C" int mh_warp_bwd_data(const float *x, const float *g_deform, const float *g_topo, const void *wT_d, const void *wT_t,
+                                int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t arith,
+                                int32_t skip_dpre4, int32_t elided, void *stream) {
+    if (arith == MH_ARITH_F32)
+        return skip_dpre4 || elided ? MH_ERR_ARG
+                                    : warp_bwd_data_f32(x, g_deform, g_topo, reinterpret_cast<const float *>(wT_d),
+                                                        reinterpret_cast<const float *>(wT_t), n_bands, acts, dpre, g_x, M, stream);
+    if (arith != MH_ARITH_B3) return MH_ERR_ARG;
     if (M == 0) return MH_OK;
-    if (M < 0 || !x || !w3T_d || !w3T_t || !acts || !dpre || n_bands < 0 || n_bands > 6) return MH_ERR_ARG;
+    if (M < 0 || !x || !wT_d || !wT_t || !acts || !dpre || n_bands < 0 || n_bands > 6) return MH_ERR_ARG;
     const bool small = b3_small_batch(M);
     if (skip_dpre4 && small) return MH_ERR_ARG;       // (mh_warp_regen_dpre4(M) is never set for such a batch)
     if (elided && !mh_warp_regen_dpre4(M)) return MH_ERR_ARG;      // only the per-layer weight-gradient kernels go by the words
@@ -1173,45 +1184,41 @@ static int warp_bwd_data_b3(const float *x, const float *g_deform, const float *
     if (b3_lds_opt_in() != MH_OK) return MH_ERR_LAUNCH;
     if (small)
         hipLaunchKernelGGL(warp_bwd_b3_kernel<4>, dim3((unsigned)blocks), dim3(256), B3_LDS_BYTES, mh_stream(stream), x, g_deform,
-                           g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t), (int)n_bands,
+                           g_topo, reinterpret_cast<const f32x4 *>(wT_d), reinterpret_cast<const f32x4 *>(wT_t), (int)n_bands,
                            acts, dpre, g_x, M, mh_mlp_tiles(M));
     else if (elided && skip_dpre4)
         hipLaunchKernelGGL((warp_bwd_b3_kernel<8, false, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
-                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(wT_d), reinterpret_cast<const f32x4 *>(wT_t),
                            (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
     else if (elided)
         hipLaunchKernelGGL((warp_bwd_b3_kernel<8, true, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
-                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           x, g_deform, g_topo, reinterpret_cast<const f32x4 *>(wT_d), reinterpret_cast<const f32x4 *>(wT_t),
                            (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
     else if (skip_dpre4)
         hipLaunchKernelGGL((warp_bwd_b3_kernel<8, false>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream), x,
-                           g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           g_deform, g_topo, reinterpret_cast<const f32x4 *>(wT_d), reinterpret_cast<const f32x4 *>(wT_t),
                            (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
     else
         hipLaunchKernelGGL(warp_bwd_b3_kernel<8>, dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream), x,
-                           g_deform, g_topo, reinterpret_cast<const f32x4 *>(w3T_d), reinterpret_cast<const f32x4 *>(w3T_t),
+                           g_deform, g_topo, reinterpret_cast<const f32x4 *>(wT_d), reinterpret_cast<const f32x4 *>(wT_t),
                            (int)n_bands, acts, dpre, g_x, M, mh_mlp_tiles(M));
     MH_CHECK_LAUNCH();
     return MH_OK;
 }
-extern "C" int mh_warp_bwd_data_b3(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d, const void *w3T_t,
-                                   int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M, int32_t skip_dpre4,
-                                   void *stream) {
-    return warp_bwd_data_b3(x, g_deform, g_topo, w3T_d, w3T_t, n_bands, acts, dpre, g_x, M, skip_dpre4, false, stream);
-}
-extern "C" int mh_warp_bwd_data_b3_elide(const float *x, const float *g_deform, const float *g_topo, const void *w3T_d,
-                                         const void *w3T_t, int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M,
-                                         int32_t skip_dpre4, int32_t elided, void *stream) {
-    return warp_bwd_data_b3(x, g_deform, g_topo, w3T_d, w3T_t, n_bands, acts, dpre, g_x, M, skip_dpre4, elided != 0, stream);
-}
 
 // elide: the H rows without a non-zero are not written; every reader of this scratch must then go by the line words
-static int warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                       const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform, float *out_topo,
-                       float *acts, int64_t M, bool elide, void *stream) {
+// w_{d,t}: the fp32 packs (arith = MH_ARITH_F32: mlp.hip's kernel) or the sliced ones
+extern "C" int mh_warp_fwd(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w_d,
+                           const void *w_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                           float *out_topo, float *acts, int64_t M, int32_t arith, int32_t elide, void *stream) {
+    if (arith == MH_ARITH_F32)
+        return elide ? MH_ERR_ARG
+                     : warp_fwd_f32(x, slot, bias0_d, bias0_t, reinterpret_cast<const float *>(w_d), reinterpret_cast<const float *>(w_t),
+                                    bias_d, bias_t, n_bands, out_deform, out_topo, acts, M, stream);
+    if (arith != MH_ARITH_B3) return MH_ERR_ARG;
     if (M == 0) return MH_OK;
     if (elide && (!acts || M < 0 || !mh_warp_regen_dpre4(M))) return MH_ERR_ARG;      // only the per-layer weight-gradient kernels go by the words
-    if (M < 0 || !x || !bias0_d || !bias0_t || !w3_d || !w3_t || !bias_d || !bias_t || !out_deform || !out_topo || n_bands < 0 ||
+    if (M < 0 || !x || !bias0_d || !bias0_t || !w_d || !w_t || !bias_d || !bias_t || !out_deform || !out_topo || n_bands < 0 ||
         n_bands > 6)
         return MH_ERR_ARG;
     const bool small = b3_small_batch(M);
@@ -1220,7 +1227,7 @@ static int warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d
     if (b3_lds_opt_in() != MH_OK) return MH_ERR_LAUNCH;
 #define B3_FWD_LAUNCH(NW_, PARK_, THREADS_)                                                                                          \
     hipLaunchKernelGGL((warp_fwd_b3_kernel<NW_, PARK_>), dim3((unsigned)blocks), dim3(THREADS_), B3_LDS_BYTES, mh_stream(stream), x, slot, \
-                       bias0_d, bias0_t, reinterpret_cast<const f32x4 *>(w3_d), reinterpret_cast<const f32x4 *>(w3_t), bias_d, bias_t, \
+                       bias0_d, bias0_t, reinterpret_cast<const f32x4 *>(w_d), reinterpret_cast<const f32x4 *>(w_t), bias_d, bias_t, \
                        (int)n_bands, out_deform, out_topo, acts, M, mh_mlp_tiles(M))
     if (small) {
         if (acts)
@@ -1230,7 +1237,7 @@ static int warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d
     } else {
         if (acts && elide)
             hipLaunchKernelGGL((warp_fwd_b3_kernel<8, true, true>), dim3((unsigned)blocks), dim3(B3_THREADS), B3_LDS_BYTES, mh_stream(stream),
-                               x, slot, bias0_d, bias0_t, reinterpret_cast<const f32x4 *>(w3_d), reinterpret_cast<const f32x4 *>(w3_t),
+                               x, slot, bias0_d, bias0_t, reinterpret_cast<const f32x4 *>(w_d), reinterpret_cast<const f32x4 *>(w_t),
                                bias_d, bias_t, (int)n_bands, out_deform, out_topo, acts, M, mh_mlp_tiles(M));
         else if (acts)
             B3_FWD_LAUNCH(8, true, B3_THREADS);
@@ -1240,14 +1247,4 @@ static int warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d
 #undef B3_FWD_LAUNCH
     MH_CHECK_LAUNCH();
     return MH_OK;
-}
-extern "C" int mh_warp_fwd_b3(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                              const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
-                              float *out_topo, float *acts, int64_t M, void *stream) {
-    return warp_fwd_b3(x, slot, bias0_d, bias0_t, w3_d, w3_t, bias_d, bias_t, n_bands, out_deform, out_topo, acts, M, false, stream);
-}
-extern "C" int mh_warp_fwd_b3_elide(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const void *w3_d,
-                                    const void *w3_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
-                                    float *out_topo, float *acts, int64_t M, int32_t elide, void *stream) {
-    return warp_fwd_b3(x, slot, bias0_d, bias0_t, w3_d, w3_t, bias_d, bias_t, n_bands, out_deform, out_topo, acts, M, elide != 0, stream);
 }

@@ -218,3 +218,17 @@ __device__ __forceinline__ void split2(float x0, float x1, uint32_t &hi, uint32_
     mid = m.u;
     lo = l.u;
 }
+
+// ---- host launchers that an entry point in one file reaches in the other (not exported) ---------------------------------
+// mlp.hip: the native fp32 MFMA forms behind mh_warp_fwd / mh_warp_bwd_data / mh_field_fwd (mlp_b3.hip), the entry's arguments
+// without its arithmetic and eliding flags
+#define MH_HIDDEN __attribute__((visibility("hidden")))
+MH_HIDDEN int warp_fwd_f32(const float *x, const int32_t *slot, const float *bias0_d, const float *bias0_t, const float *wpack_d,
+                           const float *wpack_t, const float *bias_d, const float *bias_t, int32_t n_bands, float *out_deform,
+                           float *out_topo, float *acts, int64_t M, void *stream);
+MH_HIDDEN int warp_bwd_data_f32(const float *x, const float *g_deform, const float *g_topo, const float *wpackT_d,
+                                const float *wpackT_t, int32_t n_bands, const float *acts, float *dpre, float *g_x, int64_t M,
+                                void *stream);
+MH_HIDDEN int field_fwd_f32(const float *xc, const float *feat_s, const float *feat_c, const float *topo, const float *wpack,
+                            const float *bias, const float *beta, int32_t n_bands, int32_t with_color, float *sdf, float *sigma,
+                            float *albedo, float *acts, int64_t M, void *stream);

@@ -173,8 +173,8 @@ def _bin_points(lib, x, bound):
 #         instruction, and the slowest (the fp32 MFMA runs at the vector-ALU rate on gfx950).
 # (A third form, two fp16 slices at power-of-two scales -- 22-bit operands, NOT fp32-faithful -- existed in rounds 3-5 and was
 # deleted in round 6: git history, csrc/mlp_h2.hip.)
-# The field nets' fused backward follows the b3 mode too (mh_field_bwd_fused_b3); the f32 mode runs it on the native fp32
-# MFMA (mh_field_bwd_fused); see FIELD_BWD below.
+# The field nets' fused backward (mh_field_bwd_fused) follows the b3 mode too; the f32 mode runs it on the native fp32 MFMA; see
+# FIELD_BWD below.
 MLP_MODES = ("b3", "f32")
 MODE_DTYPE = {"f32": "f32", "b3": "f32 (exact 3 x bf16 operand split, 6 slice products per MAC on the bf16 MFMA pipe, fp32 accumulate)"}
 _mode = os.environ.get("MORPHEUS_MLP", "b3")
@@ -1217,29 +1217,8 @@ def sample_positions_nograd(rays_o, rays_d, ray_idx, t_starts, t_ends):
 REGEN_DPRE4 = os.environ.get("MORPHEUS_REGEN_DPRE4", "1") != "0"
 
 
-def _wgrad(lib, acts, dpre, acts_tile, dpre_tile, act_off, dpre_off, in_pad, out_pad, n_tiles, dev, tag, b3=False, in_live=None,
-           out_live=None):
-    """in_live / out_live: rows of each layer's input / dPre tile that carry values (None: all; include/morpheus_hip.h)"""
-    n_layers = len(act_off)
-    il_p = None if in_live is None else _i32arr(in_live)[1]
-    ol_p = None if out_live is None else _i32arr(out_live)[1]
-    dw_len = int(sum(i * o for i, o in zip(in_pad, out_pad)))
-    db_len = int(sum(out_pad))
-    a_np, a_p = _i32arr(act_off)
-    d_np, d_p = _i32arr(dpre_off)
-    i_np, i_p = _i32arr(in_pad)
-    o_np, o_p = _i32arr(out_pad)
-    ws = torch.empty(lib.mh_mlp_wgrad_workspace_floats(n_layers, i_p, o_p, n_tiles), device=dev)
-    # an empty query (n_tiles == 0) returns MH_OK without writing: the token gradient must then be zeros, not heap contents
-    raw = torch.empty(dw_len + db_len, device=dev) if n_tiles > 0 else torch.zeros(dw_len + db_len, device=dev)
-    dw_raw, db_raw = raw[:dw_len], raw[dw_len:]
-    _timed("mh_mlp_wgrad_b3" if b3 else "mh_mlp_wgrad", ptr(acts), ptr(dpre), acts_tile, dpre_tile, n_layers, a_p, d_p, i_p, o_p, il_p,
-           ol_p, ptr(ws), ptr(dw_raw), ptr(db_raw), n_tiles, key="mh_mlp_wgrad[" + tag + "]")
-    return raw          # dw_raw | db_raw, tile-row order (packing.JointPacker.unpack_grads maps it back)
-
-
-WARP_ACT_ROWS, WARP_DPRE_ROWS = 64 + 2 * 640 + 40, 2 * 672     # csrc/mlp.hip: activations + 40 rows of ReLU masks
-FIELD_ACT_ROWS = 96 + 64 * 5 + 8   # activations + 8 rows of ReLU masks
+# `arith` of the MLP entry points (include/morpheus_hip.h: MH_ARITH_F32, MH_ARITH_B3), by "is it the b3 form?"
+_ARITH = {False: 0, True: 1}
 
 
 # A/B and test switch: False = every field query returns its own gradient tensors and autograd adds them up (the round-3 form).
@@ -1312,7 +1291,7 @@ class _PackOperands(torch.autograd.Function):
         bwd pack  [transposed A fragments]           (non-differentiable)
         token     [raw_len] uninitialised carrier    (differentiable)
 
-    Every MLP call of the step takes the token as an input and returns `mh_mlp_wgrad`'s raw tile-order gradient
+    Every MLP call of the step takes the token as an input and returns `mh_warp_wgrad`'s raw tile-order gradient
     (dW tiles | db tiles) as the token's gradient; autograd sums the calls' contributions (ONE add of one flat tensor per
     extra call instead of one per parameter per call) and this Function's backward maps the sum to the natural layout
     with one gather.  `zero_bias0`: the first-layer bias of the warp nets reaches its parameter through the per-frame
@@ -1433,7 +1412,7 @@ class _WarpMLP(torch.autograd.Function):
         ctx.set_materialize_grads(False)      # unused outputs hand backward None, not a zero-filled tensor (one launch each)
         require_gpu(x, bias0_d, bias0_t)
         lib = _lib.load()
-        (wd, wt), (bd, bt), (wdT, wtT) = opnd.w, opnd.b, opnd.wT
+        bd, bt = opnd.b
         x = x.detach().contiguous().float()
         M, dev = x.shape[0], x.device
         need_grad = any(ctx.needs_input_grad)
@@ -1448,18 +1427,11 @@ class _WarpMLP(torch.autograd.Function):
         if elide and need_grad and opnd.w3 is not None and opnd.wT3 is not None and bias0_d.shape[0] == 1:
             level = lib.mh_warp_elides(M)
         ctx.elided, ctx.elided_fwd = level >= 1, level >= 2
-        if ctx.elided_fwd:
-            _timed("mh_warp_fwd_b3_elide", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
-                   n_bands, ptr(deform), ptr(topo), ptr(acts), M, 1, key="mh_warp_fwd")
-        elif opnd.w3 is not None:
-            _timed("mh_warp_fwd_b3", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(opnd.w3[0]), ptr(opnd.w3[1]), ptr(bd), ptr(bt),
-                   n_bands, ptr(deform), ptr(topo), ptr(acts), M, key="mh_warp_fwd")
-        else:
-            _timed("mh_warp_fwd", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), n_bands,
-                   ptr(deform), ptr(topo), ptr(acts), M)
-        ctx.b3, ctx.mode = opnd.wT3 is not None, opnd.mode
-        if ctx.b3:
-            wdT, wtT = opnd.wT3
+        ctx.b3, ctx.mode = opnd.w3 is not None, opnd.mode         # (the sliced packs w3 / wT3 are cut together)
+        wd, wt = opnd.w3 if ctx.b3 else opnd.w
+        wdT, wtT = opnd.wT3 if ctx.b3 else opnd.wT
+        _timed("mh_warp_fwd", ptr(x), ptr(slot_c), ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), n_bands, ptr(deform),
+               ptr(topo), ptr(acts), M, _ARITH[ctx.b3], int(ctx.elided_fwd))
         ctx.save_for_backward(x, slot_c, wdT, wtT, acts)
         ctx.n_bands, ctx.n_slots, ctx.jp = n_bands, bias0_d.shape[0], opnd.jp
         # the caller SAYS when slot[i] == i (model._slots' one-slot-per-sample case); n_slots == M alone does not imply it
@@ -1478,38 +1450,23 @@ class _WarpMLP(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous()
         gd, gt = c(g_deform), c(g_topo)
         # b3, large batches: dPre4 (16 KB of a tile's 172) is not parked, the layer-4 weight-gradient launches make it again from
-        # the incoming gradient, the ReLU sign words and the T5 slices -- the same bits (include/morpheus_hip.h: mh_warp_wgrad_b3)
+        # the incoming gradient, the ReLU sign words and the T5 slices -- the same bits (include/morpheus_hip.h: mh_warp_bwd_data)
         regen = bool(ctx.b3 and REGEN_DPRE4 and lib.mh_warp_regen_dpre4(M))
-        if ctx.elided:
-            _timed("mh_warp_bwd_data_b3_elide", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre),
-                   ptr(g_x), M, int(regen), 1, key="mh_warp_bwd_data")
-        elif ctx.b3:
-            _timed("mh_warp_bwd_data_b3", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre),
-                   ptr(g_x), M, int(regen), key="mh_warp_bwd_data")
-        else:
-            _timed("mh_warp_bwd_data", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre), ptr(g_x), M)
-        if ctx.b3:
-            jp = ctx.jp
-            ws = torch.empty(max(lib.mh_warp_wgrad_workspace_floats(M), 1), device=dev)
-            dw_len = sum(i * o for i, o in zip(_WARP_WG[2], _WARP_WG[3]))
-            raw_len = dw_len + sum(_WARP_WG[3])
-            assert raw_len == jp.raw_len
-            raw = torch.empty(raw_len, device=dev) if M > 0 else torch.zeros(raw_len, device=dev)      # (an empty call writes nothing)
-            if ctx.elided:
-                _timed("mh_warp_wgrad_b3_elide", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), 1, ptr(ws),
-                       ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
-            else:
-                _timed("mh_warp_wgrad_b3", ptr(acts), ptr(dpre), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), int(regen), ptr(ws),
-                       ptr(raw[:dw_len]), ptr(raw[dw_len:]), M, key="mh_mlp_wgrad[warp]")
-        else:
-            raw = _wgrad(lib, acts, dpre, WARP_ACT_ROWS * 32, WARP_DPRE_ROWS * 32, _WARP_WG[0], _WARP_WG[1], _WARP_WG[2],
-                         _WARP_WG[3], n_tiles, dev, "warp", b3=False, in_live=_WARP_WG[4], out_live=_WARP_WG[5])
+        _timed("mh_warp_bwd_data", ptr(x), ptr(gd), ptr(gt), ptr(wdT), ptr(wtT), ctx.n_bands, ptr(acts), ptr(dpre), ptr(g_x), M,
+               _ARITH[ctx.b3], int(regen), int(ctx.elided))
+        ws = torch.empty(max(lib.mh_warp_wgrad_workspace_floats(M), 1), device=dev)
+        raw_len = ctx.jp.raw_len                                  # == mh_warp_raw_floats(): dW tiles | db tiles, tile-row order
+        raw = torch.empty(raw_len, device=dev) if M > 0 else torch.zeros(raw_len, device=dev)      # (an empty call writes nothing)
+        b3_only = (ptr(gd), ptr(gt), ptr(wdT), ptr(wtT)) if ctx.b3 else (None,) * 4     # what regenerating dPre4 reads
+        _timed("mh_warp_wgrad", ptr(acts), ptr(dpre), *b3_only, _ARITH[ctx.b3], int(regen), int(ctx.elided), ptr(ws), ptr(raw), M,
+               key="mh_mlp_wgrad[warp]")
         # per-slot first-layer bias gradient: sum of dPre0 over the points of each slot
         if ctx.n_slots == 1:
             (od, ot) = ctx.jp.bias0_raw
             g_b0d, g_b0t = raw[od:od + 128][None], raw[ot:ot + 128][None]
         else:
-            dp = dpre.view(n_tiles, WARP_DPRE_ROWS, 32)
+            # rows 0:128 and 672:800 of a dPre tile: dPre0 of deform_net and of topo_net (csrc/mlp_dev.h: "warp dpre")
+            dp = dpre.view(n_tiles, lib.mh_warp_dpre_floats(1) // (lib.mh_mlp_tiles(1) * 32), 32)
             per_pt_d = dp[:, 0:128, :].permute(0, 2, 1).reshape(-1, 128)[:M]
             per_pt_t = dp[:, 672:800, :].permute(0, 2, 1).reshape(-1, 128)[:M]
             if ctx.identity:              # one slot per sample, slot[i] == i: the per-point rows ARE the answer
@@ -1521,23 +1478,6 @@ class _WarpMLP(torch.autograd.Function):
         return (g_x, None, g_b0d, g_b0t, raw, None, None, None, None)
 
 
-def _warp_wg_geometry():
-    act_off, dpre_off, in_pad, out_pad, in_live, out_live = [], [], [], [], [], []
-    for net in range(2):
-        for l in range(6):
-            act_off.append(0 if l == 0 else (64 + net * 640 + (l - 1) * 128) * 32)
-            dpre_off.append((net * 672 + l * 128) * 32)
-            in_pad.append(64 if l == 0 else 128)
-            out_pad.append(32 if l == 5 else 128)
-            # rows that carry values: 40 of H0's 64 (20 encoding k-steps x 2 halves), 3 | 2 of dPre5's 32 -- the b3 kernels write,
-            # and every weight-gradient kernel reads, only those (csrc/mlp.hip: wg_row)
-            in_live.append(40 if l == 0 else 128)
-            out_live.append((3, 2)[net] if l == 5 else 128)
-    return act_off, dpre_off, in_pad, out_pad, in_live, out_live
-
-
-_WARP_WG = _warp_wg_geometry()
-
 def warp_mlp(x, slot, bias0_d, bias0_t, n_bands, opnd: MLPOperands, slots_are_identity: bool = False, elide: bool = False):
     """slots_are_identity: slot[i] == i for every sample (bias0 rows are per sample): the first-layer bias gradient is then
     the per-point dPre0 rows themselves; any other slot map goes through index_add_.
@@ -1548,26 +1488,23 @@ def warp_mlp(x, slot, bias0_d, bias0_t, n_bands, opnd: MLPOperands, slots_are_id
 
 def _field_fwd(lib, xc, fs, fc, tp, beta_c, n_bands, with_color, opnd, need_grad):
     """-> sdf, sigma, albedo|None, acts|None (parked activations for backward)."""
-    w, b = opnd.w[0], opnd.b[0]
+    b3 = opnd.w3 is not None
+    w, b = (opnd.w3 if b3 else opnd.w)[0], opnd.b[0]
     M, dev = xc.shape[0], xc.device
     acts = _scratch(lib.mh_field_acts_floats(M), dev) if need_grad else None
     sdf, sigma = torch.empty(M, device=dev), torch.empty(M, device=dev)
     albedo = torch.empty(M, 3, device=dev) if with_color else None
-    if opnd.w3 is not None:
-        _timed("mh_field_fwd_b3", ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(opnd.w3[0]), ptr(b), ptr(beta_c), n_bands,
-               int(bool(with_color)), ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M, key="mh_field_fwd")
-    else:
-        _timed("mh_field_fwd", ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(w), ptr(b), ptr(beta_c), n_bands, int(bool(with_color)),
-               ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M)
+    _timed("mh_field_fwd", ptr(xc), ptr(fs), ptr(fc), ptr(tp), ptr(w), ptr(b), ptr(beta_c), n_bands, int(bool(with_color)),
+           ptr(sdf), ptr(sigma), ptr(albedo), ptr(acts), M, _ARITH[b3])
     return sdf, sigma, albedo, acts
 
 
-# Arithmetic of the fused field backward in the b3 mode: the bf16 pipe like every other MLP kernel of the mode (mh_field_bwd_fused_b3),
+# Arithmetic of the fused field backward in the b3 mode: the bf16 pipe like every other MLP kernel of the mode (arith = MH_ARITH_B3),
 # both passes -- colour + sdf (cfg3's: 2.13 -> 1.78 ms) and sdf-only (the finite-difference taps, 12 of every 13 points of a
 # training step: virtual-view 72 x 72 2.56 -> 1.88 ms).  Same-box A/Bs: profiles/r04_ab_field_bwd_b3.txt.  The colour + sdf pass
 # only won once the weight gradient of the sdf net's geo rows had moved into the colour launch: before, the sliced sdf launch
 # spilled 91 registers beside its 192 accumulators and measured equal to the fp32 form.
-# MORPHEUS_FIELD_BWD = "f32" keeps the native fp32 MFMA form (mh_field_bwd_fused; what the f32 mode always uses), "sdf" the
+# MORPHEUS_FIELD_BWD = "f32" keeps the native fp32 MFMA form (what the f32 mode always uses), "sdf" the
 # sliced form for the sdf-only pass alone (A/B).
 # The colour + sdf pass of "b3" runs the PAIR form of the two launches (two waves per SIMD, csrc/mlp.hip field_pair_*_kernel;
 # bit-identical outputs; same-box A/B in profiles/r07_field_bwd_pair.txt).  "b3w1" keeps the one-wave kernels for that pass too
@@ -1617,10 +1554,10 @@ def _field_bwd(lib, xc, wT, beta_c, acts, sdf, albedo, g_sdf, g_sigma, g_albedo,
         want = _PAIR_NEVER if FIELD_BWD == "b3w1" else _pair_min_default
         if lib.mh_field_bwd_pair_min_points(-1) != want:
             lib.mh_field_bwd_pair_min_points(want)
-    _timed("mh_field_bwd_fused_b3" if b3 else "mh_field_bwd_fused", ptr(xc), ptr(sdf), ptr(albedo if with_color else None), ptr(c(g_sdf)),
-           ptr(c(g_sigma)), ptr(c(g_albedo)), ptr(wT), ptr(beta_c), n_bands, int(with_color), ptr(acts), ptr(dgeo), ptr(ws),
+    _timed("mh_field_bwd_fused", ptr(xc), ptr(sdf), ptr(albedo if with_color else None), ptr(c(g_sdf)), ptr(c(g_sigma)),
+           ptr(c(g_albedo)), ptr(wT), ptr(beta_c), n_bands, int(with_color), ptr(acts), ptr(dgeo), ptr(ws),
            ptr(raw) if raw_into is None else ctypes.c_void_p(raw_into), int(raw_into is not None), ptr(g_xc), ptr(g_fs), ptr(g_fc),
-           ptr(g_tp), ptr(gmax), M, key="mh_field_bwd_fused")
+           ptr(g_tp), ptr(gmax), M, _ARITH[bool(b3)])
     return g_xc, g_fs, g_fc, g_tp, raw, gmax
 
 

@@ -329,7 +329,7 @@ class JointPacker:
       flat in   : [W of net 0 | W of net 1 | ... | b of net 0 | b of net 1 | ... | 0]        (natural, effective)
       fwd pack  : [A-fragments net 0 | net 1 | ... | bias pack net 0 | net 1 | ...]          -> `w[k]`, `b[k]` slices
       bwd pack  : [transposed fragments net 0 | net 1 | ...]                                 -> `wT[k]` slices
-      raw grads : [dW tiles net 0 | net 1 | ... | db tiles net 0 | net 1 | ...] (mh_mlp_wgrad's output) ->
+      raw grads : [dW tiles net 0 | net 1 | ... | db tiles net 0 | net 1 | ...] (mh_warp_wgrad's output) ->
       natural   : [dW net 0 | dW net 1 | ... | db net 0 | db net 1 | ...]
     """
 
@@ -460,7 +460,7 @@ class JointPacker:
         return buf[sl[0]:sl[0] + sl[1]]
 
     def unpack_grads(self, raw: torch.Tensor, zero_bias0: bool = False):
-        """raw [raw_len] = mh_mlp_wgrad's dw_raw | db_raw -> per net (list of natural dW, list of natural db), views of
+        """raw [raw_len] = mh_warp_wgrad's dW | db -> per net (list of natural dW, list of natural db), views of
         one gathered buffer.  zero_bias0: the first layer's bias gradient of every net comes out as zeros."""
         assert raw.numel() == self.raw_len
         if zero_bias0:

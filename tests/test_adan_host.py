@@ -228,7 +228,7 @@ def test_header_declares_the_adan_entry_points():
     raw = ctypes.CDLL(_lib.SO)
     for name in ("mh_adan_workspace_bytes", "mh_adan_step", "mh_adan_step_dev"):
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS and hasattr(raw, name), name
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
     assert "adan.hip" in build.SOURCES and build.FILE_FLAGS["adan.hip"] == ["-ffp-contract=off"]
     P, I32, I64, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
     assert lib.mh_adan_workspace_bytes.restype is I64 and list(lib.mh_adan_workspace_bytes.argtypes) == []

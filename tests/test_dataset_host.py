@@ -225,7 +225,7 @@ def test_library_takes_bad_dataset_arguments_without_a_launch():
     assert lib.mh_generate_rays_dev(1.0, 1.0, 0.0, 0.0, None, 2, 6, 8, None, 48, None, 0, *([None] * 4), None) == 1
     assert lib.mh_dataset_virtual_pose(0, *([None] * 4), 0, *([None] * 3), 5, 1.0, *([0.0] * 6), *([None] * 6), None) == 0
     assert lib.mh_dataset_virtual_pose(3, *([None] * 4), 2, *([None] * 3), 5, 1.0, *([0.0] * 6), *([None] * 6), None) == 1
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
 
 
 def test_dataset_source_is_built_without_contraction():

@@ -23,7 +23,7 @@ def _fns():
 def test_library_version_build_list_and_flags():
     from morpheus_amd import _lib, build
     lib, fns = _fns()
-    assert lib.mh_abi_version() == 9 and _lib._ABI == 9
+    assert lib.mh_abi_version() == 10 and _lib._ABI == 10
     assert "encoders.hip" in build.SOURCES
     assert build.FILE_FLAGS["encoders.hip"] == ["-ffp-contract=off"]
     for name in ("mh_freq_encode_fwd", "mh_freq_encode_bwd", "mh_sh_encode_fwd", "mh_sh_encode_bwd"):

@@ -834,7 +834,7 @@ def test_warp_sliced_arithmetic_against_float64(data, monkeypatch):
 
 @pytest.mark.parametrize("mlp", ["b3", "f32"])
 def test_warp_large_batch_weight_gradients(mlp, monkeypatch):
-    """The large-batch kernels of the warp path (from 16 384 tiles on mh_mlp_wgrad(_b3) launches one kernel per layer: the
+    """The large-batch kernels of the warp path (from 16 384 tiles on mh_warp_wgrad launches one kernel per layer: the
     slice-once-per-workgroup b3 kernel / the three-register-set fp32 kernel; the 8-wave forward / backward run hundreds of
     workgroups per CU) against the small-batch forms the oracle tests pin: one call on 600 000 points must give the same
     outputs, d/dx and parameter gradients as the same points fed in six chunks (same terms, different kernels and order)."""
@@ -874,7 +874,7 @@ def test_warp_large_batch_weight_gradients(mlp, monkeypatch):
         assert float((ga - gb).abs().max()) / scale <= 2e-5, (tuple(gb.shape), float((ga - gb).abs().max()) / scale)
     if mlp == "b3":
         # round 6: at this size backward-data does not park dPre4 and the layer-4 weight-gradient launches regenerate it from the
-        # incoming gradient, the ReLU sign words and the T5 slices (mh_warp_wgrad_b3) -- the SAME BITS as reading the parked rows,
+        # incoming gradient, the ReLU sign words and the T5 slices (mh_warp_wgrad, regen_dpre4) -- the SAME BITS as reading the parked rows,
         # also when one net has no incoming gradient at all
         assert ops.REGEN_DPRE4 and ops._lib.load().mh_warp_regen_dpre4(M) == 1 and ops._lib.load().mh_warp_regen_dpre4(CH) == 0
         monkeypatch.setattr(ops, "REGEN_DPRE4", False)

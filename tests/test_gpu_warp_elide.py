@@ -215,7 +215,8 @@ def test_two_slots_read_dpre0_rows_and_elide_nothing():
 
 
 def test_switches_and_the_small_batch_refusal():
-    """mh_warp_elides follows both switches and the size; an elided tile handed to the merged small-batch kernels is MH_ERR_ARG"""
+    """mh_warp_elides follows both switches and the size.  (An elided tile handed to the merged small-batch kernels is MH_ERR_ARG:
+    host-validated, tests/test_host.py::test_mlp_entries_validate_arithmetic_and_flags_without_gpu.)"""
     from morpheus_amd import ops
     lib = ops._lib.load()
     assert lib.mh_warp_elide_zero_lines(-1) == 2 and lib.mh_warp_elides(BIG) == 2 and lib.mh_warp_elides(257) == 0
@@ -226,9 +227,3 @@ def test_switches_and_the_small_batch_refusal():
     finally:
         lib.mh_warp_elide_zero_lines(2)
         lib.mh_warp_skip_zero_lines(1)
-    M = 257
-    buf = torch.zeros(max(lib.mh_warp_acts_floats(M), lib.mh_warp_wgrad_workspace_floats(M), 1 << 20), device=DEV)
-    p = buf.data_ptr()
-    assert lib.mh_warp_wgrad_b3_elide(p, p, None, None, p, p, 0, 1, p, p, p + 4 * 200000, M, None) == 1
-    assert lib.mh_warp_bwd_data_b3_elide(p, None, None, p, p, 6, p, p, None, M, 0, 1, None) == 1
-    assert lib.mh_warp_fwd_b3_elide(p, None, p, p, p, p, p, p, 6, p, p, p, M, 1, None) == 1

@@ -2,7 +2,7 @@
 
 The forward parks, per tile, net, hidden layer and lane half, a 64-bit word saying which of the layer's 128 parked rows (one
 128-byte line of 32 points each) carry a non-zero (csrc/mlp_b3.hip: b3_park_line_word); the per-layer kernels of
-mh_warp_wgrad_b3 fetch a zero line in place of a row whose bit is 0 (csrc/mlp.hip: wg_line_ptr), for H rows and for the dPre rows
+mh_warp_wgrad fetch a zero line in place of a row whose bit is 0 (csrc/mlp.hip: wg_line_ptr), for H rows and for the dPre rows
 masked by the same ReLU signs.  Points are consecutive samples of synthetic rays (tools/parked_line_zeros.py), as in training:
 only then do whole lines vanish.
 

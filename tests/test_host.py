@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(raw, name), f"{name} declared in include/morpheus_hip.h but not exported"
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
     assert lib.mh_status_string(1).decode().startswith("invalid argument")
     # size queries are pure host functions
     assert lib.mh_mlp_tiles(1) == 4 and lib.mh_mlp_tiles(129) == 8
@@ -52,8 +52,8 @@ def test_argument_validation_without_gpu(lib):
     assert lib.mh_grid_stage_min_points(before) == before
     assert lib.mh_composite_fwd(*([None] * 10), 0, None) == 0
     assert lib.mh_composite_fwd(*([None] * 10), 5, None) == 1
-    assert lib.mh_warp_fwd(*([None] * 8), 6, None, None, None, 128, None) == 1
-    assert lib.mh_field_fwd(*([None] * 7), 7, 1, None, None, None, None, 128, None) == 1        # n_bands > 6
+    assert lib.mh_warp_fwd(*([None] * 8), 6, None, None, None, 128, 0, 0, None) == 1
+    assert lib.mh_field_fwd(*([None] * 7), 7, 1, None, None, None, None, 128, 0, None) == 1     # n_bands > 6
     # round-3 entry points: the caller-side glue kernels and the graph pass
     assert lib.mh_masked_mean_fwd(9, None, None, None, 0, 1, None, None, None, None) == 1                # unknown kind
     assert lib.mh_masked_mean_fwd(4, None, None, None, 0, 2, None, None, None, None) == 1                # eikonal rows are [M,3]
@@ -68,6 +68,83 @@ def test_argument_validation_without_gpu(lib):
     assert lib.mh_render_loss_fwd(*([None] * 9), 5, 1.0, 1.0, 1.0, None, None, None, None) == 1
     assert lib.mh_render_loss_bwd(*([None] * 7), 0, 1.0, 1.0, 1.0, None, None, None, None, None) == 0
     assert lib.mh_graph_count_memset_nodes(None, None, None, None) == 1 and lib.mh_graph_replace_memset_nodes(None, None) == 1
+
+
+REMOVED_MLP_ENTRIES = ("mh_warp_fwd_b3", "mh_warp_fwd_b3_elide", "mh_warp_bwd_data_b3", "mh_warp_bwd_data_b3_elide", "mh_mlp_wgrad",
+                       "mh_mlp_wgrad_b3", "mh_mlp_wgrad_workspace_floats", "mh_warp_wgrad_b3", "mh_warp_wgrad_b3_elide",
+                       "mh_field_fwd_b3", "mh_field_bwd_fused_b3")
+
+
+def _mlp_entries(lib, p):
+    """name -> call(M, arith, *flags) of the five MLP entry points, every pointer argument = `p` (an address or None)"""
+    return {
+        "mh_warp_fwd": lambda M, arith, elide=0: lib.mh_warp_fwd(p, None, p, p, p, p, p, p, 6, p, p, p, M, arith, elide, None),
+        "mh_warp_bwd_data": lambda M, arith, skip_dpre4=0, elided=0: lib.mh_warp_bwd_data(p, None, None, p, p, 6, p, p, None, M, arith,
+                                                                                           skip_dpre4, elided, None),
+        "mh_warp_wgrad": lambda M, arith, regen_dpre4=0, elided=0: lib.mh_warp_wgrad(
+            p, p, None, None, *((p, p) if arith else (None, None)), arith, regen_dpre4, elided, p, p, M, None),
+        "mh_field_fwd": lambda M, arith: lib.mh_field_fwd(p, p, p, None, p, p, p, 6, 1, p, p, p, p, M, arith, None),
+        "mh_field_bwd_fused": lambda M, arith: lib.mh_field_bwd_fused(p, p, p, p, p, p, p, p, 6, 1, p, p, p, p, 0, p, p, p, None, None,
+                                                                      M, arith, None),
+    }
+
+
+def test_mlp_entries_validate_arithmetic_and_flags_without_gpu(lib):
+    """One entry point per MLP pass (ABI 10): `arith` is 0 (fp32 MFMA) or 1 (b3), the b3-only flags are refused with arith = 0, an
+    eliding flag needs a batch of the per-layer weight-gradient path, an empty call is fine.  Status codes from the host-side
+    checks: nothing is launched and no pointer is followed (the addresses are host memory)."""
+    buf = np.zeros(64, dtype=np.float32)
+    calls = _mlp_entries(lib, buf.ctypes.data)
+    assert not buf.any()
+    for name, call in calls.items():
+        assert call(128, 2) == 1, name                       # neither arithmetic
+        assert call(128, -1) == 1, name
+        assert call(0, 0) == 0 and call(0, 1) == 0, name     # M = 0
+        assert call(-1, 0) == 1 and call(-1, 1) == 1, name
+    assert calls["mh_warp_fwd"](128, 0, 1) == 1                              # arith = 0, elide = 1
+    assert calls["mh_warp_bwd_data"](128, 0, 1, 0) == 1                      # arith = 0, skip_dpre4 = 1
+    assert calls["mh_warp_bwd_data"](128, 0, 0, 1) == 1
+    assert calls["mh_warp_wgrad"](128, 0, 1, 0) == 1                         # arith = 0, regen_dpre4 = 1
+    assert calls["mh_warp_wgrad"](128, 0, 0, 1) == 1
+    p = buf.ctypes.data                                                      # arith = 0 takes none of the four b3-only pointers
+    assert lib.mh_warp_wgrad(p, p, None, None, p, p, 0, 0, 0, p, p, 128, None) == 1
+    assert lib.mh_warp_wgrad(p, p, p, None, None, None, 0, 0, 0, p, p, 128, None) == 1
+    # an eliding writer / reader on a batch that the per-layer weight-gradient kernels do not serve (these three were asserted
+    # beside the GPU tests of eliding before the entries were folded)
+    M = 257
+    assert not lib.mh_warp_regen_dpre4(M)
+    assert calls["mh_warp_wgrad"](M, 1, 0, 1) == 1
+    assert calls["mh_warp_bwd_data"](M, 1, 0, 1) == 1
+    assert calls["mh_warp_fwd"](M, 1, 1) == 1
+    assert calls["mh_warp_wgrad"](M, 1, 1, 0) == 1 and calls["mh_warp_bwd_data"](M, 1, 1, 0) == 1      # nor is dPre4 regenerated there
+    assert not buf.any()
+
+
+def test_warp_geometry_is_stated_by_the_library(lib):
+    """The warp and field tile geometry lives in csrc/ (mlp_dev.h, mlp.hip: warp_wg_geometry); Python asks for it.  chunking.py
+    is used without the library and keeps literals: they are pinned to the library's queries here."""
+    from morpheus_amd import chunking, ops, packing
+    assert lib.mh_warp_raw_floats() == packing.warp_joint_packer().raw_len
+    assert chunking.WARP_PARK_BYTES == (lib.mh_warp_acts_floats(128) + lib.mh_warp_dpre_floats(128)) * 4 // 128
+    assert chunking.FIELD_PARK_BYTES - 300 == lib.mh_field_acts_floats(128) * 4 // 128
+    assert lib.mh_warp_dpre_floats(1) // (lib.mh_mlp_tiles(1) * 32) == 2 * 672      # rows of a dPre tile (ops._WarpMLP.backward)
+    for name in ("_wgrad", "_warp_wg_geometry", "_WARP_WG", "WARP_ACT_ROWS", "WARP_DPRE_ROWS", "FIELD_ACT_ROWS"):
+        assert not hasattr(ops, name), name
+
+
+def test_removed_mlp_entries_are_gone(lib):
+    """None of the eleven entry points that ABI 10 folded is declared by the header or exported by the built library."""
+    from morpheus_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "morpheus_hip.h")).read()
+    code = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    declared = set(re.findall(r"\b(mh_[a-zA-Z0-9_]+)\s*\(", code))
+    raw = ctypes.CDLL(os.path.join(ROOT, "morpheus_amd", "_build", "libmorpheus_hip.so"))
+    assert len(REMOVED_MLP_ENTRIES) == 11
+    for name in REMOVED_MLP_ENTRIES:
+        assert name not in declared and name not in _lib.EXPORTS, name
+        assert not hasattr(raw, name), f"{name} is still exported"
+    for name in ("warp_fwd_f32", "warp_bwd_data_f32", "field_fwd_f32"):           # the launchers between mlp.hip and mlp_b3.hip
+        assert not hasattr(raw, name), f"{name} is exported"
 
 
 def _declared_parameter_counts(hdr):
@@ -114,9 +191,9 @@ def test_header_parser_refuses_what_it_cannot_type(lib):
     """A declaration outside the parser's closed type table, or one it cannot read at all, raises and names the declaration; so
     does a library whose ABI version is not the header's.  Fed with text: the real header is not touched."""
     from morpheus_amd import _lib
-    head = "#define MH_ABI_VERSION 9   /* history */\nint mh_abi_version(void);\n"
+    head = "#define MH_ABI_VERSION 10   /* history */\nint mh_abi_version(void);\n"
     abi, sigs = _lib.parse_header(head + "double mh_ok(const double *a, double b, /* why */ float c, int d);  // trailing\n")
-    assert abi == 9 and list(sigs) == ["mh_abi_version", "mh_ok"]
+    assert abi == 10 and list(sigs) == ["mh_abi_version", "mh_ok"]
     assert sigs["mh_ok"] == (ctypes.c_double, [ctypes.c_void_p, ctypes.c_double, ctypes.c_float, ctypes.c_int32])
     for bad in ("int mh_bad(size_t n);", "int mh_bad(struct mh_box b);", "int mh_bad(unsigned int a);", "int mh_bad(int);",
                 "int mh_bad();", "void mh_bad(int a);", "float *mh_bad(void);", "int mh_bad(int (*cb)(int));",
@@ -126,15 +203,15 @@ def test_header_parser_refuses_what_it_cannot_type(lib):
     with pytest.raises(_lib.MorpheusHipError, match="MH_ABI_VERSION"):
         _lib.parse_header("int mh_abi_version(void);")
     hdr = open(os.path.join(ROOT, "include", "morpheus_hip.h")).read()
-    assert hdr.count("#define MH_ABI_VERSION 9 ") == 1
-    with pytest.raises(_lib.MorpheusHipError, match=r"ABI version 9, include/morpheus_hip\.h declares 10"):
-        _lib.bind(ctypes.CDLL(_lib.SO), hdr.replace("#define MH_ABI_VERSION 9 ", "#define MH_ABI_VERSION 10 "))
+    assert hdr.count("#define MH_ABI_VERSION 10 ") == 1
+    with pytest.raises(_lib.MorpheusHipError, match=r"ABI version 10, include/morpheus_hip\.h declares 11"):
+        _lib.bind(ctypes.CDLL(_lib.SO), hdr.replace("#define MH_ABI_VERSION 10 ", "#define MH_ABI_VERSION 11 "))
     assert set(_lib.bind(ctypes.CDLL(_lib.SO))) == set(_lib.EXPORTS)                        # a side handle gets the same table
 
 
 def test_launch_names_the_entry_point_it_called(lib, monkeypatch):
     """_lib.launch / ops._timed append the stream, check the status and name the function they CALLED (a hand-written label had
-    drifted: mh_mlp_wgrad_b3 was reported as mh_mlp_wgrad).  Host-validated bad arguments: no device, no launch."""
+    drifted: one entry point was reported under another's name).  Host-validated bad arguments: no device, no launch."""
     from morpheus_amd import _lib, ops
     monkeypatch.setattr(_lib, "_CUR_DEVICE", lambda: 0)                                      # the current stream without a device
     monkeypatch.setattr(_lib, "_RAW_STREAM", lambda device: None)
@@ -143,8 +220,8 @@ def test_launch_names_the_entry_point_it_called(lib, monkeypatch):
     with pytest.raises(_lib.MorpheusHipError, match=r"^mh_composite_fwd: invalid argument .*\(status 1\)$"):
         _lib.launch("mh_composite_fwd", *([None] * 10), 5)
     assert not ops.TIMER.enabled
-    with pytest.raises(_lib.MorpheusHipError, match=r"^mh_warp_fwd_b3: invalid argument"):    # the function, not the timer key
-        ops._timed("mh_warp_fwd_b3", *([None] * 8), 7, None, None, None, 128, key="mh_warp_fwd")
+    with pytest.raises(_lib.MorpheusHipError, match=r"^mh_warp_wgrad: invalid argument"):     # the function, not the timer key
+        ops._timed("mh_warp_wgrad", *([None] * 6), 2, 0, 0, None, None, 128, key="mh_mlp_wgrad[warp]")
     with pytest.raises(KeyError):
         _lib.launch("mh_no_such_entry_point")
     with pytest.raises(_lib.MorpheusHipError, match=r"^label: invalid argument"):            # the plain form tools and tests use

@@ -195,7 +195,7 @@ def test_header_and_build_list_the_new_entry_points():
                  "mh_icp_wsums_workspace_bytes", "mh_icp_wsums"):
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS, name
     assert "poseinit.hip" in build.SOURCES and build.FILE_FLAGS["poseinit.hip"] == ["-ffp-contract=off"]
-    assert hdr.count("#define MH_ABI_VERSION 9 ") == 1
+    assert hdr.count("#define MH_ABI_VERSION 10 ") == 1
     import ctypes
     sig = _lib._DECLARED["mh_icp_wsums"]
     assert sig[1][6] is ctypes.c_double and len(sig[1]) == 10      # inv_2nu2 is a host double

@@ -315,7 +315,7 @@ def test_library_takes_bad_preprocess_arguments_without_a_launch():
         args = list(ok)
         args[at] = bad
         assert lib.mh_prep_frames(*args, None) == 1, (at, bad)
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
 
 
 def test_preprocess_source_is_built_without_contraction():

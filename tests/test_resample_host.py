@@ -186,7 +186,7 @@ def test_entry_points_are_declared_and_abi_unchanged():
     from morpheus_amd import _lib
     for name in ("mh_resample_stage", "mh_sample_pdf", "mh_resample_ranges", "mh_resample_packed"):
         assert name in _lib.EXPORTS
-    assert _lib._ABI == 9
+    assert _lib._ABI == 10
     lib = _lib.load()
     # the LDS staging holds the longest ray the shipped step marches in the shipped boxes
     assert int(lib.mh_resample_stage()) == 384 >= max(int(lib.mh_march_cap(0.01, 1.0)), int(lib.mh_march_cap(0.01, 1.01)))

@@ -103,7 +103,7 @@ def test_source_is_built_with_its_flag_and_exported(lib):
     from morpheus_amd import _lib, build
     assert "subdivide.hip" in build.SOURCES and build.FILE_FLAGS["subdivide.hip"] == ["-ffp-contract=off"]
     assert "mh_subdiv_count" in _lib.EXPORTS and "mh_subdiv_emit" in _lib.EXPORTS
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
 
 
 def test_argument_validation_without_gpu(lib):

@@ -150,7 +150,7 @@ def test_sparse_entry_points_are_declared_and_exported():
     raw = ctypes.CDLL(_lib.SO)
     for name in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS and hasattr(raw, name), name
-    assert hdr.count("#define MH_ABI_VERSION 9 ") == 1 and lib.mh_abi_version() == 9
+    assert hdr.count("#define MH_ABI_VERSION 10 ") == 1 and lib.mh_abi_version() == 10
     assert "tsdf_sparse.hip" in build.SOURCES and build.FILE_FLAGS["tsdf_sparse.hip"] == ["-ffp-contract=off"]
     P, I32, I64, Fl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     assert list(lib.mh_tsdf_sparse_integrate.argtypes) == [P, P, P, I32, I32, Fl, Fl, Fl, Fl, P, Fl, Fl, Fl, Fl, Fl, Fl, Fl, I32, I32,

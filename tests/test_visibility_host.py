@@ -108,7 +108,7 @@ def test_header_declares_the_entry_points_and_abi_is_still_9():
     with open(build.HEADER) as f:
         text = f.read()
     abi, sigs = _lib.parse_header(text)
-    assert abi == 9 and _lib._ABI == 9
+    assert abi == 10 and _lib._ABI == 10
     v = ctypes.c_void_p
     assert sigs["mh_visibility_mask"] == (ctypes.c_int32, [v, ctypes.c_int32, v, v, v, v, ctypes.c_int32, ctypes.c_int64,
                                                             ctypes.c_float, v, v, v, v])

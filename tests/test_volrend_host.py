@@ -238,14 +238,14 @@ NEW = ("mh_pack_info", "mh_ray_weights_fwd", "mh_ray_weights_bwd", "mh_accumulat
 def test_header_build_and_argument_checks():
     from morpheus_amd import _lib, build
     hdr = open(os.path.join(ROOT, "include", "morpheus_hip.h")).read()
-    assert hdr.count("#define MH_ABI_VERSION 9 ") == 1
+    assert hdr.count("#define MH_ABI_VERSION 10 ") == 1
     for name in NEW:
         assert len(re.findall(r"\b%s\s*\(" % name, hdr)) == 1 and name in _lib.EXPORTS
     assert "volrend.hip" in build.SOURCES and "volrend.hip" not in build.FILE_FLAGS           # the default flags
     assert "composite.hip" in build.SOURCES
     build.build()
     lib = _lib.load()
-    assert lib.mh_abi_version() == 9
+    assert lib.mh_abi_version() == 10
     # bad arguments: a status, no launch (there is no device here)
     assert lib.mh_pack_info(None, 0, 0, 0, None, None, None) == 0
     assert lib.mh_pack_info(None, 0, 5, 3, None, None, None) == 1

@@ -36,11 +36,11 @@ def run(M, n_slots, with_acts, scale=0.15):
 
         def call():
             if mode == "b3":
-                check(lib.mh_warp_fwd_b3(ptr(x), ptr(slot), ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6,
-                                         ptr(d), ptr(t), ptr(acts), M, stream()), "b3")
+                check(lib.mh_warp_fwd(ptr(x), ptr(slot), ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6,
+                                      ptr(d), ptr(t), ptr(acts), M, 1, 0, stream()), "b3")
             else:
                 check(lib.mh_warp_fwd(ptr(x), ptr(slot), ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), 6, ptr(d), ptr(t),
-                                      ptr(acts), M, stream()), "f32")
+                                      ptr(acts), M, 0, 0, stream()), "f32")
         call(); torch.cuda.synchronize()
         n = 10 if M > 500000 else 3
         t0 = time.perf_counter()

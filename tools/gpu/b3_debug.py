@@ -36,9 +36,9 @@ for mode in ("f32", "b3"):
     acts = torch.zeros(lib.mh_warp_acts_floats(M), device=dev)
     d, t = torch.empty(M, 3, device=dev), torch.empty(M, 2, device=dev)
     if mode == "b3":
-        check(lib.mh_warp_fwd_b3(ptr(x), None, ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, stream()), "b3")
+        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, 1, 0, stream()), "b3")
     else:
-        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, stream()), "f32")
+        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, 0, 0, stream()), "f32")
     torch.cuda.synchronize()
     outs[mode] = (d, t, acts.view(lib.mh_mlp_tiles(M), -1, 32))
 a0, a1 = outs["f32"][2], outs["b3"][2]
@@ -57,9 +57,9 @@ def go(mode):
     acts = torch.zeros(lib.mh_warp_acts_floats(M), device=dev)
     d, t = torch.empty(M, 3, device=dev), torch.empty(M, 2, device=dev)
     if mode == "b3":
-        check(lib.mh_warp_fwd_b3(ptr(x), None, ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, stream()), "b3")
+        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(op.w3[0]), ptr(op.w3[1]), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, 1, 0, stream()), "b3")
     else:
-        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, stream()), "f32")
+        check(lib.mh_warp_fwd(ptr(x), None, ptr(b0d), ptr(b0t), ptr(wd), ptr(wt), ptr(bd), ptr(bt), 6, ptr(d), ptr(t), ptr(acts), M, 0, 0, stream()), "f32")
     torch.cuda.synchronize()
     return acts.view(lib.mh_mlp_tiles(M), -1, 32)
 ref = go("f32")

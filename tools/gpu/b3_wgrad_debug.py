@@ -12,25 +12,29 @@ for nout in (3, 2):
 x = torch.rand(M, 3, device=DEV) * 2 - 1
 b0 = [torch.randn(1, 128, device=DEV) * 0.3 for _ in range(2)]
 wd_, wt_ = torch.randn(M, 3, device=DEV), torch.randn(M, 2, device=DEV)
-orig = ops._wgrad
-cap = {}
-def both(lib, acts, dpre, *a, **kw):
-    kw2 = dict(kw); kw2["b3"] = False
-    r32 = orig(lib, acts, dpre, *a, **kw2)
-    kw2["b3"] = True
-    r3 = orig(lib, acts, dpre, *a, **kw2)
-    cap["r32"], cap["r3"], cap["acts"], cap["dpre"] = r32, r3, acts, dpre
-    return r3
-ops._wgrad = both
+# the b3 forward and backward-data park the tiles (every row: no eliding, dPre4 parked); both arithmetic forms of mh_warp_wgrad read them
+from morpheus_amd.ops import ptr, stream, check
+lib = ops._lib.load()
 ops.set_mlp_mode("b3")
-ps = [[p.clone().requires_grad_(True) for p in net] for net in nets]
-d, t = ops.warp_mlp(x, None, b0[0], b0[1], 6, ops.prepare_warp_operands(ps[0], ps[1]))
-((d * wd_).sum() + (t * wt_).sum()).backward()
-r32, r3 = cap["r32"], cap["r3"]
+op = ops.prepare_warp_operands(nets[0], nets[1])
+acts, dpre = torch.zeros(lib.mh_warp_acts_floats(M), device=DEV), torch.zeros(lib.mh_warp_dpre_floats(M), device=DEV)
+d, t, g_x = torch.empty(M, 3, device=DEV), torch.empty(M, 2, device=DEV), torch.empty(M, 3, device=DEV)
+check(lib.mh_warp_fwd(ptr(x), None, ptr(b0[0]), ptr(b0[1]), ptr(op.w3[0]), ptr(op.w3[1]), ptr(op.b[0]), ptr(op.b[1]), 6, ptr(d), ptr(t),
+                      ptr(acts), M, 1, 0, stream()), "fwd")
+check(lib.mh_warp_bwd_data(ptr(x), ptr(wd_), ptr(wt_), ptr(op.wT3[0]), ptr(op.wT3[1]), 6, ptr(acts), ptr(dpre), ptr(g_x), M, 1, 0, 0,
+                           stream()), "bwd_data")
+ws = torch.empty(max(lib.mh_warp_wgrad_workspace_floats(M), 1), device=DEV)
+r32, r3 = torch.zeros(lib.mh_warp_raw_floats(), device=DEV), torch.zeros(lib.mh_warp_raw_floats(), device=DEV)
+check(lib.mh_warp_wgrad(ptr(acts), ptr(dpre), None, None, None, None, 0, 0, 0, ptr(ws), ptr(r32), M, stream()), "wgrad f32")
+check(lib.mh_warp_wgrad(ptr(acts), ptr(dpre), ptr(wd_), ptr(wt_), ptr(op.wT3[0]), ptr(op.wT3[1]), 1, 0, 0, ptr(ws), ptr(r3), M,
+                        stream()), "wgrad b3")
+torch.cuda.synchronize()
+cap = {"acts": acts, "dpre": dpre}
 print("acts finite", bool(torch.isfinite(cap["acts"].view(-1, 1384, 32)[:, :1344]).all()), "dpre finite", bool(torch.isfinite(cap["dpre"]).all()))
 print("raw len", r3.numel(), "nan in b3:", int(torch.isnan(r3).sum()), "nan in f32:", int(torch.isnan(r32).sum()))
 off = 0
-geo = ops._WARP_WG
+geo = (None, None, [64, 128, 128, 128, 128, 128] * 2, [128, 128, 128, 128, 128, 32] * 2)    # padded in / out rows (csrc/mlp.hip: warp_wg_geometry)
+assert sum(i * o + o for i, o in zip(geo[2], geo[3])) == r3.numel()
 for l, (i, o) in enumerate(zip(geo[2], geo[3])):
     n = i * o
     a, b = r3[off:off + n], r32[off:off + n]

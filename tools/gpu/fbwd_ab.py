@@ -5,7 +5,7 @@
     MORPHEUS_HIP_LIB=... python tools/gpu/fbwd_ab.py --one out.pt
 
 Cases: colour + sdf pass with d/dx (cfg3's call), colour + sdf without d/dx, sdf-only pass with and without d/dx (the finite-difference
-taps), M = 2 097 152 points each.  Compared: every output of mh_field_bwd_fused_b3 (g_xc, g_feat_s, g_feat_c, g_topo, raw weight / bias
+taps), M = 2 097 152 points each.  Compared: every output of mh_field_bwd_fused in the b3 arithmetic (g_xc, g_feat_s, g_feat_c, g_topo, raw weight / bias
 / beta gradients, gmax words) -- bit for bit where possible, else max relative difference."""
 import os
 import subprocess

@@ -118,23 +118,25 @@ def build_cases(M, dev):
     deform, topo = torch.empty(M, 3, device=dev), torch.empty(M, 2, device=dev)
     g_d, g_t, g_x = torch.randn(M, 3, device=dev), torch.randn(M, 2, device=dev), torch.empty(M, 3, device=dev)
     (bd, bt) = wop.b
-    n_tiles = lib.mh_mlp_tiles(M)
 
     def warp_fwd():
-        ops.check(lib.mh_warp_fwd_b3(ptr(x), None, ptr(b0[0]), ptr(b0[1]), ptr(wop.w3[0]), ptr(wop.w3[1]), ptr(bd), ptr(bt), 6, ptr(deform),
-                                     ptr(topo), ptr(acts), M, stream()), "fwd")
+        ops.check(lib.mh_warp_fwd(ptr(x), None, ptr(b0[0]), ptr(b0[1]), ptr(wop.w3[0]), ptr(wop.w3[1]), ptr(bd), ptr(bt), 6, ptr(deform),
+                                  ptr(topo), ptr(acts), M, 1, 0, stream()), "fwd")
 
     def warp_bwd():
-        ops.check(lib.mh_warp_bwd_data_b3(ptr(x), ptr(g_d), ptr(g_t), ptr(wop.wT3[0]), ptr(wop.wT3[1]), 6, ptr(acts), ptr(dpre), ptr(g_x), M, 0,
-                                          stream()), "bwd")
+        ops.check(lib.mh_warp_bwd_data(ptr(x), ptr(g_d), ptr(g_t), ptr(wop.wT3[0]), ptr(wop.wT3[1]), 6, ptr(acts), ptr(dpre), ptr(g_x), M, 1,
+                                       0, 0, stream()), "bwd")
 
-    def warp_wgrad():
-        ops._wgrad(lib, acts, dpre, ops.WARP_ACT_ROWS * 32, ops.WARP_DPRE_ROWS * 32, ops._WARP_WG[0], ops._WARP_WG[1], ops._WARP_WG[2],
-                   ops._WARP_WG[3], n_tiles, dev, "warp", b3=True)
+    ws = torch.empty(max(lib.mh_warp_wgrad_workspace_floats(M), 1), device=dev)
+    raw = torch.empty(lib.mh_warp_raw_floats(), device=dev)
 
-    cases["mh_warp_fwd_b3"] = warp_fwd
-    cases["mh_warp_bwd_data_b3"] = warp_bwd
-    cases["mh_mlp_wgrad_b3[warp]"] = warp_wgrad
+    def warp_wgrad():          # dPre4 was parked above (skip_dpre4 = 0): nothing is regenerated
+        ops.check(lib.mh_warp_wgrad(ptr(acts), ptr(dpre), ptr(g_d), ptr(g_t), ptr(wop.wT3[0]), ptr(wop.wT3[1]), 1, 0, 0, ptr(ws), ptr(raw),
+                                    M, stream()), "wgrad")
+
+    cases["mh_warp_fwd[b3]"] = warp_fwd
+    cases["mh_warp_bwd_data[b3]"] = warp_bwd
+    cases["mh_warp_wgrad[b3]"] = warp_wgrad
     # ---- field nets
     Ws = [torch.randn(64, 73, device=dev) * 0.2, torch.randn(64, 64, device=dev) * 0.2, torch.randn(33, 64, device=dev) * 0.2]
     Wc = [torch.randn(64, 64, device=dev) * 0.2, torch.randn(64, 64, device=dev) * 0.2, torch.randn(3, 64, device=dev) * 0.2]
@@ -156,8 +158,8 @@ def build_cases(M, dev):
         sdf, sigma, albedo, facts = state["f"]
         ops._field_bwd(lib, x, wT, beta, facts, sdf, albedo, g_sdf, g_sig, g_alb, 6, True, True, True, True, fop.jp, b3=b3)
 
-    cases["mh_field_fwd_b3"] = field_fwd
-    cases["mh_field_bwd_fused_b3"] = field_bwd
+    cases["mh_field_fwd[b3]"] = field_fwd
+    cases["mh_field_bwd_fused[b3]"] = field_bwd
     # ---- hash grid backward (one table, d/dx)
     from morpheus_amd import synth
     from morpheus_amd.ops import level_resolutions

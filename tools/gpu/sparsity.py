@@ -12,17 +12,21 @@ o, d, t, rid = [v.to(dev) for v in synth.frame_rays(0, HW, HW)]
 N = o.shape[1]
 rend = harness.make_renderer(model, S, jitter=synth.ray_jitter(N).to(dev))
 timg, tdep = [v.to(dev) for v in synth.targets(N)]
-cap = {}
-orig = ops._wgrad
-def spy(lib, acts, dpre, *a, **kw):
-    if kw.get("b3") is not None and a[-1] == "warp" or (len(a) >= 10 and a[9] == "warp"):
-        cap["acts"], cap["dpre"] = acts, dpre
-    return orig(lib, acts, dpre, *a, **kw)
-ops._wgrad = spy
-res = rend.render_rays(o, d, t, rid, HW, HW, ambient_ratio=1.0, shading="albedo", light_d=torch.nn.functional.normalize(o[0] + 0.3, dim=-1))
-harness.bench_loss(res, timg, tdep).backward()
 lib = _lib.load()
 M = N * S
+lib.mh_warp_elide_zero_lines(0)            # every parked line is written: the tiles are read whole below
+# the warp call on the M render samples parks its tiles in scratch buffers of these sizes
+want = {lib.mh_warp_acts_floats(M): "acts", lib.mh_warp_dpre_floats(M): "dpre"}
+cap = {}
+orig = ops._scratch
+def spy(n, device, dtype=torch.float32):
+    buf = orig(n, device, dtype)
+    if int(n) in want:
+        cap[want[int(n)]] = buf
+    return buf
+ops._scratch = spy
+res = rend.render_rays(o, d, t, rid, HW, HW, ambient_ratio=1.0, shading="albedo", light_d=torch.nn.functional.normalize(o[0] + 0.3, dim=-1))
+harness.bench_loss(res, timg, tdep).backward()
 nt = lib.mh_mlp_tiles(M)
 a = cap["acts"].view(nt, -1, 32); dp = cap["dpre"].view(nt, -1, 32)
 print("tiles", nt)

@@ -30,7 +30,7 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 for it in range(int(os.environ.get('MH_TRACE_ITERS', '3'))):
     e0.record()
     rc = lib.mh_warp_fwd(x.data_ptr(), None, b0d.data_ptr(), b0t.data_ptr(), wd.data_ptr(), wt.data_ptr(), bd.data_ptr(),
-                         bt.data_ptr(), 6, deform.data_ptr(), topo.data_ptr(), None if acts is None else acts.data_ptr(), M, st)
+                         bt.data_ptr(), 6, deform.data_ptr(), topo.data_ptr(), None if acts is None else acts.data_ptr(), M, 0, 0, st)
     e1.record()
     torch.cuda.synchronize()
     assert rc == 0

@@ -32,9 +32,9 @@ st = torch.cuda.current_stream().cuda_stream
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 for it in range(4):
     e0.record()
-    rc = lib.mh_warp_fwd_b3(x.data_ptr(), None, b0d.data_ptr(), b0t.data_ptr(), op.w3[0].data_ptr(), op.w3[1].data_ptr(),
-                            op.b[0].data_ptr(), op.b[1].data_ptr(), 6, deform.data_ptr(), topo.data_ptr(),
-                            None if acts is None else acts.data_ptr(), M, st)
+    rc = lib.mh_warp_fwd(x.data_ptr(), None, b0d.data_ptr(), b0t.data_ptr(), op.w3[0].data_ptr(), op.w3[1].data_ptr(),
+                         op.b[0].data_ptr(), op.b[1].data_ptr(), 6, deform.data_ptr(), topo.data_ptr(),
+                         None if acts is None else acts.data_ptr(), M, 1, 0, st)
     e1.record(); torch.cuda.synchronize(); assert rc == 0
 print("kernel ms %.3f (stamped build)%s" % (e0.elapsed_time(e1), " WITHOUT parking" if acts is None else ""))
 buf = (ctypes.c_longlong * (256 * 64))()
