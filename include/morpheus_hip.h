@@ -1265,6 +1265,30 @@ int mh_sds_grad(const float *noise_preds, const float *ws, const float *noise, c
                 int32_t T, const float *scale, float guidance_scale, int32_t R, int32_t B, int64_t n, float *grad,
                 double *partials, uint32_t *ticket, float *loss, void *stream);
 
+/* ---- video output: baseline JPEG frames (csrc/video.hip; morpheus_amd/video.py is its Python face) ---------------------------
+ * Purely additive: MH_ABI_VERSION is unchanged.  csrc/video.hip's header is the definition -- colour transform, sub-sampling,
+ * integer DCT, quantiser, scan order, entropy coder, each with its rounding -- and tests/video_oracle.py restates it; the two agree
+ * byte for byte.  Integer arithmetic only.
+ * mh_jpeg_blocks: the 8 x 8 blocks of one frame of H x W pixels (1 .. 65535) with `channels` = 1 (one component) or 3 (RGB ->
+ *   YCbCr, `subsampling` 420 or 444; ignored for one channel); -1 for other arguments or more blocks than a frame's int32 bit
+ *   count allows (1 295 225).
+ * mh_jpeg_scan_capacity: the proven worst case of one frame's entropy-coded segment in bytes, a multiple of 32: a block is at
+ *   most 20 + 63 * 26 = 1658 bits and byte stuffing at most doubles the bytes.  -1 for blocks outside [1, 1 295 225].
+ * mh_jpeg_workspace_bytes: the scratch of one mh_jpeg_encode call with per-frame capacity cap; -1 for arguments it would refuse.
+ * mh_jpeg_quant_table: table int32 [64] on the HOST, natural order = the Annex K table (chroma: 0 luminance, 1 chrominance)
+ *   scaled by the IJG rule for quality 1 .. 100.
+ * mh_jpeg_encode: frames uint8 [F,H,W,channels] on the device (4-byte aligned, F <= 65535) -> out uint8 [F,cap]: frame f's
+ *   entropy-coded segment, stuffed and 1-padded, in out[f][0 .. nbytes[f]); the markers around it are the caller's.  cap: a
+ *   positive multiple of 32, mh_jpeg_scan_capacity(blocks) for a call that cannot overflow.  With a smaller cap every write is
+ *   still held inside out[f][0 .. cap) and the workspace, nbytes[f] <= cap, and *overflow (int32, device; cleared by the call)
+ *   becomes 1.  workspace: mh_jpeg_workspace_bytes(F, blocks, cap) bytes, 16-byte aligned.  Nine launches, no host read. */
+int64_t mh_jpeg_blocks(int32_t H, int32_t W, int32_t channels, int32_t subsampling);
+int64_t mh_jpeg_scan_capacity(int64_t blocks);
+int64_t mh_jpeg_workspace_bytes(int32_t F, int64_t blocks, int64_t cap);
+int mh_jpeg_quant_table(int32_t quality, int32_t chroma, int32_t *table);
+int mh_jpeg_encode(const uint8_t *frames, int32_t F, int32_t H, int32_t W, int32_t channels, int32_t subsampling, int32_t quality,
+                   void *workspace, uint8_t *out, int64_t cap, int32_t *nbytes, int32_t *overflow, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

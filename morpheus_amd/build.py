@@ -28,7 +28,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 SO = os.path.join(OUT_DIR, "libmorpheus_hip.so")
 SOURCES = ["hashgrid.hip", "hashgrid_general.hip", "composite.hip", "sampler.hip", "mlp.hip", "mlp_b3.hip", "optim.hip", "wnorm.hip", "normal.hip", "graph.hip", "losses.hip",
-           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip", "volrend.hip", "dataset.hip", "preprocess.hip", "estimator.hip", "resample.hip", "imageops.hip", "guidance.hip"]
+           "mesh.hip", "raster.hip", "mesheval.hip", "subdivide.hip", "tsdf.hip", "tsdf_sparse.hip", "visibility.hip", "adan.hip", "poseinit.hip", "encoders.hip", "volrend.hip", "dataset.hip", "preprocess.hip", "estimator.hip", "resample.hip", "imageops.hip", "guidance.hip", "video.hip"]
 HEADER = os.path.join(HERE, "..", "include", "morpheus_hip.h")      # the C ABI; _lib.py binds the library from this text
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent scalar fp32 adds / muls of the epilogues into v_pk_* instructions, which
 # cost more than two plain ones beside MFMAs (MI355X_MICROARCH.md); measured on one box, whole library, cfg3: 15.61 -> 15.38
@@ -54,6 +54,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # estimator.hip: un-contracted by its own pragma, like sampler.hip (tests/estimator_oracle.py states the operations)
 # resample.hip: un-contracted by its own pragma, the same way (tests/resample_oracle.py states the operations)
 # imageops.hip, guidance.hip: un-contracted by their own pragmas, the same way (tests/imageops_oracle.py, tests/guidance_oracle.py)
+# video.hip: integer arithmetic only (tests/video_oracle.py): nothing to contract, neither a pragma nor an entry here
 FILE_FLAGS = {"adan.hip": ["-ffp-contract=off"], "losses.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"], "raster.hip": ["-ffp-contract=off"],
               "mesheval.hip": ["-ffp-contract=off"], "subdivide.hip": ["-ffp-contract=off"], "tsdf.hip": ["-ffp-contract=off"],
               "tsdf_sparse.hip": ["-ffp-contract=off"], "poseinit.hip": ["-ffp-contract=off"], "encoders.hip": ["-ffp-contract=off"],

@@ -153,6 +153,28 @@ __device__ __forceinline__ float wave_excl_from_incl(float incl, float v, int la
     return v >= WAVE_OPAQUE_SD ? (lane ? below : 0.f) : incl - v;
 }
 
+// ---- workgroup exclusive scan of ints, built from the wave scan ------------------------------------------------------------
+// The sum of v over the threads below this one, in thread order, for a workgroup of NW whole wavefronts; *total = the sum over
+// the workgroup, the same in every thread.  Every thread of the workgroup must reach the call (two barriers; `lds`, NW ints
+// of shared memory, is free again when it returns).  Integer sums: no association order to state.
+template <int NW>
+__device__ __forceinline__ int block_excl_scan(int v, int *lds, int *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = wave_incl_scan(v, lane);
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    int below = 0, sum = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int s = lds[i];
+        if (i < wave) below += s;
+        sum += s;
+    }
+    __syncthreads();
+    *total = sum;
+    return below + incl - v;
+}
+
 // ---- ballot rank: the number of set bits of `mask` below `lane`, valid in every lane ------------------------------------
 __device__ __forceinline__ int wave_rank(unsigned long long mask, int lane) {
     return __popcll(mask & ((1ull << lane) - 1ull));

@@ -21,6 +21,7 @@ from ._lib import MorpheusHipError, launch, ptr
 from .geometry import (cv2gl, host_array, host_ptr, intrinsics, mesh_arrays, transform_points,  # noqa: F401  (cv2gl: re-exported)
                        world_to_camera)
 from .mesh import load_mesh
+from .video import VideoWriter
 
 MODES = {"color": 0, "normal": 1, "shaded": 2}
 MAX_SIDE = 16384
@@ -163,7 +164,7 @@ def render_all_meshes(meshes_or_dir, poses, K, H: int, W: int, save_images_dir: 
                       save_depths_dir: Optional[str] = None, scale: int = 4, epoch: Optional[int] = None,
                       convention: str = "opengl", mode: str = "shaded", near: float = 0.01,
                       background: Sequence[float] = (1.0, 1.0, 1.0), ambient: float = 0.3, device="cuda",
-                      keep_results: bool = False):
+                      keep_results: bool = False, video_path: Optional[str] = None, fps=20):
     """The loop of render_all_meshes (morpheus.py:418-470): mesh i is rendered from poses[i] at (scale*H) x (scale*W) with
     K[:2] * scale and the principal point at the image centre -- (scale*W/2, scale*H/2) here, where a pixel centre sits at
     (i + 0.5, j + 0.5); Open3D's set_K writes w/2 - 0.5 for the same point in its integer-centre convention.
@@ -172,8 +173,9 @@ def render_all_meshes(meshes_or_dir, poses, K, H: int, W: int, save_images_dir: 
     not touch the disk.  Writes {i:04d}.png under save_images_dir (needs PIL) and depths.npz with keys depth_{i} under
     save_depths_dir.  -> {"depth_{i}": host float32 [scale*H, scale*W]}, what depths.npz holds (the reference keeps no more
     than that across frames); with keep_results the list of render_mesh results instead, device tensors of 20 bytes per
-    pixel and frame.  The per-frame depth PNGs of capture_depth_image (morpheus.py:461) are not written; video encoding
-    stays with the caller."""
+    pixel and frame.  The per-frame depth PNGs of capture_depth_image (morpheus.py:461) are not written.  With video_path the
+    frames also go, from the device, to a Motion-JPEG .avi at `fps` (video.VideoWriter: what the reference's make_video makes
+    of the PNGs, morpheus.py:467-468); without it no video is written."""
     Image = None
     if save_images_dir is not None:
         try:
@@ -185,16 +187,28 @@ def render_all_meshes(meshes_or_dir, poses, K, H: int, W: int, save_images_dir: 
     fx, fy = K[0, 0] * scale, K[1, 1] * scale
     h, w = int(H * scale), int(W * scale)
     results, depths = [], {}
-    for i, mesh in mesh_sequence(meshes_or_dir, device, epoch):
-        out = render_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), mesh.get("normals"), c2w=poses[i], H=h, W=w,
-                          fx=fx, fy=fy, cx=w / 2.0, cy=h / 2.0, convention=convention, mode=mode, near=near,
-                          background=background, ambient=ambient)
-        if keep_results:
-            results.append(out)
-        depths[f"depth_{i}"] = out["depth"].cpu().numpy()
-        if Image is not None:
-            rgb = (out["image"].nan_to_num(0.0).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
-            Image.fromarray(rgb).save(os.path.join(save_images_dir, f"{i:04d}.png"))
+    writer = None
+    if video_path is not None:
+        writer = VideoWriter(video_path, fps)
+    done = False
+    try:
+        for i, mesh in mesh_sequence(meshes_or_dir, device, epoch):
+            out = render_mesh(mesh["vertices"], mesh["triangles"], mesh.get("colors"), mesh.get("normals"), c2w=poses[i], H=h, W=w,
+                              fx=fx, fy=fy, cx=w / 2.0, cy=h / 2.0, convention=convention, mode=mode, near=near,
+                              background=background, ambient=ambient)
+            if keep_results:
+                results.append(out)
+            depths[f"depth_{i}"] = out["depth"].cpu().numpy()
+            if Image is not None or writer is not None:
+                rgb = (out["image"].nan_to_num(0.0).clamp(0, 1) * 255).round().to(torch.uint8)
+                if writer is not None:
+                    writer.append(rgb)                             # coded from the device, batch by batch
+                if Image is not None:
+                    Image.fromarray(rgb.cpu().numpy()).save(os.path.join(save_images_dir, f"{i:04d}.png"))
+        done = True
+    finally:
+        if writer is not None:
+            writer.close(discard_pending=not done)
     if save_depths_dir is not None:
         os.makedirs(save_depths_dir, exist_ok=True)
         np.savez(os.path.join(save_depths_dir, "depths.npz"), **depths)
